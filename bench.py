@@ -2,6 +2,16 @@
 
 `python bench.py --gpus N --steps K --warmup W` prints ONE JSON line (rank 0).
 
+A plain run does only what the headline figure needs: it sets up, warms up,
+times the K steps and prints metric / value / unit / ms_per_step / config.
+`--dump-outputs DIR` also writes what the last timed step computed, the
+forward's logits [7,724 x 8] in float32, to DIR/logits.npy (fixture inputs and
+seeded weights: identical from run to run, so two builds can be compared
+output for output).  `--full` adds every other leg described below, outside
+the timed steps: eager_forward_us, config.factor_build_ms, roofline*,
+forward_kernels, ops, train_step_ms, setup_ms, cpu_baseline, cpu_stock_csr,
+gpu_stock, configs and config 5.
+
 Workload (BASELINE.json configs[1]): the R8 doc-topic graph exactly as the
 reference prepares it (tests/golden/r8_graph.npz, written by the reference's
 own builder and PrepareData in the build container; 7,724 nodes, Â nnz
@@ -88,6 +98,12 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every other leg (eager forward, per-op and roofline figures, "
+                         "rocprofv3 child runs, CPU and stock baselines, training step, setup costs, configs 3-5); "
+                         "the options below that steer those legs have no effect without it")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (the forward's logits) to DIR/<name>.npy")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of hipGraph replay")
     ap.add_argument("--graph-steps", type=int, default=10,
                     help="forwards captured per hipGraph (steps must be a multiple; amortises the per-replay floor)")
@@ -105,7 +121,10 @@ def parse():
     ap.add_argument("--cpu-child", default=None, help=argparse.SUPPRESS)   # internal: the pinned CPU leg
     ap.add_argument("--dry-run", action="store_true",
                     help="print each rank's launch view (rank, world) as JSON and exit before any GPU call")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def launch_ranks(args):
@@ -949,7 +968,7 @@ def main():
     first_forward_ms = (time.perf_counter() - tf) * 1e3
     a_csr, x_csr = as_csr(adj), as_csr(x)
     nnz_a, nnz_x = a_csr.nnz, x_csr.nnz
-    fb_r8 = factor_build_ms(a_csr, x)
+    fb_r8 = factor_build_ms(a_csr, x) if args.full else None
     if args.no_graph:
         step = forward
         per = 1
@@ -982,7 +1001,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps // per):
-        step()
+        last = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier(device_ids=[torch.cuda.current_device()])
@@ -992,6 +1011,44 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t)
+
+    # ---- what the last timed step computed: the forward's logits [N x nclass]
+    #      (a replayed graph leaves them in its captured output tensor)
+    if args.dump_outputs and rank == 0:
+        if args.no_graph:
+            out = last
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "logits.npy"), out.detach().float().cpu().numpy())
+
+    ms = elapsed / args.steps * 1e3
+    value = 2 * nnz_a * args.steps * world / elapsed
+    line = {
+        "metric": "SpMM edges/s and GCN-forward ms on R8 doc-topic graph, 1×MI355X",
+        "value": value,
+        "unit": "edges/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "R8 graph fixture generated in-container by the reference's own builder; random-init weights",
+        "config": {"workload": "R8 GCN forward (eval), hidden 200, 8 classes, nfeat 7463",
+                   "nodes": N, "adj_nnz": nnz_a, "x_nnz": nnz_x, "graph": not args.no_graph,
+                   "forwards_per_graph": per,
+                   "path": forward_path(a_csr, x, nhid, nclass),
+                   "factor_build_ms": fb_r8,
+                   "parallelism": f"replicas{world}" if world > 1 else "single"},
+        "full": args.full,
+    }
+    if not args.full:   # a plain run: the headline figure only
+        if rank == 0:
+            print(json.dumps(line))
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # ---- the forward as the reference's trainer issues it: eager calls, one
     #      model.forward per step (trainer.py:357,382), no graph -- host launch
@@ -1204,8 +1261,6 @@ def main():
     if (world > 1 or args.config5) and not args.no_configs:
         config5 = sharded_config5(dev, world, rank, datasets, ops)
 
-    ms = elapsed / args.steps * 1e3
-    value = 2 * nnz_a * args.steps * world / elapsed
     kn, kd = optimes[north], optimes[dom]
     # the slowest op of the product forward as it runs (its own launches in the
     # rocprofv3 trace, against that op's algorithmic bytes); the unfused per-op
@@ -1234,26 +1289,8 @@ def main():
             "hip_events": {"avg_call_us": kn["cold_us"], "avg_call_us_warm": kn["warm_us"],
                            "frac": kn["frac_cold"], "frac_warm": kn["frac_warm"]},
             "algorithmic_bytes": nb}
-    line = {
-        "metric": "SpMM edges/s and GCN-forward ms on R8 doc-topic graph, 1×MI355X",
-        "value": value,
-        "unit": "edges/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms,
+    line.update({
         "eager_forward_us": round(eager_us, 3),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "R8 graph fixture generated in-container by the reference's own builder; random-init weights",
-        "config": {"workload": "R8 GCN forward (eval), hidden 200, 8 classes, nfeat 7463",
-                   "nodes": N, "adj_nnz": nnz_a, "x_nnz": nnz_x, "graph": not args.no_graph,
-                   "forwards_per_graph": per,
-                   "path": forward_path(a_csr, x, nhid, nclass),
-                   "factor_build_ms": fb_r8,
-                   "parallelism": f"replicas{world}" if world > 1 else "single"},
         "roofline": roof,
         # the same op under rocprofv3: kernel time without the dispatch gap that the
         # per-call HIP-event figure above includes
@@ -1275,7 +1312,7 @@ def main():
         "gpu_stock": gpu_stock,
         "configs": configs,
         "config5_column_sharded": config5,
-    }
+    })
     if rank == 0:
         print(json.dumps(line))
     if world > 1:

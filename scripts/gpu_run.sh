@@ -7,8 +7,8 @@
 #   micro:<binary>[:<args>]   prebuilt scripts/micro/<binary> on the R8 A-hat (NS_ONLY, PROF honoured)
 #   test:<pytest -k expr>     GPU tests matching the expression (-m gpu)
 #   tests                     the whole GPU suite
-#   bench[:<args>]            python bench.py <args> (default --steps 200 --warmup 20) -> bench.json
-#   benchn:<name>:<args>      python bench.py <args> -> bench_<name>.json
+#   bench[:<args>]            python bench.py --full <args> (default --steps 200 --warmup 20) -> bench.json
+#   benchn:<name>:<args>      python bench.py <args> -> bench_<name>.json (a plain run unless <args> holds --full)
 #   prof:<script>[:<args>]    rocprofv3 --kernel-trace --stats over python scripts/<script> -> <script>_stats/
 #   py:<script>[:<args>]      python scripts/<script> <args> -> <script>.log
 #   vpy:<variant>:<script>[:<args>]  the same on _variants/libgcnk_<variant>.so
@@ -47,7 +47,7 @@ for step in "$@"; do
       rc=$?; tail -n 15 "$out/pytest_gpu.log"; [ $rc -eq 0 ] || { echo "rc=$rc"; exit 1; } ;;
     bench)
       args="${rest:---steps 200 --warmup 20}"
-      timeout -k 10 900 python -u bench.py $args --rocprof-dir "$out/bench_prof" > "$out/bench.json" 2> "$out/bench.err"
+      timeout -k 10 900 python -u bench.py --full $args --rocprof-dir "$out/bench_prof" > "$out/bench.json" 2> "$out/bench.err"
       rc=$?; tail -c 3000 "$out/bench.json"; [ $rc -eq 0 ] || { echo "rc=$rc"; tail -n 20 "$out/bench.err"; exit 1; } ;;
     benchn)   # benchn:<name>:<args>: python bench.py <args> -> bench_<name>.json (several per call)
       nm="${rest%%:*}"; args="${rest#*:}"

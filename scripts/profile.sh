@@ -3,6 +3,7 @@
 cd "${GRAFT_REPO_ROOT:-/root/repo}" || exit 2
 mkdir -p gpurun_out/prof
 export TMPDIR=/tmp
+BENCH_ARGS="--full ${BENCH_ARGS}"   # every leg of the bench, not only the timed forward
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof -o run -- \
   python3 bench.py --steps ${STEPS:-100} --warmup 10 --cpu-sample-s 0 ${BENCH_ARGS} > gpurun_out/prof/bench.log 2>&1
 rc=$?
