@@ -20,5 +20,9 @@ Modules:
   csr_ref   numpy float64 restatement from the math (CSR SpMM, adjacency
             normalisation, GEMM, column sums) for kernel-level parity.
   spmm_ref.c  plain-C CSR SpMM (double accumulation) for large parity cases,
-            built into oracle/liboracle.so by __graft_entry__.build().
+            built into oracle/liboracle.so by __graft_entry__.build(); also a
+            second writing of the dropout hash (oracle_hash_u24).
+  hash_ref  numpy restatement of the device dropout mask (include/gcnk.h,
+            GCNK_EPI_BIAS_RELU_HASH), pinned by tests/test_hash_ref.py and
+            used by tests/test_hash_dropout.py.
 """
