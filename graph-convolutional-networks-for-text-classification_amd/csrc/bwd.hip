@@ -39,13 +39,6 @@ constexpr int kBwdBatch = 8;       // rows per lane whose H1 loads are in flight
 #define GCNK_BWD_TARGET 256
 #endif
 constexpr int kBwdTarget = GCNK_BWD_TARGET;    // workgroups per slice (256: one per CU)
-// 1 (default): the row lanes' gW2 / gb1 partials summed as float4 pieces where P == PM
-#ifndef GCNK_BWD2_VSUM
-#define GCNK_BWD2_VSUM 1
-#endif
-#ifndef GCNK_BWD2_STAMPV   // stamps-build timeline variant (2: around the lane sum)
-#define GCNK_BWD2_STAMPV 1
-#endif
 
 template <int VEC>
 struct VecIO;
@@ -183,9 +176,7 @@ __global__ void __launch_bounds__(kBwdBlock) gcn_bwd2_kernel(Bwd2Args a) {
   }
   if (g_dma) __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): this wave's DMA (and loads) landed
   __syncthreads();
-#if GCNK_BWD2_STAMPV != 2
   stamp(a.stamps, 1);
-#endif
 
   for (int32_t b0 = rl; b0 < nr; b0 += RL * kBwdBatch) {
     // the batch's H1 loads first (one latency; the first batch's are in flight
@@ -226,13 +217,8 @@ __global__ void __launch_bounds__(kBwdBlock) gcn_bwd2_kernel(Bwd2Args a) {
     }
   }
 
-#if GCNK_BWD2_STAMPV == 2
-  stamp(a.stamps, 1);   // (variant timeline: 1 rows done, 2 after the lane-sum barrier, 3 partial stored)
-#else
   stamp(a.stamps, 2);
-#endif
   float* prow = a.part + (int64_t)blockIdx.x * a.part_ld;
-#if GCNK_BWD2_VSUM
   // P == PM with 16-B partial rows: the thread's VEC x PM gW2 terms then its VEC
   // gb1 terms as float4 pieces in LDS, each output float4 (8 of gW2 + 1 of gb1
   // per column unit) summed over the row lanes in lane order and stored as one
@@ -255,9 +241,6 @@ __global__ void __launch_bounds__(kBwdBlock) gcn_bwd2_kernel(Bwd2Args a) {
       mine[(VEC * PM + v) / 4] = g4;
     }
     __syncthreads();
-#if GCNK_BWD2_STAMPV == 2
-    stamp(a.stamps, 2);
-#endif
     const f32x4v* red = reinterpret_cast<const f32x4v*>(s_red);
     for (int e = tid; e < CT * KE4; e += kBwdBlock) {
       const int u = e / KE4, k4 = e - u * KE4;
@@ -273,9 +256,7 @@ __global__ void __launch_bounds__(kBwdBlock) gcn_bwd2_kernel(Bwd2Args a) {
           if (4 * (k4 - VEC * PM / 4) + i < VEC) prow[(int64_t)a.N * a.P + c0 + 4 * (k4 - VEC * PM / 4) + i] = sum[i];
       }
     }
-  } else
-#endif
-  {
+  } else {
   // row lanes -> one partial per column, summed in lane order
   {
     float* mine = s_red + tid * KE;
@@ -287,9 +268,6 @@ __global__ void __launch_bounds__(kBwdBlock) gcn_bwd2_kernel(Bwd2Args a) {
     }
   }
   __syncthreads();
-#if GCNK_BWD2_STAMPV == 2
-  stamp(a.stamps, 2);
-#endif
   for (int e = tid; e < CT * KE; e += kBwdBlock) {
     const int u = e / KE, k = e % KE;
     const int v = k / (PM + 1), p = k % (PM + 1);

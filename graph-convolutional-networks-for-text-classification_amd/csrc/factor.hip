@@ -73,17 +73,6 @@ struct FactorArgs {
   Epi epi;
 };
 
-// 1 (default): the item loop skips the last column slot where it lies past F
-// (R8: hubfactor_gc1 10.09 -> 9.78 us, profiles/r05_factor_lastu.log)
-#ifndef GCNK_FACTOR_LASTU
-#define GCNK_FACTOR_LASTU 1
-#endif
-
-// 1 (default): U's rows staged in LDS by DMA where the block's LDS allows
-#ifndef GCNK_FACTOR_ULDS
-#define GCNK_FACTOR_ULDS 1
-#endif
-
 template <int KS>
 __host__ __device__ constexpr int region1_floats(int F, int ntq) {
   return (4 * KS * F + bpad(F, ntq)) > kRB * (64 * ntq + 4) ? (4 * KS * F + bpad(F, ntq)) : kRB * (64 * ntq + 4);
@@ -225,11 +214,9 @@ hubfactor_gc1_kernel(FactorArgs a) {
       float4 sv[NTQ];
 #pragma unroll
       for (int u = 0; u < NTQ; ++u) {
-#if GCNK_FACTOR_LASTU
         // the last column slot only where it lies inside F (R8: 2 of 16 lanes):
         // inactive lanes move no LDS bytes, and this loop is LDS-bandwidth-bound
         if (u == NTQ - 1 && c16 + 16 * u >= Q) { sv[u] = make_float4(0.f, 0.f, 0.f, 0.f); continue; }
-#endif
         sv[u] = *reinterpret_cast<const float4*>(srow + 64 * u);
       }
 #pragma unroll
@@ -410,7 +397,7 @@ extern "C" int gcnk_hubfactor_gc1_f32(int32_t M, int32_t F, int32_t Kc, int32_t 
   a.M = M; a.F = F; a.Kc = Kc; a.nhub = nhub; a.P = P;
   // U's rows through LDS where they fit (R8: 95 + 8.7 KB; the 20ng-shaped 70
   // topic-weight columns at 152 KB take the direct loads)
-  a.u_lds = GCNK_FACTOR_ULDS && ldu % 4 == 0 && aligned16(U) && lds_b + hubfactor_u_bytes(Kc) <= 160 * 1024;
+  a.u_lds = ldu % 4 == 0 && aligned16(U) && lds_b + hubfactor_u_bytes(Kc) <= 160 * 1024;
   a.U = U; a.ldu = ldu; a.W = W; a.ldw = ldw; a.k0 = k0;
   a.S = S; a.lds = lds; a.rec = rec; a.rec_words = rec_words;
   a.W2 = W2; a.ldw2 = ldw2; a.H = H; a.ldh = ldh; a.C2 = C2; a.ldc2 = ldc2;

@@ -651,10 +651,7 @@ extern "C" int gcnk_gemm_f32(int32_t transA, int32_t transB, int32_t M, int32_t 
   GemmEpi e{bias, R, ldr, scale, epilogue};
   hipStream_t s = (hipStream_t)stream;
   const bool ta = transA != 0, tb = transB != 0;
-#ifndef GCNK_GEMM_NARROW_SHORTK
-#define GCNK_GEMM_NARROW_SHORTK 1
-#endif
-  if (GCNK_GEMM_NARROW_SHORTK && !ta && !tb && M >= 16384 && N > 16 && N <= 32 && N % 4 == 0 && K > 128 &&
+  if (!ta && !tb && M >= 16384 && N > 16 && N <= 32 && N % 4 == 0 && K > 128 &&
       K <= 256 && K % 4 == 0 && lda % 4 == 0 && ldb % 4 == 0 && aligned16(A) && aligned16(B) && split_k == 1) {
     // gc2's support H1 W2 at many rows ([nodes x 200] x [200 x classes]):
     // 64-row workgroups, each wave one whole K chain per output (no cross-wave
@@ -694,10 +691,7 @@ extern "C" int gcnk_gemm_f32(int32_t transA, int32_t transB, int32_t M, int32_t 
 #undef GCNK_SKINNY_KS
     return launch_check("gemm_skinny_ksplit_kernel");
   }
-#ifndef GCNK_GEMM_SHORTK
-#define GCNK_GEMM_SHORTK 1
-#endif
-  if (GCNK_GEMM_SHORTK && !ta && !tb && K > 0 && K <= 128 && K % 4 == 0 && N > 64 && N % 4 == 0 && lda % 4 == 0 &&
+  if (!ta && !tb && K > 0 && K <= 128 && K % 4 == 0 && N > 64 && N % 4 == 0 && lda % 4 == 0 &&
       ldb % 4 == 0 && aligned16(A) && aligned16(B) && split_k == 1) {
     const int64_t nrb8 = ((int64_t)M + 64 * 8 - 1) / (64 * 8);  // groups of 8 row blocks
     const dim3 grid((unsigned)(nrb8 * 8 * ((N + 16 * kShortkNT - 1) / (16 * kShortkNT))));
@@ -717,9 +711,6 @@ extern "C" int gcnk_gemm_f32(int32_t transA, int32_t transB, int32_t M, int32_t 
 #undef GCNK_SHORTK
     return launch_check("gemm_shortk_kernel");
   }
-#ifndef GCNK_GEMM_SMALLM_WK
-#define GCNK_GEMM_SMALLM_WK 1
-#endif
 #ifndef GCNK_WK_KBW   // 16-deep k blocks per wave (a slab is 8 waves of them)
 #define GCNK_WK_KBW 2
 #endif
@@ -729,7 +720,7 @@ extern "C" int gcnk_gemm_f32(int32_t transA, int32_t transB, int32_t M, int32_t 
   // small M, long K: the in-workgroup K split (gemm_smallm_wk_kernel), slabs of
   // 8 waves x 16 KBW k, summed by gemm_slab_reduce4_kernel
   const int64_t wk_S = ((int64_t)K + 8 * 16 * GCNK_WK_KBW - 1) / (8 * 16 * GCNK_WK_KBW);
-  if (GCNK_GEMM_SMALLM_WK && !ta && !tb && M <= 64 && K >= 512 && N % 4 == 0 && lda % 4 == 0 && aligned16(A) &&
+  if (!ta && !tb && M <= 64 && K >= 512 && N % 4 == 0 && lda % 4 == 0 && aligned16(A) &&
       split_k > 1 && wk_S <= split_k && wk_S <= 65535 &&
       (int64_t)M * lda * 4 < INT32_MAX && ((int64_t)K + 16) * ldb * 4 < INT32_MAX) {   // (its buffer offsets)
     const dim3 grid((unsigned)wk_S, (unsigned)((N + 16 * GCNK_WK_NTG - 1) / (16 * GCNK_WK_NTG)));

@@ -26,9 +26,9 @@
 //    of several leaves one partial per segment, and the last segment to
 //    finish (arrival counter in the plan) sums them in segment order and
 //    stores the row -- no fix-up launch.  With whole-wavefront groups (F >
-//    128) a wavefront takes two light rows at once (their items in one vector
-//    load, their gathers in one batch stream).  Every lane issues the U gathers of
-//    a batch before its first FMA (U independent 16-B loads in flight), and a
+//    128) a wavefront takes one light row (its items in one vector load).
+//    Every lane issues the U gathers of a batch before its first FMA (U
+//    independent 16-B loads in flight), and a
 //    unit's one store follows all of its loads, so no gather waits behind a
 //    store.  Heavy segments come first in the grid (the longest work is
 //    dispatched first); light rows follow in row order.  bias/ReLU/dropout
@@ -36,148 +36,42 @@
 //
 // Every sum has a fixed order (no float atomics): results are bitwise
 // reproducible run to run.
+//
+// This file: the kernels, their launches and the entry points that touch the
+// device.  The plan format and the row kernel's geometry are in spmm_plan.h,
+// the host planner in spmm_plan.cpp.
 #include "gcnk_common.h"
+#include "spmm_plan.h"
 
 #include <algorithm>
 #include <climits>
 #include <type_traits>
 #include <vector>
 
+// The schedule's overridable numbers (a `make variant` build may set them; the
+// choices that are settled are listed with their measurements in DESIGN.md,
+// "Settled schedule choices").
+#ifndef GCNK_TILE_MAXNT
+#define GCNK_TILE_MAXNT 4   // 16-column MFMA n-tiles per tile workgroup
+#endif
+#ifndef GCNK_TILE_PHASES
+#define GCNK_TILE_PHASES 2  // tile kernel: LDS writes / MFMA k-steps in this many phases (tile_body)
+#endif
+#ifndef GCNK_HEAVY_U
+#define GCNK_HEAVY_U 6      // gathers in flight per lane in a heavy segment (whole-wavefront groups)
+#endif
+#ifndef GCNK_ROW_U
+#define GCNK_ROW_U 8        // gathers in flight per lane for light rows
+#endif
+// (GCNK_STAMPS: the debug timeline, gcnk_common.h)
+
 namespace gcnk {
 namespace {
 
-constexpr int32_t kMagic = 0x474e4b35;  // "GNK5"
-constexpr int kRB = 64;                 // tile rows per dense block (4 waves x 16)
-constexpr int kKC = 64;                 // condensed columns per tile chunk (16 MFMA k-steps)
-#ifndef GCNK_TILE_MAXNT
-#define GCNK_TILE_MAXNT 4
-#endif
-// 16-column MFMA n-tiles per tile workgroup.  4 (R8 F = 200: 4 slices, 484
-// workgroups for X_hubs W1): tile 6.8 us against 7.3 with 8 and 7.5 with 1, the
-// forward 0.5-1 us shorter, factored or not (profiles/r03_tile_nt.log)
 constexpr int kMaxNT = GCNK_TILE_MAXNT;
-constexpr int kMaxColTiles = 64;        // row-kernel column tiles per launch (arrival counters per heavy row)
-constexpr int kMaxSeg = 64;             // slots per heavy entry (bounds a last arriver's combine)
-constexpr int kMaxSegRow = kMaxSeg * kMaxSeg;  // segments per heavy row (two combine levels)
-// Schedule knobs of the whole-wavefront (F > 128) row kernel, overridable at
-// compile time for experiments (scripts/variants.sh times prebuilt variants).
-// Measured on R8 A-hat F = 200 / 20ng-shaped (profiles/r01_variants.log):
-// 2 light rows per wavefront 10.6 / 18.2-19.0 us vs 1: 10.4 / 18.8 (the launch
-// then fits one residency round); 4 rows: 13.9 / 25.4; heavy U = 16: 11.5 (120
-// VGPRs, 4 waves/SIMD); 512-thread workgroups (8 waves per heavy segment): 10.7.
-// Write-through (sc1) output stores: the launch leaves no dirty output lines
-// in the XCD L2s for the kernel boundary to write back (R8 X W1: tile kernel
-// 13.2 -> 11.4 us in the forward, forward 36.4 -> 34.7 us).  2: nontemporal
-// stores instead (experiment).
-#ifndef GCNK_TILE_SC1
-#define GCNK_TILE_SC1 1
-#endif
-// Tile kernel: LDS writes / MFMA k-steps in this many phases (tile_body)
-#ifndef GCNK_TILE_PHASES
-#define GCNK_TILE_PHASES 2
-#endif
-// Nontemporal (streaming) output stores of the row kernel's finished rows: the
-// launch leaves no dirty output lines in the XCD L2s for the end-of-kernel
-// write-back.  R8 A-hat S1, F = 200, cold (HIP events per call,
-// profiles/r04_probe_nt.log): 9.46 -> 8.16 us, document rows alone 8.16 ->
-// 6.95, topic rows alone 9.05 -> 7.78 (a cold 12.4 MB copy: 4.35 -> 3.25 us,
-// scripts/micro/ns_micro.hip).  Write-through (sc1) stores measured 9.06 us
-// there (removed).
-#ifndef GCNK_ROW_NT
-#define GCNK_ROW_NT 1
-#endif
-// Light rows per wavefront (whole-wavefront groups).  Round 4, with the
-// nontemporal stores and the gather-wait fix, cold R8 A-hat F = 200
-// (profiles/r04_sweep2_*.log): one row per wavefront takes the document rows
-// alone from 6.95 to 5.27 us and the launch from 8.30 to 8.14 (the topic rows,
-// 7.76 alone, now bound it); two rows had measured even in round 1.
-#ifndef GCNK_LIGHT_RPW
-#define GCNK_LIGHT_RPW 1
-#endif
-// Gathers in flight per lane in a heavy segment.  With one light row per
-// wavefront the kernel holds 6 under its 64-VGPR cap (8 spills 16 B/lane, 12
-// spills 148): a 12-item segment is two batches of 6 instead of three of 4.
-// Cold R8 A-hat F = 200 (scripts/r04_step19.sh, four runs each, the last in
-// profiles/r04_sweep3_*.log): 8.10-8.15 -> 7.90-7.97 us; R8 F = 8
-// unchanged (5.47-5.50), the 20ng-shaped graph at F = 200 12.6 -> 12.8
-// (profiles/r04_hu_*.log).
-#ifndef GCNK_HEAVY_U
-#define GCNK_HEAVY_U 6
-#endif
-#ifndef GCNK_WAVE_BLOCK
-#define GCNK_WAVE_BLOCK 256
-#endif
-constexpr int kHeavyU = GCNK_HEAVY_U;        // gathers in flight per lane in a heavy segment
-#ifndef GCNK_ROW_U
-#define GCNK_ROW_U 8
-#endif
-constexpr int kRowU = GCNK_ROW_U;            // gathers in flight per lane for light rows
-#ifndef GCNK_NARROW_WG
-#define GCNK_NARROW_WG 1
-#endif
-// Lane groups of 8-32 lanes (256-thread workgroups): a heavy segment spans the
-// whole 4-wavefront workgroup (4x the nonzeros per segment, 4x fewer partials)
-// instead of one wavefront.  R8 A-hat at F = 64: 7.30 -> 6.69 us, F = 32 even.
-// Round 1-4 kept 1-4 lanes on one-wave workgroups (256-thread ones measured
-// 5.64 -> 6.14 us at F = 8); with round 5's padded heavy items the 256-thread
-// ones win from 2 lanes on (kNarrowMin below: F = 8 5.41 -> 4.73 us).
-constexpr bool kNarrowWG = GCNK_NARROW_WG != 0;
-// smallest group width (lanes) that takes 256-thread workgroups with
-// workgroup-wide heavy segments (experiment knob; narrower groups run one-wave
-// workgroups)
-#ifndef GCNK_NARROW_MIN_LPR
-#define GCNK_NARROW_MIN_LPR 2
-#endif
-constexpr int kNarrowMin = GCNK_NARROW_MIN_LPR;
-// Heavy segments of whole-wavefront plans keep a padded copy of their items
-// (segment u's at u * segp, col -1 past its end), so a heavy workgroup loads
-// its items at an address it knows from its index, in flight with its unit
-// word -- no unit -> items dependency before the gathers.
-#ifndef GCNK_HEAVY_DIRECT
-#define GCNK_HEAVY_DIRECT 1
-#endif
-constexpr int kWaveBlock = GCNK_WAVE_BLOCK;  // workgroup size for whole-wavefront groups
-constexpr int kLightRPW = GCNK_LIGHT_RPW;    // light rows per wavefront with whole-wavefront groups
-constexpr int kLightMax64 = 64 / kLightRPW;  // their nonzero limit (kLightRPW rows' items fill one 64-lane load)
+constexpr int kHeavyU = GCNK_HEAVY_U;
+constexpr int kRowU = GCNK_ROW_U;
 
-// ---------------------------------------------------------------------------
-// Plan layout (int32 words).  Header (16 words, see gcnk.h):
-//   0 magic  1 M  2 K  3 lane groups per wavefront (64 / LPR)  4 ipc (light-row limit)
-//   5 nunits  6 nhunits (heavy region, padded)  7 nheavy (rows of > 1 segment)
-//   8 ntile (chunks)  9 nred  10 nslabs  11 ntblk (tile blocks)  12 has_diag | segp << 1 | tops << 30  13 nnz
-//   14 nslots (partial slots)  15 nsingle (chunk items of single-chunk blocks, listed first)
-// Body: items int2[nnz] {col, value bits} in CSR order | units int4[nunits]
-//   {row (-1: empty), nz begin, nz end, heavy entry * 64 + slot or -1}: the
-//   heavy region first, then light rows, each laid out so that the units of
-//   workgroup b belong to XCD class b % 8 (below) | heavy int4[nheavy]
-//   {row, first partial slot, slots, -1 (a row of <= kMaxSeg segments), or for
-//   a row of more (bit 30 of header word 12 set): one entry per group of <=
-//   kMaxSeg segments with .w = the top entry's slot for the group's sum, and
-//   the top entry, .w = -2} | tile part (descriptors,
-//   condensed columns, A fragments, reduce rows int4[64 * nred] {row (-1:
-//   none), first slab, slabs, diagonal value bits}, row lists, extracted
-//   diagonal float[64 * ntblk] in block order) | (segp > 0) the heavy units'
-//   items, padded: int2[nhunits][segp], col -1 past a unit's end.
-struct Layout {
-  int64_t M, nnz, nunits, nhunits, nheavy, nslots, ntile, nred, ntblk, has_diag, segp, tops;
-  int64_t items, units, heavy, tdesc, tcols, tfrag, red, trows, dval, hitems, total;
-  __host__ __device__ explicit Layout(const int32_t* h) {
-    M = h[1]; nunits = h[5]; nhunits = h[6]; nheavy = h[7]; ntile = h[8]; nred = h[9]; ntblk = h[11];
-    has_diag = h[12] & 1; segp = ((uint32_t)h[12] >> 1) & ((1u << 29) - 1); tops = ((uint32_t)h[12] >> 30) & 1;
-    nnz = h[13]; nslots = h[14];
-    items = 16;
-    units = (items + 2 * nnz + 3) & ~3LL;
-    heavy = units + 4 * nunits;
-    tdesc = (heavy + 4 * nheavy + 3) & ~3LL;
-    tcols = tdesc + 4 * ntile;
-    tfrag = (tcols + (int64_t)kKC * ntile + 3) & ~3LL;
-    red = tfrag + (int64_t)kRB * kKC * ntile;
-    trows = red + 4 * nred * kRB;
-    dval = trows + (int64_t)kRB * ntblk;
-    hitems = (dval + (has_diag ? (int64_t)kRB * ntblk : 0) + 3) & ~3LL;
-    total = hitems + 2 * nhunits * segp;   // padded heavy items int2[nhunits][segp]
-  }
-};
 
 // Coherent (sc1) raw-buffer accesses from a wave-uniform base (see RowPlan).
 typedef float f32v4 __attribute__((ext_vector_type(4)));
@@ -600,34 +494,30 @@ __device__ __forceinline__ void finish_row(const typename Vec<VEC>::T& acc, int3
   using V = Vec<VEC>;
   using T = typename V::T;
   const T h = colok ? V::epi(epi, acc, bv, r, colv) : V::zero();
-#if GCNK_ROW_NT
+  // nontemporal: no dirty output lines left in the XCD L2s for the end-of-kernel write-back
   if (colok && store_main) store_nt(C + (int64_t)r * ldc + colv, h);
-#else
-  if (colok && store_main) V::store(C + (int64_t)r * ldc + colv, h);
-#endif
   proj.apply(pa, &h, r, lg);
 }
 
 // grid.x: [0, nhb) heavy blocks, one heavy segment per wavefront (per
 // workgroup for 64-lane groups); then light blocks, one light row per lane
 // group.  grid.y: column tiles of LPR*VEC.
-#ifndef GCNK_ROW_WPE
-#define GCNK_ROW_WPE 8
-#endif
 // Whole-wave groups at 8 waves per SIMD (<= 64 VGPRs, no spills there; the
 // narrower groups would spill): R8's 1832 workgroups then fit one residency
 // round (at 66 VGPRs, 7 per SIMD, 40 of them waited for a second round)
 template <int BLOCK, int LPR, int VEC, int U, int NP, bool O32>
-__global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(LPR == 64 && NP <= 8 ? GCNK_ROW_WPE : 1)))
+__global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(LPR == 64 && NP <= 8 ? 8 : 1)))
 spmm_row_kernel(RowPlan rp, int32_t nhb, const float* __restrict__ B, int64_t ldb, int32_t F,
                 float* __restrict__ C, int64_t ldc, Epi epi, float* __restrict__ part, int64_t part_ld,
                 ProjArgs pa) {
   resolve_rng(epi);
   using V = Vec<VEC>;
   using T = typename V::T;
-  constexpr int SG = BLOCK / LPR;  // lane groups per workgroup
+  constexpr RowGeom G = row_geom(LPR);
+  static_assert(G.block == BLOCK, "the plan is laid out for RowGeom's workgroups");
+  constexpr int SG = G.sg;         // lane groups per workgroup
   constexpr int SW = 64 / LPR;     // lane groups per wavefront
-  constexpr int WPB = BLOCK / 64;  // wavefronts per workgroup
+  constexpr int WPB = G.wpb;       // wavefronts per workgroup
   const int tid = threadIdx.x;
   const int lg = tid % LPR;
   const int64_t colv = (int64_t)blockIdx.y * (LPR * VEC) + (int64_t)lg * VEC;
@@ -647,13 +537,13 @@ spmm_row_kernel(RowPlan rp, int32_t nhb, const float* __restrict__ B, int64_t ld
 
   if ((int32_t)blockIdx.x >= nhb) {
     if constexpr (LPR == 64) {
-      // ---- light rows, whole-wavefront groups: kLightRPW units per wavefront,
-      //      their items in one vector load (row r's after rows < r's), their
-      //      gathers in one stream of U-wide batches (light rows are at most
-      //      kLightMax64 nonzeros each, so kLightRPW of them fill 64 lanes): the
-      //      light part of the grid is kLightRPW times fewer wavefronts and the
-      //      whole launch fits one residency round.
-      constexpr int R = kLightRPW;
+      // ---- light rows, whole-wavefront groups: one unit per wavefront, its
+      //      items (at most 64: the planner's light-row limit) in one vector load,
+      //      its gathers in U-wide batches.  Written as a loop nest over R rows
+      //      per wavefront with R = 1 (the planner and RowGeom::lpb assume one):
+      //      the same path written for one row compiles to other machine code,
+      //      so the nest stays until a kernel round re-times it.
+      constexpr int R = 1;
       const int32_t u0 = __builtin_amdgcn_readfirstlane(rp.nhunits + ((int32_t)blockIdx.x - nhb) * SG * R +
                                                         (tid / 64) * R);
       // (with a projection every wavefront reaches its barrier: past the end all
@@ -725,10 +615,11 @@ spmm_row_kernel(RowPlan rp, int32_t nhb, const float* __restrict__ B, int64_t ld
   // ---- heavy segment.  One unit per wavefront whose SW lane groups take nonzeros
   //      q, q + SW, ... (LPR < 64); with whole-wavefront groups (LPR == 64) one
   //      unit per workgroup, its WPB wavefronts interleaving the nonzeros and
-  //      meeting in LDS.  Either way GS = SW * (LPR == 64 ? WPB : 1) groups
-  //      share the segment and every sum has a fixed order.
-  constexpr bool WG = WPB > 1 && (LPR == 64 || (kNarrowWG && LPR >= kNarrowMin));
-  constexpr int GS = WG ? SW * WPB : SW;
+  //      meeting in LDS; so too for the narrower groups on 256-thread workgroups
+  //      (RowGeom::wg_heavy).  Either way GS groups share the segment and every
+  //      sum has a fixed order.
+  constexpr bool WG = G.wg_heavy;
+  constexpr int GS = G.gs;
   __shared__ T s_red[WG ? WPB : 1][64];
   __shared__ int32_t s_last;
   const int lane = tid & 63;
@@ -737,7 +628,7 @@ spmm_row_kernel(RowPlan rp, int32_t nhb, const float* __restrict__ B, int64_t ld
   const int32_t u = WG ? (int32_t)blockIdx.x : __builtin_amdgcn_readfirstlane((int32_t)blockIdx.x * WPB + w);
   if (u >= rp.nhunits) return;  // WG: uniform over the workgroup
   const int4 un = rp.units[u];
-  if (LPR == 64 && GCNK_HEAVY_DIRECT && rp.segp > 0) {
+  if (LPR == 64 && rp.segp > 0) {
     // the unit word and the padded items load together (a padding unit's items are all -1)
     gather_rows_wave_direct<VEC, kHeavyU, GS, O32>(rp.hitems + (int64_t)u * rp.segp, rp.segp, q, B, ldb, colv, colok,
                                                    acc);
@@ -1108,18 +999,12 @@ __device__ __forceinline__ void tile_body(int32_t bx, const int4* __restrict__ t
         v = make_float4(o[0], o[1], o[2], o[3]);
       }
     }
-#if GCNK_TILE_SC1 == 2   // (experiment: nontemporal stores)
-    store_nt(dst, v);
-#elif GCNK_TILE_SC1
-    {
+    {  // write-through (sc1): no dirty output lines left in the XCD L2s for the kernel boundary
       const float* base = uniform_ptr(single ? C : slabs);
       const int64_t off = dst - base;
       if (off >= 0 && off < ((int64_t)1 << 29)) store_coherent_v(base, off, v);
       else Vec<4>::store_aligned(dst, v);
     }
-#else
-    Vec<4>::store_aligned(dst, v);
-#endif
   }
   stamp(epi, 3);
 }
@@ -1217,26 +1102,6 @@ spmm_tile_reduce_kernel(const int4* __restrict__ red, int32_t F, const float* __
 // ---------------------------------------------------------------------------
 // Dispatch
 
-inline int next_pow2(int v) {
-  int p = 1;
-  while (p < v) p <<= 1;
-  return p;
-}
-
-// Lanes per group from F alone (a plan does not depend on pointer alignment,
-// which only picks VEC at launch): the smallest power of two covering the row
-// in VEC-wide vectors, at most 64 (a whole wavefront per row and column tile;
-// heavy segments then belong to a 4-wavefront workgroup).  Measured against
-// 16/32-lane groups in profiles/r01_sweep_rows*.log.
-inline int choose_lpr(int32_t F, int lanes_hint) {
-  if (lanes_hint > 0) return next_pow2(lanes_hint > 64 ? 64 : lanes_hint);
-  const int Wv = (F % 4 == 0) ? F / 4 : F;
-  return Wv <= 64 ? next_pow2(Wv < 1 ? 1 : Wv) : 64;
-}
-
-// Narrow groups use one-wave workgroups so a light launch still spans the chip.
-inline int choose_block(int lpr) { return lpr == 64 ? kWaveBlock : lpr >= kNarrowMin ? 256 : 64; }
-
 struct RowLaunch {
   RowPlan rp;
   int32_t K;  // rows of B (bounds the 32-bit gather offsets)
@@ -1252,14 +1117,12 @@ struct RowLaunch {
   hipStream_t s;
 };
 
-template <int BLOCK, int LPR, int VEC, int U, int NP>
+template <int LPR, int VEC, int U, int NP>
 int launch_rows(const RowLaunch& a) {
-  constexpr int SG = BLOCK / LPR, WPB = BLOCK / 64;
-  constexpr int LPB = LPR == 64 ? SG * kLightRPW : SG;  // light units per workgroup
-  // heavy segments: one per workgroup for whole-wavefront groups, else one per wavefront
-  const int64_t nhb = (LPR == 64 || (kNarrowWG && LPR >= kNarrowMin && WPB > 1)) ? (int64_t)a.rp.nhunits
-                                                            : ((int64_t)a.rp.nhunits + WPB - 1) / WPB;
-  const int64_t nlb = ((int64_t)a.rp.nunits - a.rp.nhunits + LPB - 1) / LPB;
+  constexpr RowGeom G = row_geom(LPR);
+  constexpr int BLOCK = G.block;
+  const int64_t nhb = ((int64_t)a.rp.nhunits + G.hpb - 1) / G.hpb;                 // heavy workgroups
+  const int64_t nlb = ((int64_t)a.rp.nunits - a.rp.nhunits + G.lpb - 1) / G.lpb;  // light workgroups
   if (nhb + nlb == 0) return GCNK_OK;
   if (nhb + nlb > (int64_t)INT32_MAX) {
     set_error("gcnk_spmm_csr_f32: %lld workgroups exceed the grid", (long long)(nhb + nlb));
@@ -1277,19 +1140,14 @@ int launch_rows(const RowLaunch& a) {
     e.mask = e.mask ? e.mask + c0 : nullptr;
     e.offset += (uint64_t)c0;  // hash index shifts with the column
     // 32-bit gather offsets when every byte the launch reads lies within 4 GB of its B base
-#ifndef GCNK_ROW_O32
-#define GCNK_ROW_O32 1
-#endif
-    const bool o32 = GCNK_ROW_O32 && (int64_t)a.K * a.ldb * 4 + (int64_t)Fw * 4 < ((int64_t)1 << 32);
+    const bool o32 = (int64_t)a.K * a.ldb * 4 + (int64_t)Fw * 4 < ((int64_t)1 << 32);
     const dim3 grid((unsigned)(nhb + nlb), (unsigned)((Fw + tileF - 1) / tileF));
-    if (o32)
-      hipLaunchKernelGGL((spmm_row_kernel<BLOCK, LPR, VEC, U, NP, true>), grid, dim3(BLOCK), 0, a.s, a.rp, (int32_t)nhb,
-                         a.B + c0, a.ldb, Fw, a.C ? a.C + c0 : nullptr, a.ldc, e, a.part ? a.part + c0 : nullptr,
-                         a.part_ld, a.pa);
-    else
-      hipLaunchKernelGGL((spmm_row_kernel<BLOCK, LPR, VEC, U, NP, false>), grid, dim3(BLOCK), 0, a.s, a.rp,
-                         (int32_t)nhb, a.B + c0, a.ldb, Fw, a.C ? a.C + c0 : nullptr, a.ldc, e,
-                         a.part ? a.part + c0 : nullptr, a.part_ld, a.pa);
+    auto launch = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, grid, dim3(BLOCK), 0, a.s, a.rp, (int32_t)nhb, a.B + c0, a.ldb, Fw,
+                         a.C ? a.C + c0 : nullptr, a.ldc, e, a.part ? a.part + c0 : nullptr, a.part_ld, a.pa);
+    };
+    if (o32) launch(spmm_row_kernel<BLOCK, LPR, VEC, U, NP, true>);
+    else launch(spmm_row_kernel<BLOCK, LPR, VEC, U, NP, false>);
     const int rc = launch_check("spmm_row_kernel");
     if (rc) return rc;
   }
@@ -1299,13 +1157,13 @@ int launch_rows(const RowLaunch& a) {
 template <int VEC>
 int dispatch_rows(int lpr, const RowLaunch& a) {
   switch (lpr) {
-    case 1: return launch_rows<kNarrowMin <= 1 ? 256 : 64, 1, VEC, kRowU, 0>(a);
-    case 2: return launch_rows<kNarrowMin <= 2 ? 256 : 64, 2, VEC, kRowU, 0>(a);
-    case 4: return launch_rows<kNarrowMin <= 4 ? 256 : 64, 4, VEC, kRowU, 0>(a);
-    case 8: return launch_rows<256, 8, VEC, kRowU, 0>(a);
-    case 16: return launch_rows<256, 16, VEC, kRowU, 0>(a);
-    case 32: return launch_rows<256, 32, VEC, kRowU, 0>(a);
-    case 64: return launch_rows<kWaveBlock, 64, VEC, kRowU, 0>(a);
+    case 1: return launch_rows<1, VEC, kRowU, 0>(a);
+    case 2: return launch_rows<2, VEC, kRowU, 0>(a);
+    case 4: return launch_rows<4, VEC, kRowU, 0>(a);
+    case 8: return launch_rows<8, VEC, kRowU, 0>(a);
+    case 16: return launch_rows<16, VEC, kRowU, 0>(a);
+    case 32: return launch_rows<32, VEC, kRowU, 0>(a);
+    case 64: return launch_rows<64, VEC, kRowU, 0>(a);
   }
   set_error("gcnk_spmm_csr_f32: unsupported lanes per group %d", lpr);
   return GCNK_EUNSUP;
@@ -1315,9 +1173,9 @@ int dispatch_rows(int lpr, const RowLaunch& a) {
 template <int NP>
 int dispatch_rows_proj(int lpr, const RowLaunch& a) {
   switch (lpr) {
-    case 16: return launch_rows<256, 16, 4, 8, NP>(a);
-    case 32: return launch_rows<256, 32, 4, 8, NP>(a);
-    case 64: return launch_rows<kWaveBlock, 64, 4, 8, NP>(a);
+    case 16: return launch_rows<16, 4, 8, NP>(a);
+    case 32: return launch_rows<32, 4, 8, NP>(a);
+    case 64: return launch_rows<64, 4, 8, NP>(a);
   }
   set_error("gcnk_spmm_proj_f32: no fused-projection kernel for %d lanes per group", lpr);
   return GCNK_EUNSUP;
@@ -1380,420 +1238,6 @@ inline int launch_tile(bool v4, int nt_need, unsigned nitems, const TileArgs& t,
   return v4 ? launch_tile_v<true>(nt_need, nitems, t, s) : launch_tile_v<false>(nt_need, nitems, t, s);
 }
 
-// ---------------------------------------------------------------------------
-// Host side of the plan.
-struct HostPlan {
-  int32_t hdr[16];
-  std::vector<int32_t> units, heavy;  // row-kernel units (int4 each), heavy rows (int4 each)
-  std::vector<int32_t> tdesc, tcols, red, trows;
-  std::vector<float> tfrag, dval;  // dval: extracted diagonal of tile rows in block order (64 per block, or empty)
-};
-
-// rowptr / colind validity (host arrays): monotone row pointers, in-range columns.
-int check_csr(const int32_t* rp, const int32_t* ci, int32_t M, int32_t K, int64_t nnz) {
-  if ((int64_t)rp[M] != nnz || rp[0] != 0) {
-    set_error("gcnk_spmm_plan: rowptr[0]=%d rowptr[M]=%d inconsistent with nnz=%lld", rp[0], rp[M], (long long)nnz);
-    return GCNK_EARG;
-  }
-  for (int32_t r = 0; r < M; ++r)
-    if (rp[r + 1] < rp[r]) {
-      set_error("gcnk_spmm_plan: rowptr decreases at row %d", r);
-      return GCNK_EARG;
-    }
-  for (int64_t k = 0; k < nnz; ++k)
-    if (ci[k] < 0 || ci[k] >= K) {
-      set_error("gcnk_spmm_plan: column index %d out of range [0, %d) at nonzero %lld", ci[k], K, (long long)k);
-      return GCNK_EARG;
-    }
-  return GCNK_OK;
-}
-
-// Row-unit + dense-tile plan from host CSR arrays (vv null: layout only).
-// (light_sort false: the layout and counts only -- enough for the plan's size)
-int host_plan(const int32_t* rp, const int32_t* ci, const float* vv, int32_t M, int32_t K, int64_t nnz, int32_t ipc,
-              int32_t groups, float dense_threshold, HostPlan& hp, bool light_sort = true) {
-  const bool want_values = vv != nullptr;
-  // ---- dense blocks (tile path).  Rows are grouped by degree class (factor-8
-  //      buckets of the off-diagonal degree), in row order within a class, 64 per
-  //      block, so rows of one shape share blocks (R8: document rows vs topic rows).
-  //      A block goes to the MFMA tile path when its nonzeros fill at least
-  //      dense_threshold of its condensed column set and each condensed column is
-  //      used at least twice on average; its rows' diagonal entries (r < K) are
-  //      taken out of the column set and added in the epilogue (dval[r] * B[r,:]).
-  std::vector<char> tile_row((size_t)M, 0);
-  int32_t ntile = 0, nred = 0, nslabs = 0, ntblk = 0, nsingle = 0;
-  bool any_diag = false;
-  hp.dval.clear();
-  // the diagonal is kept aside for square operands (A-hat's self loops); a
-  // rectangular operand (X) has no diagonal to speak of
-  auto is_diag = [&](int32_t r, int64_t k) { return M == K && ci[(size_t)k] == r; };
-  if (dense_threshold <= 1.0f && M > 0) {
-    std::vector<std::vector<int32_t>> cls(33);
-    for (int32_t r = 0; r < M; ++r) {
-      int64_t deg = 0;
-      for (int64_t k = rp[r]; k < rp[r + 1]; ++k) deg += !is_diag(r, k);
-      int bw = 0;
-      while (bw < 63 && (deg >> bw) != 0) ++bw;
-      cls[(size_t)(bw / 3)].push_back(r);
-    }
-    std::vector<int32_t> cmap((size_t)K, -1);
-    std::vector<int32_t> seen((size_t)K, -1);  // block stamp per column: distinct count without a sort
-    int32_t stampv = 0;
-    std::vector<int32_t> cols;
-    std::vector<float> dv((size_t)M, 0.f);
-    for (const std::vector<int32_t>& rows : cls) {
-      for (size_t i0 = 0; i0 < rows.size(); i0 += kRB, ++stampv) {
-        const size_t i1 = std::min(rows.size(), i0 + kRB);
-        int64_t bnnz = 0, ncols = 0;
-        for (size_t i = i0; i < i1; ++i) {
-          const int32_t r = rows[i];
-          for (int64_t k = rp[r]; k < rp[r + 1]; ++k)
-            if (!is_diag(r, k)) {
-              int32_t& sv = seen[(size_t)ci[(size_t)k]];
-              ncols += sv != stampv;
-              sv = stampv;
-              ++bnnz;
-            }
-        }
-        if (bnnz == 0) continue;
-        const int64_t nrows = (int64_t)(i1 - i0);
-        // the density test needs only the counts; the sorted column set is built
-        // for the blocks that pass it (a sparse operand -- 1M/20M -- has none)
-        if ((double)bnnz < (double)dense_threshold * (double)nrows * (double)ncols || bnnz < 2 * ncols) continue;
-        cols.clear();
-        for (size_t i = i0; i < i1; ++i) {
-          const int32_t r = rows[i];
-          for (int64_t k = rp[r]; k < rp[r + 1]; ++k)
-            if (!is_diag(r, k)) cols.push_back(ci[(size_t)k]);
-        }
-        std::sort(cols.begin(), cols.end());
-        cols.erase(std::unique(cols.begin(), cols.end()), cols.end());
-        const int32_t nch = (int32_t)((ncols + kKC - 1) / kKC);
-        const int32_t first_slab = nch > 1 ? nslabs : -1;
-        const int32_t blk = ntblk++;
-        for (int64_t c = 0; c < ncols; ++c) cmap[(size_t)cols[(size_t)c]] = (int32_t)c;
-        const size_t base_item = (size_t)ntile;
-        for (int32_t ch = 0; ch < nch; ++ch) {
-          // a chunk whose condensed columns are one contiguous run (R8's X: the
-          // 50 topic columns; 64-column pieces of the dense topic rows) is
-          // described by its first column and length (y bits 8.., w), so the
-          // kernel stages its B rows without waiting for the column list
-          const int64_t c0 = (int64_t)ch * kKC;
-          const int32_t kc = (int32_t)std::min<int64_t>(kKC, ncols - c0);
-          bool contig = true;
-          for (int32_t k = 1; k < kc && contig; ++k) contig = cols[(size_t)(c0 + k)] == cols[(size_t)c0] + k;
-          // y: rows | contiguous run << 8 | condensed width << 16 (the kernel's k-steps)
-          hp.tdesc.insert(hp.tdesc.end(), {blk, (int32_t)nrows | (contig ? kc << 8 : 0) | kc << 16,
-                                           nch > 1 ? first_slab + ch : -1, contig ? cols[(size_t)c0] : 0});
-          for (int k = 0; k < kKC; ++k) {
-            const int64_t cc = (int64_t)ch * kKC + k;
-            hp.tcols.push_back(cc < ncols ? cols[(size_t)cc] : -1);
-          }
-        }
-        for (int64_t rl = 0; rl < kRB; ++rl) hp.trows.push_back(rl < nrows ? rows[i0 + (size_t)rl] : -1);
-        hp.tfrag.resize(hp.tfrag.size() + (size_t)nch * kRB * kKC, 0.f);
-        for (size_t i = i0; i < i1; ++i) {
-          const int32_t r = rows[i];
-          const int32_t rl = (int32_t)(i - i0), t = rl / 16, lr = rl % 16;
-          tile_row[(size_t)r] = 1;
-          for (int64_t k = rp[r]; k < rp[r + 1]; ++k) {
-            if (is_diag(r, k)) {
-              any_diag = true;
-              if (want_values) dv[(size_t)r] += vv[(size_t)k];
-              continue;
-            }
-            if (!want_values) continue;
-            const int32_t cc = cmap[(size_t)ci[(size_t)k]];
-            const int32_t ch = cc / kKC, kk = cc % kKC;
-            const int32_t st = kk / 4, kq = kk % 4;
-            const int32_t ln = kq * 16 + lr;
-            hp.tfrag[(((base_item + ch) * 4 + t) * 64 + ln) * 16 + st] += vv[(size_t)k];
-          }
-        }
-        for (int64_t c = 0; c < ncols; ++c) cmap[(size_t)cols[(size_t)c]] = -1;
-        if (nch > 1) {  // one reduce entry per row: the reduce kernel needs no other plan read
-          for (int64_t rl = 0; rl < kRB; ++rl) {
-            const int32_t r = rl < nrows ? rows[i0 + (size_t)rl] : -1;
-            hp.red.insert(hp.red.end(), {r, first_slab, nch, r >= 0 ? __builtin_bit_cast(int32_t, dv[(size_t)r]) : 0});
-          }
-          ++nred;
-          nslabs += nch;
-        }
-        ntile += nch;
-      }
-    }
-    // chunk items of single-chunk blocks first, then the multi-chunk ones (which
-    // also need the reduce launch): the two runs can be launched separately
-    // (gcnk_spmm_csr_f32_part), e.g. on two streams
-    {
-      std::vector<int32_t> order;
-      for (int32_t i = 0; i < ntile; ++i)
-        if (hp.tdesc[(size_t)i * 4 + 2] < 0) order.push_back(i);
-      nsingle = (int32_t)order.size();
-      for (int32_t i = 0; i < ntile; ++i)
-        if (hp.tdesc[(size_t)i * 4 + 2] >= 0) order.push_back(i);
-      std::vector<int32_t> td((size_t)ntile * 4), tc((size_t)ntile * kKC);
-      std::vector<float> tf((size_t)ntile * kRB * kKC);
-      for (int32_t j = 0; j < ntile; ++j) {
-        const size_t i = (size_t)order[(size_t)j];
-        std::copy(hp.tdesc.begin() + i * 4, hp.tdesc.begin() + i * 4 + 4, td.begin() + (size_t)j * 4);
-        std::copy(hp.tcols.begin() + i * kKC, hp.tcols.begin() + (i + 1) * kKC, tc.begin() + (size_t)j * kKC);
-        if (!hp.tfrag.empty())
-          std::copy(hp.tfrag.begin() + i * kRB * kKC, hp.tfrag.begin() + (i + 1) * kRB * kKC,
-                    tf.begin() + (size_t)j * kRB * kKC);
-      }
-      hp.tdesc.swap(td);
-      hp.tcols.swap(tc);
-      if (!hp.tfrag.empty()) hp.tfrag.swap(tf);
-    }
-    if (any_diag) {  // block order, so kernels index it by (block, row in block) without the row list
-      hp.dval.assign((size_t)ntblk * kRB, 0.f);
-      for (size_t i = 0; i < hp.trows.size(); ++i)
-        if (hp.trows[i] >= 0) hp.dval[i] = dv[(size_t)hp.trows[i]];
-    }
-  }
-
-  // ---- row units over the other rows.  Launch geometry from `groups` = 64 / LPR.
-  if (groups < 1 || groups > 64 || (groups & (groups - 1))) {
-    set_error("gcnk_spmm_plan: groups %d is not a power of two in [1, 64]", groups);
-    return GCNK_EARG;
-  }
-  const int lpr = 64 / groups;
-  const int block = choose_block(lpr), wpb = block / 64, sg = block / lpr;
-  const bool wg_heavy = lpr == 64 || (kNarrowWG && lpr >= kNarrowMin && wpb > 1);  // a heavy segment spans the workgroup
-  const int hpb = wg_heavy ? 1 : wpb;                            // heavy units per workgroup
-  const int64_t seg = (int64_t)ipc * (lpr == 64 ? wpb : groups * (wg_heavy ? wpb : 1));  // nonzeros per segment
-  // light-row limit: 2 * ipc for whole-wavefront groups (two light rows share a
-  // wavefront, at most kLightMax64 nonzeros each; a heavy row is walked by a
-  // 4-wavefront workgroup), ipc otherwise
-  const int64_t light_max = lpr == 64 ? std::min<int64_t>(2 * (int64_t)ipc, kLightMax64) : ipc;
-  const int lpb = lpr == 64 ? sg * kLightRPW : sg;  // light units per workgroup
-  // XCD classes.  Workgroups b and b + 8 land on one XCD (round-robin dispatch;
-  // speed only, never correctness), so every unit of workgroup b is given
-  // class b % 8: a light row by its row index, a heavy segment by the column
-  // range it gathers (heavy rows are first cut where their sorted column
-  // indices cross a class boundary).  Each XCD's L2 then serves 1/8 of B
-  // instead of every XCD fetching the rows its segments happen to need
-  // (R8 Â: the topic rows gather all document rows).
-  constexpr int NX = 8;
-  auto cls = [](int64_t i, int64_t n) { return n > 0 ? (int)(i * NX / n) : 0; };
-  std::vector<std::vector<int32_t>> hq(NX), lq(NX);  // int4 units per class
-  int32_t nheavy = 0;
-  int64_t nslots = 0;
-  bool any_top = false;
-  hp.units.clear();
-  hp.heavy.clear();
-  std::vector<int64_t> rb, rcl;  // runs of one column class: start, class
-  int64_t rr_class = 0;
-  for (int32_t r = 0; r < M; ++r) {
-    if (tile_row[(size_t)r]) continue;
-    const int64_t b = rp[r], e = rp[r + 1], deg = e - b;
-    if (deg <= light_max) {
-      lq[(size_t)cls(r, M)].insert(lq[(size_t)cls(r, M)].end(), {r, (int32_t)b, (int32_t)e, -1});
-      continue;
-    }
-    rb.clear();
-    rcl.clear();
-    // cut at column-class boundaries only when the runs average half a segment or
-    // more (a 20-nonzero row must not become 8 tiny segments)
-    if (deg * 2 >= seg * NX)
-      for (int64_t k = b; k < e; ++k) {
-        const int c = cls(ci[(size_t)k], K);
-        if (rcl.empty() || rcl.back() != c) { rb.push_back(k); rcl.push_back(c); }
-      }
-    if (rb.empty() || (int64_t)rb.size() > NX) {  // short row, or columns not sorted: one run,
-      rb.assign(1, b);                              // classes dealt round-robin (balance)
-      rcl.assign(1, (int64_t)(rr_class++ % NX));
-    }
-    rb.push_back(e);
-    const int64_t nruns = (int64_t)rcl.size();
-    // segments of `seg` nonzeros (longer only past kMaxSegRow of them, ~200k
-    // nonzeros at R8's widths): a row of more than kMaxSeg segments gets two
-    // combine levels instead of longer segments, so a power-law hub is walked
-    // by many short segments, not by 64 long ones
-    int64_t sr = seg, nseg = 0;
-    for (;;) {
-      nseg = 0;
-      for (int64_t i = 0; i < nruns; ++i) nseg += (rb[(size_t)i + 1] - rb[(size_t)i] + sr - 1) / sr;
-      if (nseg <= kMaxSegRow) break;
-      sr *= 2;
-    }
-    if (nseg == 1) {
-      hq[(size_t)rcl[0]].insert(hq[(size_t)rcl[0]].end(), {r, (int32_t)b, (int32_t)e, -1});
-      continue;
-    }
-    // heavy entries: one (nseg <= kMaxSeg), or a top entry over ng groups of
-    // consecutive segments (group g: segments [g nseg / ng, (g + 1) nseg / ng))
-    const int64_t ng = nseg <= kMaxSeg ? 1 : (nseg + kMaxSeg - 1) / kMaxSeg;
-    int64_t top_slot = -1;
-    if (ng > 1) {
-      ++nheavy;
-      hp.heavy.insert(hp.heavy.end(), {r, (int32_t)nslots, (int32_t)ng, -2});
-      top_slot = nslots;
-      nslots += ng;
-      any_top = true;
-    }
-    std::vector<int32_t> seg_w((size_t)nseg);
-    for (int64_t g = 0; g < ng; ++g) {
-      const int64_t s0 = g * nseg / ng, s1 = (g + 1) * nseg / ng;
-      const int32_t hid = nheavy++;
-      hp.heavy.insert(hp.heavy.end(), {r, (int32_t)nslots, (int32_t)(s1 - s0), ng > 1 ? (int32_t)(top_slot + g) : -1});
-      for (int64_t sgi = s0; sgi < s1; ++sgi) seg_w[(size_t)sgi] = (int32_t)((int64_t)hid * 64 + (sgi - s0));
-      nslots += s1 - s0;
-    }
-    int64_t sgi = 0;
-    for (int64_t i = 0; i < nruns; ++i) {
-      const int64_t pb = rb[(size_t)i], len = rb[(size_t)i + 1] - pb, np = (len + sr - 1) / sr;
-      std::vector<int32_t>& q = hq[(size_t)rcl[(size_t)i]];
-      for (int64_t s = 0; s < np; ++s, ++sgi)
-        q.insert(q.end(), {r, (int32_t)(pb + len * s / np), (int32_t)(pb + len * (s + 1) / np), seg_w[(size_t)sgi]});
-    }
-  }
-  // lay out rounds of NX workgroups, workgroup 8k + c taking `per` units of class c
-  // (empty units pad short classes)
-  auto layout = [&](std::vector<std::vector<int32_t>>& qs, int per) {
-    size_t rounds = 0;
-    for (const auto& q : qs) rounds = std::max(rounds, (q.size() / 4 + per - 1) / per);
-    for (size_t k = 0; k < rounds; ++k)
-      for (int c = 0; c < NX; ++c)
-        for (int j = 0; j < per; ++j) {
-          const size_t i = (k * per + j) * 4;
-          if (i < qs[(size_t)c].size())
-            hp.units.insert(hp.units.end(), qs[(size_t)c].begin() + i, qs[(size_t)c].begin() + i + 4);
-          else
-            hp.units.insert(hp.units.end(), {-1, 0, 0, -1});
-        }
-  };
-#ifndef GCNK_LIGHT_SORT
-#define GCNK_LIGHT_SORT 1
-#endif
-  // light rows of a class ordered by their off-diagonal column lists, so the
-  // rows one workgroup (one CU's L1) gathers for share their B rows (R8: the
-  // document rows of one topic set); each row still writes its own C row
-  // (ordered by a key of the first two off-diagonal columns, the full lists only
-  // on equal keys, then by position: the order of a stable sort by the lists;
-  // 1M/20M: 0.49 -> 0.05 s per build)
-  if (GCNK_LIGHT_SORT && light_sort)
-    for (std::vector<int32_t>& q : lq) {
-      const size_t n = q.size() / 4;
-      std::vector<size_t> ord(n);
-      for (size_t i = 0; i < n; ++i) ord[i] = i;
-      std::vector<uint64_t> key(n);
-      for (size_t i = 0; i < n; ++i) {
-        const int32_t r = q[4 * i];
-        uint64_t c[2] = {0, 0};  // column + 1, 0 past the list's end (a prefix sorts first)
-        int got = 0;
-        for (int32_t k = q[4 * i + 1]; k < q[4 * i + 2] && got < 2; ++k)
-          if (ci[(size_t)k] != r) c[got++] = (uint64_t)ci[(size_t)k] + 1;
-        key[i] = c[0] << 32 | c[1];
-      }
-      auto less_list = [&](size_t x, size_t y) {
-        const int32_t rx = q[4 * x], ry = q[4 * y];
-        int32_t kx = q[4 * x + 1], ky = q[4 * y + 1];
-        const int32_t ex = q[4 * x + 2], ey = q[4 * y + 2];
-        for (;;) {
-          while (kx < ex && ci[(size_t)kx] == rx) ++kx;
-          while (ky < ey && ci[(size_t)ky] == ry) ++ky;
-          if (kx >= ex || ky >= ey) return kx >= ex && ky < ey;
-          if (ci[(size_t)kx] != ci[(size_t)ky]) return ci[(size_t)kx] < ci[(size_t)ky];
-          ++kx;
-          ++ky;
-        }
-      };
-      std::sort(ord.begin(), ord.end(), [&](size_t x, size_t y) {
-        if (key[x] != key[y]) return key[x] < key[y];
-        if (less_list(x, y)) return true;
-        if (less_list(y, x)) return false;
-        return x < y;
-      });
-      std::vector<int32_t> sorted(q.size());
-      for (size_t i = 0; i < n; ++i) std::copy(q.begin() + 4 * ord[i], q.begin() + 4 * ord[i] + 4, sorted.begin() + 4 * i);
-      q.swap(sorted);
-    }
-  layout(hq, hpb);
-  const int64_t nh = (int64_t)hp.units.size() / 4;
-  // padded item copies of the heavy units (whole-wavefront groups): stride = the
-  // longest unit, rounded up to 4 items
-  int64_t segp = 0;
-  if (GCNK_HEAVY_DIRECT && lpr == 64)
-    for (int64_t u = 0; u < nh; ++u)
-      if (hp.units[(size_t)(4 * u)] >= 0)
-        segp = std::max<int64_t>(segp, (int64_t)hp.units[(size_t)(4 * u + 2)] - hp.units[(size_t)(4 * u + 1)]);
-  segp = (segp + 3) & ~3LL;
-  if (segp >= (1 << 28) || 2 * nh * segp >= (int64_t)INT32_MAX) segp = 0;   // (never for real plans: keep the old path)
-  layout(lq, lpb);
-  const int64_t nunits = (int64_t)hp.units.size() / 4;
-  if (nunits >= (int64_t)INT32_MAX || nslots >= (int64_t)INT32_MAX || nheavy >= (1 << 25)) {
-    set_error("gcnk_spmm_plan: %lld row units / %lld partial slots exceed the plan's int32 fields",
-              (long long)nunits, (long long)nslots);
-    return GCNK_EUNSUP;
-  }
-  const int32_t h[16] = {kMagic, M,     K,      groups, ipc,  (int32_t)nunits, (int32_t)nh, nheavy,
-                         ntile,  nred, nslabs, ntblk,  (any_diag ? 1 : 0) | (int32_t)(segp << 1) | (any_top ? 1 << 30 : 0), (int32_t)nnz,
-                         (int32_t)nslots, nsingle};
-  std::copy(h, h + 16, hp.hdr);
-  return GCNK_OK;
-}
-
-// Full classic plan image (header, packed items, units, heavy rows, tile part).
-void classic_image(const HostPlan& hp, const int32_t* ci, const float* vv, int64_t nnz, std::vector<int32_t>& img) {
-  const Layout L(hp.hdr);
-  img.assign((size_t)L.total, 0);
-  std::copy(hp.hdr, hp.hdr + 16, img.begin());
-  for (int64_t k = 0; k < nnz; ++k) {
-    img[(size_t)(L.items + 2 * k)] = ci[k];
-    img[(size_t)(L.items + 2 * k + 1)] = vv ? __builtin_bit_cast(int32_t, vv[k]) : 0;
-  }
-  auto put = [&](int64_t off, const int32_t* p, size_t n) { std::copy(p, p + n, img.begin() + off); };
-  auto putf = [&](int64_t off, const std::vector<float>& v) {
-    for (size_t i = 0; i < v.size(); ++i) img[(size_t)off + i] = __builtin_bit_cast(int32_t, v[i]);
-  };
-  put(L.units, hp.units.data(), hp.units.size());
-  put(L.heavy, hp.heavy.data(), hp.heavy.size());
-  put(L.tdesc, hp.tdesc.data(), hp.tdesc.size());
-  put(L.tcols, hp.tcols.data(), hp.tcols.size());
-  putf(L.tfrag, hp.tfrag);
-  put(L.red, hp.red.data(), hp.red.size());
-  put(L.trows, hp.trows.data(), hp.trows.size());
-  putf(L.dval, hp.dval);
-  for (int64_t u = 0; u < L.nhunits && L.segp > 0; ++u) {
-    const int32_t r = hp.units[(size_t)(4 * u)], b = hp.units[(size_t)(4 * u + 1)], e = hp.units[(size_t)(4 * u + 2)];
-    for (int64_t i = 0; i < L.segp; ++i) {
-      const size_t o = (size_t)(L.hitems + 2 * (u * L.segp + i));
-      const bool in = r >= 0 && b + i < e;
-      img[o] = in ? ci[b + i] : -1;
-      img[o + 1] = in && vv ? __builtin_bit_cast(int32_t, vv[b + i]) : 0;
-    }
-  }
-}
-
-// The row-unit + tile plan image for host CSR arrays.
-int build_image(const int32_t* rp, const int32_t* ci, const float* vv, int32_t M, int32_t K, int64_t nnz, int32_t ipc,
-                int32_t groups, float dense_threshold, std::vector<int32_t>& img) {
-  int rc = check_csr(rp, ci, M, K, nnz);
-  if (rc) return rc;
-  HostPlan hp;
-  if ((rc = host_plan(rp, ci, vv, M, K, nnz, ipc, groups, std::fabs(dense_threshold), hp))) return rc;
-  classic_image(hp, ci, vv, nnz, img);
-  return GCNK_OK;
-}
-
-// Bytes of the plan build_image would make, without making it: the size
-// follows from its header (no light-row sort, no image).
-int64_t plan_size(const int32_t* rp, const int32_t* ci, int32_t M, int32_t K, int64_t nnz, int32_t ipc, int32_t groups,
-                  float dense_threshold) {
-  int rc = check_csr(rp, ci, M, K, nnz);
-  if (rc) return rc;
-  HostPlan hp;
-  if ((rc = host_plan(rp, ci, nullptr, M, K, nnz, ipc, groups, std::fabs(dense_threshold), hp, false))) return rc;
-  return Layout(hp.hdr).total * 4;
-}
-
-bool plan_args_ok(const int32_t* rowptr, const int32_t* colind, int32_t M, int32_t K, int64_t nnz, int32_t ipc,
-                  int32_t groups) {
-  return rowptr && M >= 0 && K >= 0 && nnz >= 0 && nnz < INT32_MAX && ipc > 0 && groups > 0 && (nnz == 0 || colind);
-}
-
 // Device CSR -> host arrays (one-time setup: synchronises `s`).
 int fetch_csr(const int32_t* rowptr, const int32_t* colind, const float* val, int32_t M, int64_t nnz, hipStream_t s,
               std::vector<int32_t>& rp, std::vector<int32_t>& ci, std::vector<float>& vv) {
@@ -1830,61 +1274,6 @@ extern "C" int gcnk_debug_set_stamps(void* buf) {
 }
 #endif
 unsigned long long* gcnk::debug_stamps() { return g_stamps; }
-
-
-// Lane groups per wavefront (64 / LPR): identifies the launch geometry a plan
-// is laid out for (heavy segments are shared by these groups, or by the 4
-// wavefronts of a workgroup when a group is a whole wavefront).
-extern "C" int32_t gcnk_spmm_groups(int32_t F, int32_t lanes_hint) { return 64 / choose_lpr(F, lanes_hint); }
-
-extern "C" int32_t gcnk_spmm_default_ipc(int32_t M, int64_t nnz, int32_t F, int32_t lanes_hint) {
-  (void)M;
-  // each lane group's share of a heavy segment (the light-row limit is 2 * ipc
-  // at 64 lanes, ipc below).  Narrow groups: 8 (one U = 8 gather batch; R8
-  // F = 8 ipc 8 5.1 us, 16 5.7).  Whole-wavefront groups: heavy segments of
-  // 4 * ipc nonzeros over a 4-wavefront workgroup, sized with the operand so
-  // the heavy segments stay a few per CU: ipc ~ nnz / 5760 in [12, 32], a
-  // multiple of 4.  Sweeps after the 16-B partial accesses
-  // (profiles/r01_variants.log): R8 (69k nnz) ipc 12 8.67 us, 16 8.95, 20 9.24,
-  // 24 9.72; 20ng-shaped (175k) 12 17.9, 16 17.0, 20 16.4, 24 16.2, 32 16.4;
-  // 1M/20M F = 256: 16 and 32 both 3.37 ms.
-  // 2-lane groups with workgroup-wide heavy segments (LPR >= kNarrowMin): 16
-  // (round 5, after the padded heavy items: R8 F = 8 4.73 us vs 5.41 with
-  // one-wave workgroups at ipc 8, profiles/r05_hub_probe_nw2.log).
-  const int lpr = choose_lpr(F, lanes_hint);
-  // (F = 16, 4 lanes: 8 stays best, 5.52 vs 6.13 us, profiles/r05_hub_probe_nw.log)
-  if (lpr != 64) return kNarrowWG && lpr >= kNarrowMin && lpr == 2 ? 16 : 8;
-  int64_t ipc = (nnz / 5760 + 2) / 4 * 4;
-  return (int32_t)std::min<int64_t>(32, std::max<int64_t>(12, ipc));
-}
-
-extern "C" int64_t gcnk_spmm_plan_bytes_host(const int32_t* rowptr, const int32_t* colind, int32_t M, int32_t K,
-                                             int64_t nnz, int32_t ipc, int32_t groups, float dense_threshold) {
-  if (!plan_args_ok(rowptr, colind, M, K, nnz, ipc, groups)) {
-    set_error("gcnk_spmm_plan_bytes: bad argument");
-    return GCNK_EARG;
-  }
-  return plan_size(rowptr, colind, M, K, nnz, ipc, groups, dense_threshold);
-}
-
-extern "C" int gcnk_spmm_plan_build_host(const int32_t* rowptr, const int32_t* colind, const float* val, int32_t M,
-                                         int32_t K, int64_t nnz, int32_t ipc, int32_t groups, float dense_threshold,
-                                         int32_t* plan, int64_t plan_bytes) {
-  if (!plan_args_ok(rowptr, colind, M, K, nnz, ipc, groups) || !plan || (nnz > 0 && !val)) {
-    set_error("gcnk_spmm_plan_build_host: bad argument");
-    return GCNK_EARG;
-  }
-  std::vector<int32_t> img;
-  const int rc = build_image(rowptr, colind, val, M, K, nnz, ipc, groups, dense_threshold, img);
-  if (rc) return rc;
-  if (plan_bytes < (int64_t)img.size() * 4) {
-    set_error("gcnk_spmm_plan_build_host: plan buffer %lld B < %lld B", (long long)plan_bytes,
-              (long long)img.size() * 4);
-    return GCNK_EARG;
-  }
-  std::copy(img.begin(), img.end(), plan);
-  return GCNK_OK;
-}
 
 extern "C" int64_t gcnk_spmm_plan_bytes(const int32_t* rowptr, const int32_t* colind, int32_t M, int32_t K,
                                         int64_t nnz, int32_t ipc, int32_t groups, float dense_threshold, void* stream) {
@@ -1930,32 +1319,11 @@ extern "C" int gcnk_spmm_plan_query(const void* plan, int32_t* out16, void* stre
   int rc = hip_check(hipMemcpyAsync(out16, plan, 64, hipMemcpyDeviceToHost, s), "plan query copy");
   if (rc) return rc;
   rc = hip_check(hipStreamSynchronize(s), "plan query sync");
-  if (!rc && out16[0] != kMagic) {
+  if (!rc && !plan_magic(out16)) {
     set_error("gcnk_spmm_plan_query: not a gcnk plan");
     return GCNK_EARG;
   }
   return rc;
-}
-
-static int64_t tile_fpad(int32_t F) { return ((int64_t)F + 15) & ~15LL; }
-
-static bool L_tops(const int32_t* hdr) { return ((uint32_t)hdr[12] >> 30) & 1; }
-
-static bool plan_magic(const int32_t* hdr) {
-  return hdr && hdr[0] == kMagic;
-}
-
-extern "C" int64_t gcnk_spmm_workspace_bytes(const int32_t* hdr, int32_t F) {
-  if (!plan_magic(hdr) || F < 0) return GCNK_EARG;
-  const int64_t ld = ((int64_t)F + 3) & ~3LL;
-  const int64_t rows = (int64_t)hdr[14] * ld * 4;
-  const int64_t slabs = (int64_t)hdr[10] * kRB * tile_fpad(F) * 4;
-  return ((rows + 255) & ~255LL) + slabs;
-}
-
-extern "C" int64_t gcnk_spmm_counter_bytes(const int32_t* hdr) {
-  if (!plan_magic(hdr)) return GCNK_EARG;
-  return (int64_t)hdr[7] * kMaxColTiles * 4;
 }
 
 static int spmm_impl(const void* plan, const int32_t* hdr, const float* B, int64_t ldb, int32_t F, float* C,
@@ -1969,7 +1337,7 @@ static int spmm_impl(const void* plan, const int32_t* hdr, const float* B, int64
     set_error("gcnk_spmm_csr_f32: bad argument (plan/header missing or not a gcnk plan, F=%d)", F);
     return GCNK_EARG;
   }
-  const int32_t M = hdr[1], K = hdr[2];
+  const int32_t M = hdr[kHdrM], K = hdr[kHdrK];
   if (M == 0 || F == 0) return GCNK_OK;
   const bool proj = pa.W != nullptr;
   if (proj && (!pa.C2 || pa.P <= 0 || pa.ldw < pa.P || pa.ldc2 < pa.P)) {
@@ -1994,9 +1362,9 @@ static int spmm_impl(const void* plan, const int32_t* hdr, const float* B, int64
     return GCNK_EARG;
   }
   const int lpr = choose_lpr(F, lanes_hint);
-  if (hdr[3] != 64 / lpr) {
+  if (hdr[kHdrGroups] != 64 / lpr) {
     set_error("gcnk_spmm_csr_f32: plan built for %d lane groups per wavefront, this F/lanes uses %d (gcnk_spmm_groups)",
-              hdr[3], 64 / lpr);
+              hdr[kHdrGroups], 64 / lpr);
     return GCNK_EARG;
   }
   const int64_t need = gcnk_spmm_workspace_bytes(hdr, F);
@@ -2028,9 +1396,9 @@ static int spmm_impl(const void* plan, const int32_t* hdr, const float* B, int64
   hipStream_t s = (hipStream_t)stream;
   if (proj) {
     // the projection needs whole rows in one group: row-kernel rows only, float4, one column tile
-    if (hdr[8] > 0 || !vec4 || F > lpr * 4 || pa.P > 32 || lpr < 16 || L_tops(hdr)) {
+    if (hdr[kHdrNtile] > 0 || !vec4 || F > lpr * 4 || pa.P > 32 || lpr < 16 || tops(hdr)) {
       set_error("gcnk_spmm_proj_f32: fused projection unsupported here (tile chunks=%d vec4=%d F=%d P=%d lanes=%d)",
-                hdr[8], (int)vec4, F, pa.P, lpr);
+                hdr[kHdrNtile], (int)vec4, F, pa.P, lpr);
       return GCNK_EUNSUP;
     }
   }
@@ -2041,7 +1409,7 @@ static int spmm_impl(const void* plan, const int32_t* hdr, const float* B, int64
     set_error("gcnk_spmm: F = %d too wide for the partial-slot offsets", F);
     return GCNK_EUNSUP;
   }
-  const int64_t rows_ws = ((int64_t)hdr[14] * part_ld * 4 + 255) & ~255LL;
+  const int64_t rows_ws = ((int64_t)hdr[kHdrNslots] * part_ld * 4 + 255) & ~255LL;
   float* slabs = workspace ? reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + rows_ws) : nullptr;
   const int64_t slab_ld = tile_fpad(F);
 
@@ -2058,7 +1426,7 @@ static int spmm_impl(const void* plan, const int32_t* hdr, const float* B, int64
     }
     const int4* td = reinterpret_cast<const int4*>(p + L.tdesc);
     // part 1: the single-chunk items [0, nsingle); part 2: the rest; 0: all
-    const int32_t nsingle = hdr[15];
+    const int32_t nsingle = hdr[kHdrNsingle];
     const int nt_need = (nt_total + nslices - 1) / nslices;
     const int32_t i0 = part == 2 ? nsingle : 0, i1 = part == 1 ? nsingle : (int32_t)L.ntile;
     TileArgs ta{td, p + L.tcols, reinterpret_cast<const float*>(p + L.tfrag), p + L.trows, dval, F, B,
@@ -2090,12 +1458,8 @@ static int spmm_impl(const void* plan, const int32_t* hdr, const float* B, int64
     // rows of more than kMaxSeg segments: their groups' sums, after the row kernel
     const int vec = vec4 ? 4 : 1;
     const dim3 grid((unsigned)L.nheavy, (unsigned)((F + 256 * vec - 1) / (256 * vec)));
-    if (vec4)
-      hipLaunchKernelGGL(spmm_heavy_top_kernel<4>, grid, dim3(256), 0, s, reinterpret_cast<const int4*>(p + L.heavy),
-                         (int32_t)L.nheavy, workspace, part_ld, F, C, ldc, e);
-    else
-      hipLaunchKernelGGL(spmm_heavy_top_kernel<1>, grid, dim3(256), 0, s, reinterpret_cast<const int4*>(p + L.heavy),
-                         (int32_t)L.nheavy, workspace, part_ld, F, C, ldc, e);
+    hipLaunchKernelGGL(vec4 ? spmm_heavy_top_kernel<4> : spmm_heavy_top_kernel<1>, grid, dim3(256), 0, s,
+                       reinterpret_cast<const int4*>(p + L.heavy), (int32_t)L.nheavy, workspace, part_ld, F, C, ldc, e);
     return launch_check("spmm_heavy_top_kernel");
   }
   return GCNK_OK;

@@ -78,8 +78,7 @@ def spmm(a, B, bias=None, epilogue=_lib.EPI_NONE, mask=None, scale=1.0, keep_pro
             _ptr(mask), mask.stride(0) if mask is not None else 0, float(scale),
             float(keep_prob), int(seed) & (2**64 - 1), int(offset) & (2**64 - 1), _ptr(rng_base),
             _ptr(ws), wsb, _ptr(cnt), 4 * cnt.numel() if cnt is not None else 0, int(lanes))
-    hdr = plan.hdr
-    nsingle, ntile, nunits = int(hdr[15]), int(hdr[8]), int(hdr[5])
+    nsingle, ntile, nunits = plan.nsingle, plan.ntile, plan.nunits
     with torch.cuda.device(B.device):
         if OVERLAP_TILE_PARTS and nsingle > 0 and (ntile > nsingle or nunits > 0):
             # the single-chunk tile blocks on a side stream, the rest (multi-chunk

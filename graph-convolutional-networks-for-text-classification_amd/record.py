@@ -131,7 +131,7 @@ class ForwardRecord:
                 lanes = 64
                 plan = adj.plan(ops.default_ipc(adj, F, lanes), int(lib.gcnk_spmm_groups(F, lanes)), DENSE_THRESHOLD)
                 # the fused projection runs on plans without dense tile blocks
-                kind = SPMM_PROJ if int(plan.hdr[8]) == 0 else None
+                kind = SPMM_PROJ if plan.ntile == 0 else None
             if kind is None:
                 lanes = 0
                 plan = adj.plan(ops.default_ipc(adj, F, lanes), int(lib.gcnk_spmm_groups(F, lanes)), DENSE_THRESHOLD)

@@ -39,7 +39,42 @@ def require_device(t, what):
 
 DENSE_THRESHOLD = 0.25  # row blocks at least this dense (condensed) run on the MFMA tile path
 
-class Plan:
+PLAN_MAGIC = 0x474E4B35  # plan header word 0 ("GNK5")
+# the 16 plan header words in order (csrc/spmm_plan.h kHdr*, include/gcnk.h)
+HEADER_WORDS = ("magic", "M", "K", "groups", "ipc", "nunits", "nhunits", "nheavy",
+                "ntile", "nred", "nslabs", "ntblk", "flags", "nnz", "nslots", "nsingle")
+
+
+def _word(name):
+    i = HEADER_WORDS.index(name)
+    return property(lambda self: int(self.hdr[i]))
+
+
+class PlanHeader:
+    """Read-only named fields over a 16-word plan header `hdr` (a ctypes or
+    numpy int32 array, or a list)."""
+    __slots__ = ("hdr",)
+
+    def __init__(self, hdr):
+        self.hdr = hdr
+
+    magic, M, K, groups, ipc, nnz = (_word(n) for n in ("magic", "M", "K", "groups", "ipc", "nnz"))
+    nunits = _word("nunits")      # row units, heavy region included
+    nhunits = _word("nhunits")    # heavy segments (the heavy region, padded)
+    nheavy = _word("nheavy")      # heavy entries: rows of more than one segment
+    ntile = _word("ntile")        # tile chunks
+    nred = _word("nred")          # multi-chunk tile blocks
+    nslabs = _word("nslabs")
+    ntblk = _word("ntblk")        # tile blocks
+    nslots = _word("nslots")      # partial slots
+    nsingle = _word("nsingle")    # chunk items of single-chunk tile blocks (listed first)
+    _flags = _word("flags")       # has_diag | segp << 1 | tops << 30
+    has_diag = property(lambda self: bool(self._flags & 1))
+    segp = property(lambda self: (self._flags >> 1) & ((1 << 29) - 1))
+    has_tops = property(lambda self: bool((self._flags >> 30) & 1))
+
+
+class Plan(PlanHeader):
     """A built SpMM plan: device buffer + the 16-word host header (gcnk.h).
 
     Plans with arrival counters (heavy rows of several segments, combined
@@ -51,7 +86,7 @@ class Plan:
     on two streams), handed out from SPARE_REGIONS regions zeroed when the
     plan is built, so a captured graph holds no memset node."""
 
-    __slots__ = ("buf", "hdr", "_counters", "_spares", "_captured", "_lock")
+    __slots__ = ("buf", "_counters", "_spares", "_captured", "_lock")
     SPARE_REGIONS = 16   # pre-zeroed regions handed to capturing streams
 
     def __init__(self, buf, hdr):

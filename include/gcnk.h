@@ -116,10 +116,13 @@ const char* gcnk_last_error(void);
  * same plan image from HOST arrays into host memory (no device needed).
  *
  * Plan header (16 int32, first words of the plan; gcnk_spmm_plan_query):
- *   0 magic 'GNK5'  1 M  2 K  3 groups  4 ipc  5 row units
- *   6 heavy segments  7 heavy rows of > 1 segment  8 tile chunks
- *   9 multi-chunk blocks  10 slabs  11 tile blocks  12 diagonal kept aside
- *   (0/1)  13 nnz  14 partial slots  15 chunk items of single-chunk tile blocks
+ *   0 magic 'GNK5'  1 M  2 K  3 groups (lane groups per wavefront, 64 / LPR)
+ *   4 ipc  5 row units  6 heavy segments (heavy region, padded)
+ *   7 heavy rows of > 1 segment  8 tile chunks  9 multi-chunk blocks  10 slabs
+ *   11 tile blocks  12 diagonal kept aside | segp << 1 | tops << 30  13 nnz
+ *   14 partial slots  15 chunk items of single-chunk tile blocks (listed first)
+ * (segp: stride of the heavy segments' padded item copies, 0 = none; tops: some
+ * row has more than 64 segments.  csrc/spmm_plan.h names the words.)
  * (Rounds 2-3 also built a hub-split plan and a split-K plan for R8's doc-topic
  * operands; both measured slower than this plan and were removed in ABI 8 --
  * DESIGN.md keeps their numbers.)

@@ -1,5 +1,5 @@
 // Which XCD runs workgroup b?  The row plan deals units to workgroups assuming
-// round-robin dispatch (workgroup b on XCD b % 8, csrc/spmm.hip "XCD classes");
+// round-robin dispatch (workgroup b on XCD b % 8, csrc/spmm_plan.cpp "XCD classes");
 // this reads each workgroup's XCC_ID hardware register and reports how often
 // that holds, for the north-star launch shape (1,832 x 256 threads) and others.
 //   hipcc -O3 --offload-arch=gfx950 xcc_map.hip -o xcc_map && ./xcc_map

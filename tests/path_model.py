@@ -1,6 +1,6 @@
 """Pure-Python model of the row-unit SpMM schedule (test infrastructure).
 
-Mirrors, step by step, the host unit planning (spmm.hip host_plan, row part:
+Mirrors, step by step, the host unit planning (csrc/spmm_plan.cpp plan_rows:
 light rows, heavy rows cut at XCD column-class boundaries and into segments,
 the class-by-workgroup layout with empty padding units) and the row kernel's
 control flow (light units per lane group, heavy segments shared by lane

@@ -82,8 +82,8 @@ def test_spmm_r8_adjacency(r8, F):
     # columns with the self loop kept aside (diagonal epilogue)
     got_t = spmm(a, B.to(DEV), dense=0.05)
     _close(got_t, ref)
-    hdr = [p for k, p in a._plans.items() if abs(k[2]) == 0.05][0].header
-    assert hdr[8] > 0 and (hdr[12] & 1) == 1, "R8 document rows: MFMA tiles over the topic columns + diagonal"
+    plan = [p for k, p in a._plans.items() if abs(k[2]) == 0.05][0]
+    assert plan.ntile > 0 and plan.has_diag, "R8 document rows: MFMA tiles over the topic columns + diagonal"
 
 
 @pytest.mark.parametrize("F", [1, 3, 7, 8, 16, 64, 100, 200, 256, 257, 1000, 4096])
@@ -122,7 +122,7 @@ def test_spmm_power_law_rows_and_linearity(rmat17, F):
     B2 = torch.from_numpy(rng.standard_normal((n, F)).astype(np.float32)).to(DEV)
     C1 = spmm(a, B1)
     if F == 256:   # rows past 64 segments: groups + the top-entry launch (spmm_heavy_top_kernel)
-        assert any((p.header[12] >> 30) & 1 for p in a._plans.values())
+        assert any(p.has_tops for p in a._plans.values())
     rows = np.unique(np.concatenate([np.argsort(deg)[-16:], rng.choice(n, 400, replace=False),
                                      np.flatnonzero(deg == 0)[:8]]))
     sub_rp = np.concatenate([[0], np.cumsum(deg[rows])])
@@ -224,9 +224,9 @@ def test_spmm_hybrid_dense_blocks(F, M):
                epilogue=_lib.EPI_BIAS_RELU_DROP, mask=torch.from_numpy(mask).to(DEV), scale=1.5)
     acc = csr_ref.spmm_csr(rp, ci, v, B)
     _close(got, csr_ref.spmm_epilogue(acc, bias, relu=True, mask=mask, scale=1.5), atol=2e-5 * np.sqrt(K))
-    hdr = list(a._plans.values())[0].header
-    assert hdr[8] > 0 and hdr[9] > 0, "dense blocks (single and multi-chunk) expected on the tile path"
-    assert (hdr[12] & 1) == (1 if M == K else 0), "diagonal entries of a square operand's tile rows are kept aside"
+    plan = list(a._plans.values())[0]
+    assert plan.ntile > 0 and plan.nred > 0, "dense blocks (single and multi-chunk) expected on the tile path"
+    assert plan.has_diag == (M == K), "diagonal entries of a square operand's tile rows are kept aside"
     # tile path disabled: the row kernel alone gives the same product
     got2 = spmm(a, torch.from_numpy(B).to(DEV), dense=2.0)
     _close(got2, acc, atol=2e-5 * np.sqrt(K))
@@ -1074,8 +1074,8 @@ def test_spmm_two_part_launch_matches_single(monkeypatch, r8):
             a = from_arrays(rp, ci, v, (700, K), DEV)
         B = torch.from_numpy(rng.standard_normal((K, 200)).astype(np.float32)).to(DEV)
         one = ops.spmm(a, B)
-        hdr = list(a._plans.values())[-1].header
-        assert hdr[15] > 0 and hdr[8] > hdr[15], "both single- and multi-chunk tile blocks expected"
+        plan = list(a._plans.values())[-1]
+        assert plan.nsingle > 0 and plan.ntile > plan.nsingle, "both single- and multi-chunk tile blocks expected"
         monkeypatch.setattr(ops, "OVERLAP_TILE_PARTS", True)
         two = ops.spmm(a, B)
         torch.cuda.synchronize()
@@ -1161,7 +1161,7 @@ def test_tile_path_repeat_streams_and_graph_replay_are_exact(r8, dense, monkeypa
     W = torch.randn(r8["nfeat"], 200, generator=torch.Generator().manual_seed(11)).to(DEV)
     one = ops.spmm(x, W, dense=dense)
     plan = list(x._plans.values())[-1]
-    assert plan.header[9] > 0, "R8 X's topic rows form a multi-chunk tile block"
+    assert plan.nred > 0, "R8 X's topic rows form a multi-chunk tile block"
     ops_spmm = ops.spmm
     def spmm_d(*a, **k):
         return ops_spmm(*a, dense=dense, **k)

@@ -133,7 +133,7 @@ def _spmm_raw(a, B, bias, seed, offset, base, ldm, keep, ldc=None, ipc=None, lan
     """gcnk_spmm_csr_f32 / _part (parts 1 then 2) / gcnk_spmm_proj_f32 (W given)
     with the hash epilogue and every argument explicit, as ops.spmm /
     ops.spmm_proj marshal them.  Returns (rc, the whole C buffer [M x ldc]
-    pre-filled with 7 -- None when not stored --, C2, plan header)."""
+    pre-filled with 7 -- None when not stored --, C2, the plan)."""
     lib = _lib.load()
     M, K = a.shape
     F = B.shape[1]
@@ -161,7 +161,7 @@ def _spmm_raw(a, B, bias, seed, offset, base, ldm, keep, ldc=None, ipc=None, lan
         rc = lib.gcnk_spmm_csr_f32_part(*head, *tail, 1, st) or lib.gcnk_spmm_csr_f32_part(*head, *tail, 2, st)
     else:
         rc = lib.gcnk_spmm_csr_f32(*head, *tail, st)
-    return rc, buf, C2, plan.header
+    return rc, buf, C2, plan
 
 
 def _t(x):
@@ -191,9 +191,9 @@ def test_row_kernel_light_and_heavy_rows(light_heavy, F):
     deg = int(np.diff(rp).max())
 
     def run(seed, offset, base, ldm, keep, store):
-        rc, buf, _, hdr = _spmm_raw(a, Bt, bt, seed, offset, base, ldm, keep, ldc=2 * F, dense=2.0)
+        rc, buf, _, plan = _spmm_raw(a, Bt, bt, seed, offset, base, ldm, keep, ldc=2 * F, dense=2.0)
         _lib.check(rc, "gcnk_spmm_csr_f32")
-        assert hdr[8] == 0 and hdr[5] > 0 and hdr[6] > 0, "row kernel only: light units and heavy segments"
+        assert plan.ntile == 0 and plan.nunits > 0 and plan.nhunits > 0, "row kernel only: light units and heavy segments"
         assert bool((buf[:, F:] == 7.0).all()), "columns past F of the output buffer are not the kernel's"
         return buf[:, :F], None
     _check_kernel(run, pre, h_atol=2e-5 * np.sqrt(deg) * SCALE)
@@ -228,9 +228,9 @@ def test_heavy_row_combines_and_top_entry(F, ipc, lanes):
     Bt, bt = _t(B), _t(bias)
 
     def run(seed, offset, base, ldm, keep, store):
-        rc, buf, _, hdr = _spmm_raw(a, Bt, bt, seed, offset, base, ldm, keep, ipc=ipc, lanes=lanes)
+        rc, buf, _, plan = _spmm_raw(a, Bt, bt, seed, offset, base, ldm, keep, ipc=ipc, lanes=lanes)
         _lib.check(rc, "gcnk_spmm_csr_f32")
-        assert hdr[7] >= 6 and (hdr[12] >> 30) & 1, "multi-segment heavy rows and a top entry expected"
+        assert plan.nheavy >= 6 and plan.has_tops, "multi-segment heavy rows and a top entry expected"
         return buf, None
     _check_kernel(run, pre, h_atol=2e-5 * np.sqrt(70_000) * SCALE)
 
@@ -251,11 +251,11 @@ def test_tile_epilogue_slab_reduce_and_two_part_launch(F, M):
     Bt, bt = _t(B), _t(bias)
 
     def run(seed, offset, base, ldm, keep, store):
-        rc, buf, _, hdr = _spmm_raw(a, Bt, bt, seed, offset, base, ldm, keep)
+        rc, buf, _, plan = _spmm_raw(a, Bt, bt, seed, offset, base, ldm, keep)
         _lib.check(rc, "gcnk_spmm_csr_f32")
-        assert hdr[8] > 0 and hdr[9] > 0, "dense blocks (single and multi-chunk) expected on the tile path"
-        assert (hdr[12] & 1) == (1 if M == K else 0)
-        assert hdr[15] > 0 and hdr[8] > hdr[15], "both single- and multi-chunk tile blocks expected"
+        assert plan.ntile > 0 and plan.nred > 0, "dense blocks (single and multi-chunk) expected on the tile path"
+        assert plan.has_diag == (M == K)
+        assert plan.nsingle > 0 and plan.ntile > plan.nsingle, "both single- and multi-chunk tile blocks expected"
         rc2, two, _, _ = _spmm_raw(a, Bt, bt, seed, offset, base, ldm, keep, parts=True)
         _lib.check(rc2, "gcnk_spmm_csr_f32_part")
         assert torch.equal(two, buf), "two-part launch"
@@ -281,9 +281,9 @@ def test_fused_projection(light_heavy, P):
     s2_atol = 2e-4 * max(1.0, SCALE * pre.max())
     if P <= 32:
         def run(seed, offset, base, ldm, keep, store):
-            rc, buf, C2, hdr = _spmm_raw(a, Bt, bt, seed, offset, base, ldm, keep, W=Wt, store_main=store)
+            rc, buf, C2, plan = _spmm_raw(a, Bt, bt, seed, offset, base, ldm, keep, W=Wt, store_main=store)
             _lib.check(rc, "gcnk_spmm_proj_f32")       # (GCNK_EUNSUP would mean the fused kernel did not run)
-            assert hdr[8] == 0
+            assert plan.ntile == 0
             return buf, C2
         _check_kernel(run, pre, h_atol=2e-5 * SCALE, W2=W2, s2_atol=s2_atol, unstored=True)
         H, S2 = ops.spmm_proj(a, Bt, Wt, bias=bt, epilogue=HASH, scale=SCALE, keep_prob=0.5, seed=5,
