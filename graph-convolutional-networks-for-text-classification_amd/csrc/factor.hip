@@ -33,6 +33,7 @@
 
 
 #include <algorithm>
+#include <type_traits>
 
 namespace gcnk {
 namespace {
@@ -43,8 +44,9 @@ constexpr int kRB = 32;         // rows per workgroup
 constexpr int kThreads = 512;   // 8 waves: 2 row strips x 4 column quarters
 constexpr int kMaxKsteps = 32;  // Kc <= 128
 constexpr int kProjMax = 32;    // projection width: P <= 32 (NP = 1 or 2 MFMA n-tiles)
-// zero floats after the staged W1[Kc]: the n-tiles past F read up to column
-// 64 NTQ - 1 of the last k-row, so the pad covers 64 NTQ - F of them (at least 64)
+// zero floats after the staged W1[Kc]: the last real n-tile reads up to column
+// 16 ceil(F / 16) - 1 of the last k-row; the pad (64 NTQ - F, at least 64) is
+// sized for every tile up to column 64 NTQ - 1, which the kernel once computed
 __host__ __device__ constexpr int bpad(int f, int ntq) { return 64 * ntq - f > 64 ? 64 * ntq - f : 64; }
 // block record (factor.py): 33 row offsets, 3 pad | 32 row ids (-1 past M) |
 // A_H items int2 {hub, value}.  Block b holds rows perm[32 b .. 32 b + 31]: the
@@ -53,8 +55,9 @@ __host__ __device__ constexpr int bpad(int f, int ntq) { return 64 * ntq - f > 6
 constexpr int kRecRow = 36, kRecHead = 68;
 // compile-time shapes (every MFMA unconditional, operands in fixed registers):
 // KS k-steps of U W1[Kc] (Kc <= 4 KS; U columns past Kc read as zero, W1 rows
-// past Kc staged as zero) and NTQ 16-column tiles per quarter of F (F <= 64 NTQ;
-// columns past F are computed from zeroed or W1 LDS words and never used)
+// past Kc staged as zero) and up to NTQ 16-column tiles per wave (F <= 64 NTQ;
+// only tiles holding a column of F are computed; the last one's columns past F
+// come from zeroed or W1 LDS words and are never used)
 // (18: the 20ng-shaped X's 70 topic-weight columns, whose W1 rows at 25 k-steps
 // would take the block's LDS past 160 KiB)
 __host__ __device__ constexpr int pick_ks(int kc) { return kc <= 52 ? 13 : kc <= 72 ? 18 : kc <= 100 ? 25 : 32; }
@@ -170,15 +173,47 @@ hubfactor_gc1_kernel(FactorArgs a) {
   f32x4 acc[NTQ];
 #pragma unroll
   for (int i = 0; i < NTQ; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const int c0 = quarter * NTQ * 16 + (lane & 15);
+  // The phase is bound by MFMA issue (the fragment reads hide behind the other
+  // wave of the SIMD: reading them ahead of the MFMAs changed nothing or lost,
+  // DESIGN section 5), so n-tiles that hold no column of F are not computed.
+  // The T = ceil(F / 16) real tiles are dealt round-robin over the column
+  // quarters, in opposite directions in the two strips (tile g of strip 0 to
+  // quarter g % 4, of strip 1 to quarter 3 - g % 4): whether the eight waves sit
+  // on the four SIMDs by wave id modulo 4 or in pairs, no SIMD carries more
+  // than ceil(T / 2) tiles a k-step (R8: 7, 7, 6, 6 in place of 8 each).  A slot
+  // without a real tile keeps its zero accumulator and stores it: those columns
+  // of s_Z feed phase 3 against zero W2 rows and must be finite.
+  const int qe = strip ? 3 - quarter : quarter;
+  const int c0 = qe * 16 + (lane & 15);
+  constexpr int kTileStep = 64;   // columns between a wave's consecutive tiles
+  {
+    const int T = (F + 15) >> 4;
+    const int nt = __builtin_amdgcn_readfirstlane(min(max((T - qe + 3) >> 2, 0), NTQ));
+    auto run = [&](auto ntc) __attribute__((always_inline)) {
+      constexpr int NT = decltype(ntc)::value;
 #pragma unroll
-  for (int s = 0; s < KS; ++s) {
-    const float* br = s_B + (4 * s + (lane >> 4)) * F + c0;
-    float bf[NTQ];
+      for (int s = 0; s < KS; ++s) {
+        const float* br = s_B + (4 * s + (lane >> 4)) * F + c0;
+        float bf[NT];
 #pragma unroll
-    for (int i = 0; i < NTQ; ++i) bf[i] = br[i * 16];
+        for (int i = 0; i < NT; ++i) bf[i] = br[i * kTileStep];
 #pragma unroll
-    for (int i = 0; i < NTQ; ++i) acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[s], bf[i], acc[i], 0, 0, 0);
+        for (int i = 0; i < NT; ++i) acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[s], bf[i], acc[i], 0, 0, 0);
+      }
+    };
+    if (nt == NTQ) {
+      run(std::integral_constant<int, NTQ>{});
+    } else if (nt == NTQ - 1) {
+      run(std::integral_constant<int, NTQ - 1>{});
+    } else {   // narrow F: fewer real tiles, uniform tests
+#pragma unroll
+      for (int s = 0; s < KS; ++s) {
+        const float* br = s_B + (4 * s + (lane >> 4)) * F + c0;
+#pragma unroll
+        for (int i = 0; i < NTQ - 2; ++i)
+          if (i < nt) acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[s], br[i * kTileStep], acc[i], 0, 0, 0);
+      }
+    }
   }
   __syncthreads();  // s_B is overwritten by s_Z below
   stamp(a.epi, 1);
@@ -187,7 +222,7 @@ hubfactor_gc1_kernel(FactorArgs a) {
   for (int i = 0; i < NTQ; ++i)
 #pragma unroll
     for (int r = 0; r < 4; ++r)
-      s_Z[(16 * strip + (lane >> 4) * 4 + r) * Fz + c0 - (lane & 15) + i * 16 + (lane & 15)] = acc[i][r];
+      s_Z[(16 * strip + (lane >> 4) * 4 + r) * Fz + c0 + i * kTileStep] = acc[i][r];
   __syncthreads();
 
   // ---- 2. row-major epilogue, 16 threads per row, NTQ float4 columns each
@@ -201,26 +236,41 @@ hubfactor_gc1_kernel(FactorArgs a) {
     float4 z[NTQ];
 #pragma unroll
     for (int u = 0; u < NTQ; ++u) z[u] = *reinterpret_cast<const float4*>(s_Z + r * Fz + 4 * (c16 + 16 * u));
-    // one item at a time: batching the items' loads (4 per round, selects past
-    // the row) measured slower, 2.28 against 2.12 us per block (LDS throughput,
-    // not the item chain, bounds this loop; profiles/r03_factor.md)
     const int2* it = reinterpret_cast<const int2*>(s_rec + kRecHead);
     const int k1 = s_rec[r + 1];
+    // b1's slots with the z reads, one wait for all of them (slots past F read
+    // the words after s_bias -- inside the block's LDS -- and are dropped)
+    float4 bv[NTQ];
+#pragma unroll
+    for (int u = 0; u < NTQ; ++u) bv[u] = *reinterpret_cast<const float4*>(s_bias + 4 * (c16 + 16 * u));
+    // One item at a time, the next item's word read ahead of this item's S_T
+    // rows (index clamped to the row's last item; the word read past the end is
+    // never used): an item costs one LDS round trip, not two, which shortens the
+    // blocks holding a hub row's long list.  Across the eight waves the loop is
+    // bound by LDS throughput, not by the item chain: every form that reads S_T
+    // rows it does not need lost (groups of 2-4 items with masked values past the
+    // row's end, a rotating prefetch of the next item's rows).
+    {
+      int k = s_rec[r];
+      const int kl = k1 - 1;
+      int2 p = it[max(min(k, kl), 0)];
 #pragma unroll 2
-    for (int k = s_rec[r]; k < k1; ++k) {
-      const int2 p = it[k];
-      const float v = __int_as_float(p.y);
-      const float* srow = s_S + p.x * F + 4 * c16;
-      float4 sv[NTQ];
+      for (; k < k1; ++k) {
+        const int2 pn = it[min(k + 1, kl)];
+        const float v = __int_as_float(p.y);
+        const float* srow = s_S + p.x * F + 4 * c16;
+        float4 sv[NTQ];
 #pragma unroll
-      for (int u = 0; u < NTQ; ++u) {
-        // the last column slot only where it lies inside F (R8: 2 of 16 lanes):
-        // inactive lanes move no LDS bytes, and this loop is LDS-bandwidth-bound
-        if (u == NTQ - 1 && c16 + 16 * u >= Q) { sv[u] = make_float4(0.f, 0.f, 0.f, 0.f); continue; }
-        sv[u] = *reinterpret_cast<const float4*>(srow + 64 * u);
+        for (int u = 0; u < NTQ; ++u) {
+          // the last column slot only where it lies inside F (R8: 2 of 16 lanes):
+          // inactive lanes move no LDS bytes
+          if (u == NTQ - 1 && c16 + 16 * u >= Q) { sv[u] = make_float4(0.f, 0.f, 0.f, 0.f); continue; }
+          sv[u] = *reinterpret_cast<const float4*>(srow + 64 * u);
+        }
+#pragma unroll
+        for (int u = 0; u < NTQ; ++u) Vec<4>::fma(z[u], v, sv[u]);
+        p = pn;
       }
-#pragma unroll
-      for (int u = 0; u < NTQ; ++u) Vec<4>::fma(z[u], v, sv[u]);
     }
     if (row >= 0) {
       auto put = [&](int q, const float4& h) __attribute__((always_inline)) {
@@ -238,16 +288,15 @@ hubfactor_gc1_kernel(FactorArgs a) {
         for (int u = 0; u < NTQ; ++u) {
           const int q = c16 + 16 * u;
           if (q < Q) {
-            const float4 bv = *reinterpret_cast<const float4*>(s_bias + 4 * q);
-            put(q, make_float4(fmaxf(z[u].x + bv.x, 0.f), fmaxf(z[u].y + bv.y, 0.f), fmaxf(z[u].z + bv.z, 0.f),
-                               fmaxf(z[u].w + bv.w, 0.f)));
+            put(q, make_float4(fmaxf(z[u].x + bv[u].x, 0.f), fmaxf(z[u].y + bv[u].y, 0.f),
+                               fmaxf(z[u].z + bv[u].z, 0.f), fmaxf(z[u].w + bv[u].w, 0.f)));
           }
         }
       } else {
 #pragma unroll
         for (int u = 0; u < NTQ; ++u) {
           const int q = c16 + 16 * u;
-          if (q < Q) put(q, Vec<4>::epi(a.epi, z[u], *reinterpret_cast<const float4*>(s_bias + 4 * q), row, 4 * (int64_t)q));
+          if (q < Q) put(q, Vec<4>::epi(a.epi, z[u], bv[u], row, 4 * (int64_t)q));
         }
       }
     }
@@ -286,8 +335,12 @@ hubfactor_gc1_kernel(FactorArgs a) {
 #pragma unroll
     for (int t = 0; t < NP; ++t)
       *reinterpret_cast<f32x4*>(s_red + (((t * 3 + quarter - 1) * 2 + strip) * 64 + lane) * 4) = pc[t];
+  // the lane's four output row ids: one 16-B read ahead of the barrier (a read
+  // per store, each behind its own wait, was four round trips after it)
+  const int4 orow = *reinterpret_cast<const int4*>(s_rec + kRecRow + 16 * strip + (lane >> 4) * 4);
   __syncthreads();
   if (quarter == 0) {
+    const int rid[4] = {orow.x, orow.y, orow.z, orow.w};
 #pragma unroll
     for (int t = 0; t < NP; ++t) {
 #pragma unroll
@@ -296,7 +349,7 @@ hubfactor_gc1_kernel(FactorArgs a) {
       const int p = 16 * t + (lane & 15);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int64_t row = s_rec[kRecRow + 16 * strip + (lane >> 4) * 4 + r];
+        const int64_t row = rid[r];
         if (row >= 0 && p < a.P) a.C2[row * a.ldc2 + p] = pc[t][r];
       }
     }
