@@ -34,7 +34,7 @@ from torch.nn import Module, Parameter
 
 from . import _lib
 from . import ops
-from .ops import GCNFn, GraphConvFn, Operand
+from .ops import Epilogue, GCNFn, GraphConvFn, Operand
 from .sparse import as_csr
 
 
@@ -196,6 +196,9 @@ def _vkey(t, aliases):
     return (getattr(t, "_version", None),) + tuple(p._version for p in aliases)
 
 
+_NO_DROPOUT = Epilogue(_lib.EPI_BIAS_RELU)
+
+
 class GraphConvolution(Module):
     """out = adj @ (infeatn @ weight) + bias   (reference layer.py:25-123)."""
 
@@ -222,8 +225,7 @@ class GraphConvolution(Module):
     def forward(self, infeatn, adj):
         xop = Operand(infeatn)
         a = as_csr(adj)
-        x_dense = xop.dense if xop.dense is not None else None
-        return GraphConvFn.apply(self.weight, self.bias, x_dense, xop, a)
+        return GraphConvFn.apply(self.weight, self.bias, xop.dense, xop, a)
 
     def __repr__(self):
         return f"{type(self).__name__} ({self.in_features} -> {self.out_features})"
@@ -245,21 +247,22 @@ class GCN(Module):
         self._memo = None   # (x, adj, version keys, Operand, CSR) of the last call
 
     def _dropout_args(self, nrows, device):
-        """Epilogue code and mask/scale for layer.py:185 (ATen dropout semantics)."""
+        """gc1's ops.Epilogue for layer.py:185 (ATen dropout semantics)."""
         p = float(self.dropout)
         if not self.training or p == 0.0:   # ATen returns the input untouched (no RNG draw)
-            return _lib.EPI_BIAS_RELU, None, 1.0, 1.0, 0, 0
+            return _NO_DROPOUT
         nhid = self.gc1.out_features
         if p >= 1.0:                         # ATen: input * 0
-            return _lib.EPI_BIAS_RELU_DROP, torch.zeros((nrows, nhid), dtype=torch.uint8, device=device), \
-                0.0, 0.0, 0, 0
+            return Epilogue(_lib.EPI_BIAS_RELU_DROP, torch.zeros((nrows, nhid), dtype=torch.uint8, device=device),
+                            0.0, 0.0)
         # noise = bernoulli(1-p) / (1-p) with the division done in float32 (ATen)
         scale = float(torch.ones((), dtype=torch.float32).div_(1.0 - p))
         if self.dropout_rng == "cpu":
             mask = host_keep_mask((nrows, nhid), 1.0 - p).to(device, non_blocking=True)
-            return _lib.EPI_BIAS_RELU_DROP, mask, scale, 1.0 - p, 0, 0
-        seed = int(torch.initial_seed()) & (2**64 - 1)
-        return _lib.EPI_BIAS_RELU_HASH, None, scale, 1.0 - p, seed, 0
+            return Epilogue(_lib.EPI_BIAS_RELU_DROP, mask, scale, 1.0 - p)
+        if self._rng_base.device != device:
+            raise RuntimeError(f"GCN buffers are on {self._rng_base.device}, operands on {device}: call .to()")
+        return Epilogue(_lib.EPI_BIAS_RELU_HASH, None, scale, 1.0 - p, int(torch.initial_seed()), 0, self._rng_base)
 
     def _operands(self, x, adj):
         """(Operand of x, CSR of adj), memoised for the inputs of the previous
@@ -276,22 +279,15 @@ class GCN(Module):
 
     def forward(self, x, adj):
         xop, a = self._operands(x, adj)
-        epi, mask, scale, keep, seed, offset = self._dropout_args(a.shape[0], a.device)
+        epi = self._dropout_args(a.shape[0], a.device)
         W1, b1, W2, b2 = self.gc1.weight, self.gc1.bias, self.gc2.weight, self.gc2.bias
         # H1 is needed only by a backward pass; inference never writes it to HBM
         keep_h1 = torch.is_grad_enabled() and (W1.requires_grad or W2.requires_grad or
                                                (b1 is not None and b1.requires_grad) or
                                                (b2 is not None and b2.requires_grad))
-        hashed = epi == _lib.EPI_BIAS_RELU_HASH
-        if hashed and self._rng_base.device != a.device:
-            raise RuntimeError(f"GCN buffers are on {self._rng_base.device}, operands on {a.device}: call .to()")
-        rng = self._rng_base if hashed else None
-        out = None
-        if not keep_h1:   # inference (trainer.py:382 under no_grad): no autograd node, one C call
-            res = ops.record_forward(W1, b1, W2, b2, xop, a, epi, mask, scale, keep, seed, offset, False, rng)
-            out = res[0] if res is not None else None
-        if out is None:
-            out = GCNFn.apply(W1, b1, W2, b2, xop, a, epi, mask, scale, keep, seed, offset, keep_h1, rng)
-        if hashed:   # the next call (or graph replay) draws the next rows*nhid hash positions
+        # inference (trainer.py:382 under no_grad): no autograd node, one C call
+        res = ops.record_forward(W1, b1, W2, b2, xop, a, epi, False) if not keep_h1 else None
+        out = res[0] if res is not None else GCNFn.apply(W1, b1, W2, b2, xop, a, epi, keep_h1)
+        if epi.rng_base is not None:   # the next call (or graph replay) draws the next rows*nhid hash positions
             self._rng_base.add_(a.shape[0] * self.gc1.out_features)
         return out

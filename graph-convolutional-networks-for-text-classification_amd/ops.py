@@ -6,6 +6,7 @@ so every op is asynchronous and hipGraph-capturable.
 """
 import ctypes
 import os
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -38,8 +39,46 @@ def default_ipc(a, F, lanes=0):
     return int(_lib.load().gcnk_spmm_default_ipc(a.shape[0], a.nnz, F, int(lanes)))
 
 
+def plan_for(a, F, lanes=0, ipc=None, dense=DENSE_THRESHOLD):
+    """The SpMM plan of CSR ``a`` for a width-F product (cached on ``a``)."""
+    if ipc is None:
+        ipc = default_ipc(a, F, lanes)
+    return a.plan(ipc, int(_lib.load().gcnk_spmm_groups(F, int(lanes))), dense)
+
+
+def workspace(nbytes, device):
+    """An uninitialised workspace of ``nbytes`` (whole floats), None for 0."""
+    return torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=device) if nbytes > 0 else None
+
+
+class Epilogue(NamedTuple):
+    """What follows an aggregation's sum (include/gcnk.h GCNK_EPI_*, reference
+    layer.py:185), under the ops' keyword names: ``**epi._asdict()`` passes it on."""
+    epilogue: int = _lib.EPI_NONE
+    mask: Optional[torch.Tensor] = None
+    scale: float = 1.0
+    keep_prob: float = 1.0
+    seed: int = 0
+    offset: int = 0
+    rng_base: Optional[torch.Tensor] = None
+
+    def on(self, device):
+        """Checked for operands on ``device``: the mask contiguous, the numbers Python floats and ints."""
+        code, m, scale, keep_prob, seed, offset, t = self
+        if t is not None and (t.dtype != torch.int64 or t.numel() < 1 or t.device != device):
+            raise RuntimeError("rng_base must be an int64 tensor of >= 1 element on the operand's device")
+        return Epilogue(code, m if m is None else m.contiguous(), float(scale), float(keep_prob), int(seed),
+                        int(offset), t)
+
+    def c_args(self):
+        """The C-ABI's arguments epilogue ... rng_base (the same in every entry point) of a checked Epilogue."""
+        code, m, scale, keep_prob, seed, offset, r = self
+        return (code, m.data_ptr() if m is not None else None, m.stride(0) if m is not None else 0, scale,
+                keep_prob, seed & (2**64 - 1), offset & (2**64 - 1), r.data_ptr() if r is not None else None)
+
+
 def spmm(a, B, bias=None, epilogue=_lib.EPI_NONE, mask=None, scale=1.0, keep_prob=1.0, seed=0, offset=0,
-         out=None, ipc=None, lanes=0, dense=None, rng_base=None):
+         out=None, ipc=None, lanes=0, dense=DENSE_THRESHOLD, rng_base=None):
     """C = epi(A @ B) with A a CSR (or torch sparse) and B dense [K, F].
 
     Replaces ``th.spmm(adj, support)`` (reference layer.py:106) and
@@ -50,7 +89,7 @@ def spmm(a, B, bias=None, epilogue=_lib.EPI_NONE, mask=None, scale=1.0, keep_pro
     include/gcnk.h GCNK_EPI_BIAS_RELU_HASH)."""
     a = as_csr(a)
     B = _dense_f32(B, "dense operand")
-    _check_rng_base(rng_base, B.device)
+    epi = Epilogue(epilogue, mask, scale, keep_prob, seed, offset, rng_base).on(B.device)
     M, K = a.shape
     if B.shape[0] != K:
         raise RuntimeError(f"spmm shape mismatch: sparse {tuple(a.shape)} @ dense {tuple(B.shape)}")
@@ -61,22 +100,15 @@ def spmm(a, B, bias=None, epilogue=_lib.EPI_NONE, mask=None, scale=1.0, keep_pro
         out = torch.empty((M, F), dtype=torch.float32, device=B.device)
     if bias is not None:
         bias = bias.contiguous()
-    if mask is not None:
-        mask = mask.contiguous()
     lib = _lib.load()
-    if ipc is None:
-        ipc = default_ipc(a, F, lanes)
-    groups = int(lib.gcnk_spmm_groups(F, int(lanes)))
-    plan = a.plan(ipc, groups, DENSE_THRESHOLD if dense is None else dense)
+    plan = plan_for(a, F, lanes, ipc, dense)
     wsb = plan.workspace_bytes(F)
-    ws = torch.empty((wsb + 3) // 4, dtype=torch.float32, device=B.device) if wsb > 0 else None
+    ws = workspace(wsb, B.device)
     cnt = plan.counters(B.device)
     args = (_ptr(plan.buf), ctypes.cast(plan.hdr, ctypes.c_void_p),
             _ptr(B), B.stride(0), F,
             _ptr(out), out.stride(0),
-            _ptr(bias), epilogue,
-            _ptr(mask), mask.stride(0) if mask is not None else 0, float(scale),
-            float(keep_prob), int(seed) & (2**64 - 1), int(offset) & (2**64 - 1), _ptr(rng_base),
+            _ptr(bias), *epi.c_args(),
             _ptr(ws), wsb, _ptr(cnt), 4 * cnt.numel() if cnt is not None else 0, int(lanes))
     nsingle, ntile, nunits = plan.nsingle, plan.ntile, plan.nunits
     with torch.cuda.device(B.device):
@@ -97,11 +129,6 @@ def spmm(a, B, bias=None, epilogue=_lib.EPI_NONE, mask=None, scale=1.0, keep_pro
             rc = lib.gcnk_spmm_csr_f32(*args, _stream(B.device))
     _lib.check(rc, "gcnk_spmm_csr_f32")
     return out
-
-
-def _check_rng_base(t, device):
-    if t is not None and (t.dtype != torch.int64 or t.numel() < 1 or t.device != device):
-        raise RuntimeError("rng_base must be an int64 tensor of >= 1 element on the operand's device")
 
 
 # Overlap the two independent parts of a hybrid plan (gcnk_spmm_csr_f32_part)
@@ -148,7 +175,7 @@ def spmm_proj(a, B, W, bias=None, epilogue=_lib.EPI_NONE, mask=None, scale=1.0, 
     a = as_csr(a)
     B = _dense_f32(B, "dense operand")
     W = _dense_f32(W, "projection")
-    _check_rng_base(rng_base, B.device)
+    epi = Epilogue(epilogue, mask, scale, keep_prob, seed, offset, rng_base).on(B.device)
     M, K = a.shape
     F = B.shape[1]
     if B.shape[0] != K or W.shape[0] != F:
@@ -157,17 +184,12 @@ def spmm_proj(a, B, W, bias=None, epilogue=_lib.EPI_NONE, mask=None, scale=1.0, 
     lib = _lib.load()
     if not lanes:
         lanes = 64   # the projection needs a whole row in one lane group (one column tile)
-    if ipc is None:
-        ipc = default_ipc(a, F, lanes)
-    groups = int(lib.gcnk_spmm_groups(F, int(lanes)))
-    plan = a.plan(ipc, groups, DENSE_THRESHOLD)
+    plan = plan_for(a, F, lanes, ipc)
     H = torch.empty((M, F), dtype=torch.float32, device=B.device) if store_main else None
     if bias is not None:
         bias = bias.contiguous()
-    if mask is not None:
-        mask = mask.contiguous()
     wsb = plan.workspace_bytes(F)
-    ws = torch.empty((wsb + 3) // 4, dtype=torch.float32, device=B.device) if wsb > 0 else None
+    ws = workspace(wsb, B.device)
     cnt = plan.counters(B.device)
     C2 = torch.empty((M, P), dtype=torch.float32, device=B.device)
     with torch.cuda.device(B.device):
@@ -175,17 +197,40 @@ def spmm_proj(a, B, W, bias=None, epilogue=_lib.EPI_NONE, mask=None, scale=1.0, 
             _ptr(plan.buf), ctypes.cast(plan.hdr, ctypes.c_void_p),
             _ptr(B), B.stride(0), F,
             _ptr(H), F,
-            _ptr(bias), epilogue,
-            _ptr(mask), mask.stride(0) if mask is not None else 0, float(scale),
-            float(keep_prob), int(seed) & (2**64 - 1), int(offset) & (2**64 - 1), _ptr(rng_base),
+            _ptr(bias), *epi.c_args(),
             _ptr(W), W.stride(0), P, _ptr(C2), C2.stride(0),
             _ptr(ws), wsb, _ptr(cnt), 4 * cnt.numel() if cnt is not None else 0, int(lanes), _stream(B.device))
     if rc == _lib.EUNSUP:
-        H = spmm(a, B, bias=bias, epilogue=epilogue, mask=mask, scale=scale, keep_prob=keep_prob, seed=seed,
-                 offset=offset, ipc=ipc, lanes=lanes, rng_base=rng_base)
+        H = spmm(a, B, bias=bias, ipc=plan.ipc, lanes=lanes, **epi._asdict())
         return (H if store_main else None), gemm(H, W)
     _lib.check(rc, "gcnk_spmm_proj_f32")
     return H, C2
+
+
+# The two-layer forward's four schedules (include/gcnk.h GCNK_FWD_*) and the
+# range of gc1's fused kernels: rows of F floats as float4s in one column tile;
+# dense-AX and factored project onto <= FUSED_MAX_P classes, factored stages in LDS.
+FWD_FACTORED, FWD_SPMM_PROJ, FWD_SPMM_GEMM, FWD_DENSE_AX = 1, 2, 3, 4
+FUSED_MAX_F, FUSED_MAX_P, FACTOR_LDS_BUDGET = 256, 32, 160 * 1024
+
+
+def fused_range(F, P=0):
+    return F % 4 == 0 and F <= FUSED_MAX_F and P <= FUSED_MAX_P
+
+
+def forward_kind(F, P, dense_ax, factored, factor_lds_bytes, fuse, fuse_max_p, proj_ntile):
+    """The numeric part of choose_forward, in priority order.  ``dense_ax``,
+    ``factored``: the operands have a DenseAX / a HubFactor (its kernel stages
+    ``factor_lds_bytes``); ``fuse``, ``fuse_max_p``: the FUSE_* knobs; ``proj_ntile``: tile
+    chunks of the adjacency's lanes-64 plan (the fused projection takes no dense tile blocks)."""
+    if fused_range(F, P):
+        if dense_ax:
+            return FWD_DENSE_AX
+        if factored and factor_lds_bytes <= FACTOR_LDS_BUDGET:
+            return FWD_FACTORED
+    if fused_range(F) and fuse and P <= fuse_max_p and proj_ntile == 0:
+        return FWD_SPMM_PROJ
+    return FWD_SPMM_GEMM
 
 
 # gc1 through the hub factorisation (factor.py, csrc/factor.hip) when the
@@ -212,20 +257,17 @@ def hubfactor_gc1(f, W1, b1, W2, epilogue=_lib.EPI_BIAS_RELU, mask=None, scale=1
     (factor.HubFactor): S_T = X[hubs] W1 (layer.py:102), then one launch of
     gcnk_hubfactor_gc1_f32 -- H1 = drop(relu(A-hat X W1 + b1))
     (layer.py:106,110,182,185) and S2 = H1 W2 (layer.py:102, gc2).  Returns
-    None when the shapes are outside the kernel's range (the caller takes the
-    SpMM path).  ``S``: S_T already computed (timing probes)."""
+    None where the kernel refuses the shapes (GCNK_EUNSUP: the caller takes the
+    SpMM path).  ``S``: S_T already computed."""
     W1 = _dense_f32(W1, "gc1 weight")
     W2 = _dense_f32(W2, "gc2 weight")
-    _check_rng_base(rng_base, W1.device)
+    epi = Epilogue(epilogue, mask, scale, keep_prob, seed, offset, rng_base).on(W1.device)
     M, F, P = f.M, W1.shape[1], W2.shape[1]
     if W1.stride(0) != F:
         W1 = W1.contiguous()   # the kernel stages W1[k0:k0+Kc], S_T and W2 as flat copies
     if W2.stride(0) != P:
         W2 = W2.contiguous()
-    if W2.shape[0] != F or P > 32 or F % 4 or F > 256:
-        return None
-    lib = _lib.load()
-    if int(lib.gcnk_hubfactor_lds_bytes(F, f.Kc, f.H, f.rec_words, P)) > 160 * 1024:
+    if W2.shape[0] != F:
         return None
     if S is None:
         S = f.hub_times(W1, train=store_h1).contiguous()
@@ -233,14 +275,10 @@ def hubfactor_gc1(f, W1, b1, W2, epilogue=_lib.EPI_BIAS_RELU, mask=None, scale=1
     S2 = torch.empty((M, P), dtype=torch.float32, device=W1.device)
     if b1 is not None:
         b1 = b1.contiguous()
-    if mask is not None:
-        mask = mask.contiguous()
     with torch.cuda.device(W1.device):
-        rc = lib.gcnk_hubfactor_gc1_f32(
+        rc = _lib.load().gcnk_hubfactor_gc1_f32(
             M, F, f.Kc, f.H, P, _ptr(f.U), f.U.stride(0), _ptr(W1), W1.stride(0), f.k0, _ptr(S), S.stride(0),
-            _ptr(f.rec), f.rec_words, _ptr(b1), epilogue,
-            _ptr(mask), mask.stride(0) if mask is not None else 0, float(scale),
-            float(keep_prob), int(seed) & (2**64 - 1), int(offset) & (2**64 - 1), _ptr(rng_base),
+            _ptr(f.rec), f.rec_words, _ptr(b1), *epi.c_args(),
             _ptr(W2), W2.stride(0), _ptr(H1), F, _ptr(S2), P, _stream(W1.device))
     if rc == _lib.EUNSUP:
         return None
@@ -272,7 +310,7 @@ def dense_ax_for(adj, xop, F=None, P=None):
     M, K = xop.shape
     if adj.shape[0] != adj.shape[1] or adj.shape[1] != M or K > DENSE_AX_MAX_K or K == 0:
         return None
-    if (F is not None and (F > 256 or F % 4)) or (P is not None and P > 32):   # (csrc/dense_gc1.hip's range)
+    if not fused_range(F or 0, P or 0):   # (csrc/dense_gc1.hip's range)
         return None
     src = xop.dense
     key = (id(src), src.data_ptr(), src._version, adj.val.data_ptr(), adj.val._version)
@@ -309,7 +347,7 @@ def dense_gc1(d, W1, b1, W2, epilogue=_lib.EPI_BIAS_RELU, mask=None, scale=1.0, 
     module's contiguous operands): the caller then takes the SpMM path."""
     W1 = _dense_f32(W1, "gc1 weight")
     W2 = _dense_f32(W2, "gc2 weight")
-    _check_rng_base(rng_base, W1.device)
+    epi = Epilogue(epilogue, mask, scale, keep_prob, seed, offset, rng_base).on(W1.device)
     M, F, P = d.AX.shape[0], W1.shape[1], W2.shape[1]
     if W1.shape[0] != d.K or W2.shape[0] != F:
         raise RuntimeError(f"dense_gc1 shape mismatch: A-hat X [{M} x {d.K}], W1 {tuple(W1.shape)}, "
@@ -318,13 +356,9 @@ def dense_gc1(d, W1, b1, W2, epilogue=_lib.EPI_BIAS_RELU, mask=None, scale=1.0, 
     S2 = torch.empty((M, P), dtype=torch.float32, device=W1.device)
     if b1 is not None:
         b1 = b1.contiguous()
-    if mask is not None:
-        mask = mask.contiguous()
     with torch.cuda.device(W1.device):
         rc = _lib.load().gcnk_dense_gc1_f32(
-            M, d.K, F, P, _ptr(d.AX), d.AX.stride(0), _ptr(W1), W1.stride(0), _ptr(b1), epilogue,
-            _ptr(mask), mask.stride(0) if mask is not None else 0, float(scale),
-            float(keep_prob), int(seed) & (2**64 - 1), int(offset) & (2**64 - 1), _ptr(rng_base),
+            M, d.K, F, P, _ptr(d.AX), d.AX.stride(0), _ptr(W1), W1.stride(0), _ptr(b1), *epi.c_args(),
             _ptr(W2), W2.stride(0), _ptr(H1), F, _ptr(S2), P, _stream(W1.device))
     if rc == _lib.EUNSUP:
         return None
@@ -365,7 +399,7 @@ def gemm(A, B, transA=False, transB=False, bias=None, epilogue=_lib.GEMM_EPI_NON
         split_k = default_split_k(M, N, K, trans=transA or transB)
     lib = _lib.load()
     wsb = lib.gcnk_gemm_workspace_bytes(M, N, K, split_k)
-    ws = torch.empty((wsb + 3) // 4, dtype=torch.float32, device=A.device) if wsb > 0 else None
+    ws = workspace(wsb, A.device)
     if R is not None:
         R = _dense_f32(R, "R")
     with torch.cuda.device(A.device):
@@ -383,7 +417,7 @@ def colsum(X):
     M, N = X.shape
     lib = _lib.load()
     wsb = lib.gcnk_colsum_workspace_bytes(M, N)
-    ws = torch.empty(max((wsb + 3) // 4, 1), dtype=torch.float32, device=X.device)
+    ws = workspace(max(wsb, 4), X.device)
     out = torch.empty(N, dtype=torch.float32, device=X.device)
     with torch.cuda.device(X.device):
         rc = lib.gcnk_colsum_f32(_ptr(X), X.stride(0), M, N, _ptr(out), _ptr(ws), wsb, _stream(X.device))
@@ -547,15 +581,48 @@ class GraphConvFn(torch.autograd.Function):
 # profiles/r05_train_trace.json -- removed in ABI 12.)
 
 
+class ForwardPath(NamedTuple):
+    """What choose_forward decided: the schedule and the operands it runs on."""
+    kind: int                  # FWD_*
+    dax: Optional[DenseAX]     # FWD_DENSE_AX: the cached A-hat X (no first product, no F-wide plan)
+    fac: object                # FWD_FACTORED: the factor.HubFactor
+    x: object                  # the first product's left operand, CSR or dense: X, factored X[hubs]
+    plan_f: object             # the SpMM kinds: the adjacency's plan at width F ...
+    lanes: int                 # ... and the lanes it was planned for
+    plan_p: object             # the adjacency's plan at width P (gc2's A-hat S2, every kind)
+
+
+def choose_forward(adj, xop, F, P, train=False, exclude=()):
+    """The ForwardPath of the two-layer forward of (adj, X) at widths (F, P):
+    the one place that picks it -- record.ForwardRecord is filled from it and
+    GCNFn's per-op path dispatches on it.  ``train``: the backward keeps H1;
+    ``exclude``: kinds whose kernel has refused these operands."""
+    dax = dense_ax_for(adj, xop, F, P) if FWD_DENSE_AX not in exclude else None
+    fac = factor_for(adj, xop) if dax is None and FWD_FACTORED not in exclude else None
+    lds = int(_lib.load().gcnk_hubfactor_lds_bytes(F, fac.Kc, fac.H, fac.rec_words, P)) if fac is not None else 0
+    known = (F, P, dax is not None, fac is not None, lds, FUSE_PROJECTION and FWD_SPMM_PROJ not in exclude, FUSE_MAX_P)
+    kind, plan_f, lanes = forward_kind(*known, proj_ntile=0), None, 0
+    if kind == FWD_SPMM_PROJ:   # so far; now with the tile chunks of the plan it would run on
+        plan_f, lanes = plan_for(adj, F, 64), 64
+        kind = forward_kind(*known, proj_ntile=plan_f.ntile)
+    if kind == FWD_SPMM_GEMM:
+        plan_f, lanes = plan_for(adj, F, 0), 0
+    x = None if kind == FWD_DENSE_AX else xop.csr if xop.csr is not None else xop.dense
+    if kind == FWD_FACTORED:
+        x = fac.x_hub if fac.hub_operand(train) == "csr" else fac.x_hub_dense
+    return ForwardPath(kind, dax if kind == FWD_DENSE_AX else None, fac if kind == FWD_FACTORED else None,
+                       x, plan_f, lanes, plan_for(adj, P, 0))
+
+
 # The whole forward from one C call (record.py, gcnk_gcn_forward_f32) wherever
 # a record applies; GCNK_FORWARD_RECORD=0 issues it op by op (A/B timing).
 USE_RECORD = os.environ.get("GCNK_FORWARD_RECORD", "1") != "0"
 
 
-def record_forward(W1, b1, W2, b2, xop, adj, epi, mask, scale, keep, seed, offset, keep_h1, rng_base):
-    """(out, H1) of GCN.forward (reference layer.py:164-190) through the
-    cached launch record of (adj, X) -- or None where the forward is issued op
-    by op (no record applies, or records are off)."""
+def record_forward(W1, b1, W2, b2, xop, adj, epi, keep_h1):
+    """(out, H1, DenseAX or None) of GCN.forward (reference layer.py:164-190)
+    through the cached launch record of (adj, X) -- or None where it is issued
+    op by op (records off, or the record's kernel would refuse the weights)."""
     if not USE_RECORD:
         return None
     from . import record
@@ -566,26 +633,18 @@ def record_forward(W1, b1, W2, b2, xop, adj, epi, mask, scale, keep, seed, offse
                            f"W1 {tuple(W1.shape)}, W2 {tuple(W2.shape)}")
     if W1.dtype != torch.float32 or W2.dtype != torch.float32:
         raise RuntimeError("GCN weights must be float32 (the reference computes in fp32)")
-    if not W1.is_contiguous():
-        W1 = W1.contiguous()
-    if not W2.is_contiguous():
-        W2 = W2.contiguous()
-    if b1 is not None and not b1.is_contiguous():
-        b1 = b1.contiguous()
-    if b2 is not None and not b2.is_contiguous():
-        b2 = b2.contiguous()
-    if mask is not None and not mask.is_contiguous():
-        mask = mask.contiguous()
+    if not (W1.is_contiguous() and W2.is_contiguous() and (b1 is None or b1.is_contiguous())
+            and (b2 is None or b2.is_contiguous())):
+        W1, b1, W2, b2 = (t if t is None else t.contiguous() for t in (W1, b1, W2, b2))
     if dev.index != torch.cuda.current_device():
         with torch.cuda.device(dev):
-            return record_forward(W1, b1, W2, b2, xop, adj, epi, mask, scale, keep, seed, offset, keep_h1, rng_base)
+            return record_forward(W1, b1, W2, b2, xop, adj, epi, keep_h1)
     rec, stream = record.get(adj, xop, F, P, dev, train=bool(keep_h1))
-    if rec is None:
-        return None
-    if rec.kind == record.DENSE_AX and not all(t is None or t.data_ptr() % 16 == 0 for t in (W1, b1)):
+    if rec.kind == FWD_DENSE_AX and not all(t is None or t.data_ptr() % 16 == 0 for t in (W1, b1)):
         return None   # (gcnk_dense_gc1_f32 takes 16-B aligned W1 / b1 rows: the per-op path falls back)
-    return rec.run(W1, b1, W2, b2, epi, mask, float(scale), float(keep), int(seed), int(offset), rng_base,
-                   keep_h1, stream)
+    if epi.mask is not None and not epi.mask.is_contiguous():   # (GCN._dropout_args' values are checked ones otherwise)
+        epi = epi.on(dev)
+    return rec.run(W1, b1, W2, b2, epi, keep_h1, stream)
 
 
 def record_backward(ctx, g, W2, H1, need):
@@ -601,8 +660,29 @@ def record_backward(ctx, g, W2, H1, need):
     if dev.index != torch.cuda.current_device():
         with torch.cuda.device(dev):
             return record_backward(ctx, g, W2, H1, need)
-    rec, stream = record.get_backward(ctx.adj, ctx.xop, H1.shape[1], P, dev)
+    rec, stream = record.get_backward(ctx.adj, ctx.xop, H1.shape[1], P, dev, dax=ctx.dax)
     return rec.run(g, H1, W2, ctx.scale, need[0], ctx.has_b1 and need[1], need[2], ctx.has_b2 and need[3], stream)
+
+
+def _gc1_per_op(adj, xop, W1, b1, W2, epi, keep_h1, exclude=()):
+    """(H1, S2, DenseAX or None) op by op: the launches choose_forward's path
+    issues from one C call through its record."""
+    path = choose_forward(adj, xop, W1.shape[1], W2.shape[1], keep_h1, exclude)
+    kw = epi._asdict()
+    if path.kind == FWD_DENSE_AX:
+        res = dense_gc1(path.dax, W1, b1, W2, store_h1=keep_h1, **kw)
+    else:
+        S1 = spmm(path.x, W1) if isinstance(path.x, CSR) else gemm(path.x, W1)   # layer.py:102
+        if path.kind == FWD_FACTORED:
+            res = hubfactor_gc1(path.fac, W1, b1, W2, store_h1=keep_h1, S=S1, **kw)
+        elif path.kind == FWD_SPMM_PROJ:
+            res = spmm_proj(adj, S1, W2, bias=b1, store_main=keep_h1, lanes=path.lanes, **kw)
+        else:
+            H1 = spmm(adj, S1, bias=b1, lanes=path.lanes, **kw)
+            res = H1, gemm(H1, W2)
+    if res is None:   # the kernel refused these operands (dense-AX, factored): ask again without its kind
+        return _gc1_per_op(adj, xop, W1, b1, W2, epi, keep_h1, exclude + (path.kind,))
+    return res + (path.dax,)
 
 
 class GCNFn(torch.autograd.Function):
@@ -626,41 +706,14 @@ class GCNFn(torch.autograd.Function):
     """
 
     @staticmethod
-    def forward(ctx, W1, b1, W2, b2, xop, adj, epi, mask, scale, keep, seed, offset, keep_h1=True, rng_base=None):
-        res = record_forward(W1, b1, W2, b2, xop, adj, epi, mask, scale, keep, seed, offset, keep_h1, rng_base)
+    def forward(ctx, W1, b1, W2, b2, xop, adj, epi, keep_h1=True):
+        res = record_forward(W1, b1, W2, b2, xop, adj, epi, keep_h1)
         if res is not None:
-            out, H1 = res
-            ctx.xop, ctx.adj, ctx.scale = xop, adj, float(scale)
-            ctx.dax = ctx.fac = None
-            ctx.has_b1, ctx.has_b2 = b1 is not None, b2 is not None
-            ctx.save_for_backward(W2, H1)
-            return out
-        dax = dense_ax_for(adj, xop, W1.shape[1], W2.shape[1])
-        fac = factor_for(adj, xop) if dax is None else None
-        res = None
-        if dax is not None:
-            res = dense_gc1(dax, W1, b1, W2, epilogue=epi, mask=mask, scale=scale, keep_prob=keep, seed=seed,
-                            offset=offset, rng_base=rng_base, store_h1=keep_h1)
-        elif fac is not None:
-            res = hubfactor_gc1(fac, W1, b1, W2, epilogue=epi, mask=mask, scale=scale, keep_prob=keep, seed=seed,
-                                offset=offset, rng_base=rng_base, store_h1=keep_h1)
-        out = None
-        if res is not None:
-            H1, S2 = res
-        elif FUSE_PROJECTION and W2.shape[1] <= FUSE_MAX_P:
-            S1 = xop.times(W1)
-            H1, S2 = spmm_proj(adj, S1, W2, bias=b1, epilogue=epi, mask=mask, scale=scale, keep_prob=keep,
-                               seed=seed, offset=offset, store_main=keep_h1, rng_base=rng_base)
+            out, H1, ctx.dax = res
         else:
-            S1 = xop.times(W1)
-            H1 = spmm(adj, S1, bias=b1, epilogue=epi, mask=mask, scale=scale, keep_prob=keep, seed=seed,
-                      offset=offset, rng_base=rng_base)
-            S2 = gemm(H1, W2)
-        if out is None:
+            H1, S2, ctx.dax = _gc1_per_op(adj, xop, W1, b1, W2, epi, keep_h1)
             out = spmm(adj, S2, bias=b2, epilogue=_lib.EPI_BIAS if b2 is not None else _lib.EPI_NONE)
-        ctx.xop, ctx.adj, ctx.scale = xop, adj, float(scale)
-        ctx.dax = dax
-        ctx.fac = fac if (dax is None and res is not None) else None
+        ctx.xop, ctx.adj, ctx.scale = xop, adj, float(epi.scale)
         ctx.has_b1, ctx.has_b2 = b1 is not None, b2 is not None
         ctx.save_for_backward(W2, H1)
         return out
@@ -672,7 +725,7 @@ class GCNFn(torch.autograd.Function):
         need = ctx.needs_input_grad
         res = record_backward(ctx, g, W2, H1, need)
         if res is not None:
-            return res + (None,) * 10
+            return res + (None,) * 4
         gW1 = gb1 = gW2 = gb2 = None
         adjT = ctx.adj.t()
         gS2 = spmm(adjT, g)
@@ -695,6 +748,5 @@ class GCNFn(torch.autograd.Function):
             if ctx.dax is not None:   # Z1 = (A-hat X) W1  =>  gW1 = (A-hat X)^T gZ1
                 gW1 = gemm(ctx.dax.AX[:, :ctx.dax.K], gZ1, transA=True)
             else:
-                gS1 = spmm(adjT, gZ1)
-                gW1 = ctx.xop.t_times(gS1)
-        return gW1, gb1, gW2, gb2, None, None, None, None, None, None, None, None, None, None
+                gW1 = ctx.xop.t_times(spmm(adjT, gZ1))
+        return (gW1, gb1, gW2, gb2) + (None,) * 4

@@ -9,16 +9,22 @@ kernels (profiles/r03_eager_forward_host_profile.log).  A ForwardRecord holds,
 per (adjacency, features, widths, stream), every pointer that does not change
 between calls -- plans and their host headers, workspaces, counter regions,
 the factored operands and the intermediates S1 / S2 -- in a C struct, and one
-ctypes call issues the whole forward.  The launches, their arguments and their
-order are those of ops.GCNFn's per-op path, so results are bitwise the same.
+ctypes call issues the whole forward.
+
+Which schedule a forward runs (dense-AX, hub-factored, SpMM + projection or
+SpMM + GEMM), on which operands and plans, is decided in one place,
+ops.choose_forward: a ForwardRecord is filled from the ForwardPath it returns
+and ops.GCNFn's per-op path dispatches on the same value, so the launches,
+their arguments and their order agree and results are bitwise the same.
 """
 import ctypes
 import threading
+from collections import namedtuple
 
 import torch
 
 from . import _lib, factor, ops
-from .sparse import DENSE_THRESHOLD
+from .sparse import CSR
 
 _c = ctypes
 
@@ -52,7 +58,7 @@ class GcnBwd(_c.Structure):
                 ("bwd2_ws", _c.c_void_p), ("bwd2_ws_bytes", _c.c_int64)]
 
 
-FACTORED, SPMM_PROJ, SPMM_GEMM, DENSE_AX = 1, 2, 3, 4
+FACTORED, SPMM_PROJ, SPMM_GEMM, DENSE_AX = ops.FWD_FACTORED, ops.FWD_SPMM_PROJ, ops.FWD_SPMM_GEMM, ops.FWD_DENSE_AX
 KIND_NAMES = {FACTORED: "factored", SPMM_PROJ: "spmm+proj", SPMM_GEMM: "spmm+gemm", DENSE_AX: "dense-ax"}
 BWD_AX_DIRECT = 1
 
@@ -67,194 +73,132 @@ def layout_ok():
     return n == len(want) and list(buf)[:n] == want
 
 
+def _scratch(nbytes, device, keep):
+    """(pointer, bytes) of a workspace of `nbytes`, (None, 0) for none.  (A
+    record's launches take raw pointers: what they point into goes on `keep`.)"""
+    ws = ops.workspace(nbytes, device)
+    if ws is None:
+        return None, 0
+    keep.append(ws)
+    return ws.data_ptr(), nbytes
+
+
+def _matrix(rows, cols, device, keep):
+    """(pointer, leading dimension) of an fp32 [rows x cols] intermediate."""
+    t = torch.empty((rows, cols), dtype=torch.float32, device=device)
+    keep.append(t)
+    return t.data_ptr(), cols
+
+
+def _gemm_operand(s, x, M, N, K, trans, device, keep):
+    """Dense `x` as left operand of the record's [M x N x K] GEMM (ops.gemm's K-slabs)."""
+    s.x_dense, s.ldx = x.data_ptr(), x.stride(0)
+    s.x_split_k = ops.default_split_k(M, N, K, trans=trans)
+    keep.append(x)
+    s.gemm_ws, s.gemm_ws_bytes = _scratch(int(_lib.load().gcnk_gemm_workspace_bytes(M, N, K, s.x_split_k)),
+                                          device, keep)
+
+
 def _fill_plan(ref, plan, F, lanes, device, keep):
     """PlanRef for `plan` at width F: its header, a workspace and the counter
     region torch's current stream uses (Plan.counters)."""
     ref.plan = plan.buf.data_ptr()
     for i in range(16):
         ref.hdr[i] = plan.hdr[i]
-    wsb = plan.workspace_bytes(F)
-    if wsb > 0:
-        ws = torch.empty((wsb + 3) // 4, dtype=torch.float32, device=device)
-        keep.append(ws)
-        ref.workspace, ref.workspace_bytes = ws.data_ptr(), wsb
+    ref.workspace, ref.workspace_bytes = _scratch(plan.workspace_bytes(F), device, keep)
     cnt = plan.counters(device)
     if cnt is not None:
         keep.append(cnt)
         ref.counters, ref.counter_bytes = cnt.data_ptr(), 4 * cnt.numel()
     ref.lanes_hint = int(lanes)
+    keep.append(plan)
 
 
 class ForwardRecord:
-    """One filled gcnk_gcn_fwd plus the tensors and plans it points into."""
+    """One gcnk_gcn_fwd filled from ops.choose_forward's ForwardPath, plus the
+    tensors and plans it points into."""
 
-    __slots__ = ("s", "keep", "kind", "M", "F", "P", "src", "pinned", "__weakref__")
+    __slots__ = ("s", "keep", "kind", "dax", "M", "F", "P", "pinned", "__weakref__")
 
     def __init__(self, adj, xop, F, P, device, train=False):
-        lib = _lib.load()
+        p = ops.choose_forward(adj, xop, F, P, train)
         M = adj.shape[0]
         s = GcnFwd()
         keep = []
-        s.M, s.F, s.P = M, F, P
-        dax = ops.dense_ax_for(adj, xop, F, P)
-        fac = ops.factor_for(adj, xop) if dax is None else None
-        kind = None
-        if dax is not None:
+        s.kind, s.M, s.F, s.P = p.kind, M, F, P
+        if p.kind == DENSE_AX:
             # gc1 from the cached A-hat X: no first product, no F-wide plan
-            kind = DENSE_AX
-            s.Kc, s.U, s.ldu = dax.K, dax.AX.data_ptr(), dax.AX.stride(0)
-            keep.append(dax.AX)
-            s2 = torch.empty((M, P), dtype=torch.float32, device=device)
-            keep.append(s2)
-            s.s2, s.lds2 = s2.data_ptr(), P
-            aP = adj.plan(ops.default_ipc(adj, P, 0), int(lib.gcnk_spmm_groups(P, 0)), DENSE_THRESHOLD)
-            _fill_plan(s.aP, aP, P, 0, device, keep)
-            keep.append(aP)
-            s.kind = kind
-            self.s, self.keep, self.kind, self.M, self.F, self.P = s, keep, kind, M, F, P
-            self.src = (adj, xop.dense)
-            return
-        if fac is not None and P <= 32 and F % 4 == 0 and F <= 256 and \
-                int(lib.gcnk_hubfactor_lds_bytes(F, fac.Kc, fac.H, fac.rec_words, P)) <= 160 * 1024:
-            kind = FACTORED
+            s.Kc, s.U, s.ldu = p.dax.K, p.dax.AX.data_ptr(), p.dax.AX.stride(0)
+            keep.append(p.dax.AX)
+        elif p.kind == FACTORED:
+            fac = p.fac
             s.Kc, s.nhub, s.k0, s.rec_words = fac.Kc, fac.H, fac.k0, fac.rec_words
             s.U, s.ldu, s.rec = fac.U.data_ptr(), fac.U.stride(0), fac.rec.data_ptr()
             keep += [fac.U, fac.rec]
-            if fac.hub_operand(train) == "csr":
-                x_csr, x_dense = fac.x_hub, None
-            else:
-                x_csr, x_dense = None, fac.x_hub_dense
         else:
-            x_csr, x_dense = xop.csr, xop.dense
-            plan = None
-            if ops.FUSE_PROJECTION and P <= ops.FUSE_MAX_P and F % 4 == 0 and F <= 256:
-                lanes = 64
-                plan = adj.plan(ops.default_ipc(adj, F, lanes), int(lib.gcnk_spmm_groups(F, lanes)), DENSE_THRESHOLD)
-                # the fused projection runs on plans without dense tile blocks
-                kind = SPMM_PROJ if plan.ntile == 0 else None
-            if kind is None:
-                lanes = 0
-                plan = adj.plan(ops.default_ipc(adj, F, lanes), int(lib.gcnk_spmm_groups(F, lanes)), DENSE_THRESHOLD)
-                kind = SPMM_GEMM
             # H1 scratch for an eval forward: the unfused path's intermediate, and
             # the fused path's fallback where the library refuses the fusion (an
             # operand it cannot take as float4, gcnk_gcn_forward_f32)
-            h = torch.empty((M, F), dtype=torch.float32, device=device)
-            keep.append(h)
-            s.h1_tmp, s.ld_h1_tmp = h.data_ptr(), F
-            _fill_plan(s.aF, plan, F, lanes, device, keep)
-            keep.append(plan)
-        # the first product S1 = X W1 (factored: S_T = X_hubs W1)
-        if x_csr is not None:
-            rows, cols = x_csr.shape
-            xp = x_csr.plan(ops.default_ipc(x_csr, F, 0), int(lib.gcnk_spmm_groups(F, 0)), DENSE_THRESHOLD)
-            _fill_plan(s.x, xp, F, 0, device, keep)
-            keep.append(xp)
-        else:
-            rows, cols = x_dense.shape
-            s.x_dense, s.ldx = x_dense.data_ptr(), x_dense.stride(0)
-            keep.append(x_dense)
-            s.x_split_k = ops.default_split_k(rows, F, cols)
-        s.x_rows, s.x_cols = rows, cols
-        # GEMM workspace: split-K slabs of X W1 (dense X); H1 W2 runs unsplit
-        gws = 0
-        if x_dense is not None:
-            gws = int(lib.gcnk_gemm_workspace_bytes(rows, F, cols, s.x_split_k))
-        if gws > 0:
-            g = torch.empty((gws + 3) // 4, dtype=torch.float32, device=device)
-            keep.append(g)
-            s.gemm_ws, s.gemm_ws_bytes = g.data_ptr(), gws
-        s1 = torch.empty((rows, F), dtype=torch.float32, device=device)
-        s2 = torch.empty((M, P), dtype=torch.float32, device=device)
-        keep += [s1, s2]
-        s.s1, s.lds1, s.s2, s.lds2 = s1.data_ptr(), F, s2.data_ptr(), P
-        # gc2's aggregation A S2 + b2 (ops.spmm, lanes 0)
-        aP = adj.plan(ops.default_ipc(adj, P, 0), int(lib.gcnk_spmm_groups(P, 0)), DENSE_THRESHOLD)
-        _fill_plan(s.aP, aP, P, 0, device, keep)
-        keep.append(aP)
-        s.kind = kind
-        self.s, self.keep, self.kind, self.M, self.F, self.P = s, keep, kind, M, F, P
-        self.src = (adj, xop.csr if xop.csr is not None else xop.dense)
+            s.h1_tmp, s.ld_h1_tmp = _matrix(M, F, device, keep)
+            _fill_plan(s.aF, p.plan_f, F, p.lanes, device, keep)
+        if p.kind != DENSE_AX:
+            # the first product S1 = X W1 (factored: S_T = X_hubs W1); H1 W2 runs unsplit
+            rows, cols = s.x_rows, s.x_cols = p.x.shape
+            if isinstance(p.x, CSR):
+                _fill_plan(s.x, ops.plan_for(p.x, F), F, 0, device, keep)
+            else:
+                _gemm_operand(s, p.x, rows, F, cols, False, device, keep)
+            s.s1, s.lds1 = _matrix(rows, F, device, keep)
+        s.s2, s.lds2 = _matrix(M, P, device, keep)
+        _fill_plan(s.aP, p.plan_p, P, 0, device, keep)   # gc2's aggregation A S2 + b2 (ops.spmm, lanes 0)
+        self.s, self.keep, self.kind, self.dax, self.M, self.F, self.P = s, keep, p.kind, p.dax, M, F, P
 
-    def run(self, W1, b1, W2, b2, epi, mask, scale, keep_prob, seed, offset, rng_base, store_h1, stream):
-        """(out, H1) of one forward; H1 is None unless store_h1."""
+    def run(self, W1, b1, W2, b2, epi, store_h1, stream):
+        """(out, H1, self.dax) of one forward with ops.Epilogue `epi`; H1 is None unless store_h1."""
         dev = W1.device
         out = torch.empty((self.M, self.P), dtype=torch.float32, device=dev)
         H1 = torch.empty((self.M, self.F), dtype=torch.float32, device=dev) if store_h1 else None
         rc = _lib.load().gcnk_gcn_forward_f32(
             _c.byref(self.s), W1.data_ptr(), b1.data_ptr() if b1 is not None else None, W2.data_ptr(),
             b2.data_ptr() if b2 is not None else None, out.data_ptr(), self.P,
-            H1.data_ptr() if H1 is not None else None, self.F, epi,
-            mask.data_ptr() if mask is not None else None, mask.stride(0) if mask is not None else 0, scale,
-            keep_prob, seed & (2**64 - 1), offset & (2**64 - 1),
-            rng_base.data_ptr() if rng_base is not None else None, stream)
+            H1.data_ptr() if H1 is not None else None, self.F, *epi.c_args(), stream)
         _lib.check(rc, "gcnk_gcn_forward_f32")
-        return out, H1
+        return out, H1, self.dax
 
 
 class BackwardRecord:
     """One filled gcnk_gcn_bwd: ops.GCNFn.backward's launches (A-hat^T G, the
     fused gcn_bwd2, A-hat^T gZ1, X^T gS1) with their plans, workspaces and
-    scratch, issued by one ctypes call (bitwise the per-op backward)."""
+    scratch, issued by one ctypes call (bitwise the per-op backward).  `dax`:
+    the forward's DenseAX (GCNFn's ctx.dax): gW1 = (A-hat X)^T gZ1 directly."""
 
-    __slots__ = ("s", "keep", "M", "F", "P", "x_cols", "src", "pinned", "__weakref__")
+    __slots__ = ("s", "keep", "M", "F", "P", "x_cols", "pinned", "__weakref__")
 
-    def __init__(self, adj, xop, F, P, device):
-        lib = _lib.load()
+    def __init__(self, adj, xop, F, P, device, dax=None):
         M = adj.shape[0]
         s = GcnBwd()
         keep = []
         s.M, s.F, s.P = M, F, P
         adjT = adj.t()
         keep.append(adjT)
-        dax = ops.dense_ax_for(adj, xop, F, P)
         for ref, width in ((s.aTP, P), (s.aTF, F)) if dax is None else ((s.aTP, P),):
-            pl = adjT.plan(ops.default_ipc(adjT, width, 0), int(lib.gcnk_spmm_groups(width, 0)), DENSE_THRESHOLD)
-            _fill_plan(ref, pl, width, 0, device, keep)
-            keep.append(pl)
-        rows, cols = xop.shape
-        s.x_rows, s.x_cols = rows, cols
-        if dax is not None:        # gW1 = (A-hat X)^T gZ1 (the DENSE_AX forward's association)
+            _fill_plan(ref, ops.plan_for(adjT, width), width, 0, device, keep)
+        rows, cols = s.x_rows, s.x_cols = xop.shape
+        if dax is not None:
             s.flags = BWD_AX_DIRECT
-            s.x_dense, s.ldx = dax.AX.data_ptr(), dax.AX.stride(0)
             s.x_rows, s.x_cols = M, dax.K
-            s.x_split_k = ops.default_split_k(dax.K, F, M, trans=True)
-            keep.append(dax.AX)
-            gws = int(lib.gcnk_gemm_workspace_bytes(dax.K, F, M, s.x_split_k))
-            if gws > 0:
-                g = torch.empty((gws + 3) // 4, dtype=torch.float32, device=device)
-                keep.append(g)
-                s.gemm_ws, s.gemm_ws_bytes = g.data_ptr(), gws
-        elif xop.csr is not None:    # X^T gS1 = spmm(X^T, gS1)  (ops.XOperand.t_times)
+            _gemm_operand(s, dax.AX, dax.K, F, M, True, device, keep)
+        elif xop.csr is not None:    # X^T gS1 = spmm(X^T, gS1)  (ops.Operand.t_times)
             xT = xop.csr.t()
-            pl = xT.plan(ops.default_ipc(xT, F, 0), int(lib.gcnk_spmm_groups(F, 0)), DENSE_THRESHOLD)
-            _fill_plan(s.xT, pl, F, 0, device, keep)
-            keep += [xT, pl]
-        else:                      # gemm(X, gS1, transA=True)
-            x = xop.dense
-            s.x_dense, s.ldx = x.data_ptr(), x.stride(0)
-            s.x_split_k = ops.default_split_k(cols, F, rows, trans=True)
-            keep.append(x)
-            gws = int(lib.gcnk_gemm_workspace_bytes(cols, F, rows, s.x_split_k))
-            if gws > 0:
-                g = torch.empty((gws + 3) // 4, dtype=torch.float32, device=device)
-                keep.append(g)
-                s.gemm_ws, s.gemm_ws_bytes = g.data_ptr(), gws
-        gS2 = torch.empty((M, P), dtype=torch.float32, device=device)
-        gZ1 = torch.empty((M, F), dtype=torch.float32, device=device)
-        keep += [gS2, gZ1]
-        s.gS2, s.gZ1 = gS2.data_ptr(), gZ1.data_ptr()
+            keep.append(xT)
+            _fill_plan(s.xT, ops.plan_for(xT, F), F, 0, device, keep)
+        else:                        # gemm(X, gS1, transA=True)
+            _gemm_operand(s, xop.dense, cols, F, rows, True, device, keep)
+        s.gS2, s.gZ1 = _matrix(M, P, device, keep)[0], _matrix(M, F, device, keep)[0]
         if dax is None:
-            gS1 = torch.empty((rows, F), dtype=torch.float32, device=device)
-            keep.append(gS1)
-            s.gS1 = gS1.data_ptr()
-        wsb = int(lib.gcnk_gcn_bwd2_workspace_bytes(M, F, P))
-        if wsb > 0:
-            w = torch.empty((wsb + 3) // 4, dtype=torch.float32, device=device)
-            keep.append(w)
-            s.bwd2_ws, s.bwd2_ws_bytes = w.data_ptr(), wsb
+            s.gS1 = _matrix(rows, F, device, keep)[0]
+        s.bwd2_ws, s.bwd2_ws_bytes = _scratch(int(_lib.load().gcnk_gcn_bwd2_workspace_bytes(M, F, P)), device, keep)
         self.s, self.keep, self.M, self.F, self.P, self.x_cols = s, keep, M, F, P, cols
-        self.src = (adj, xop.csr if xop.csr is not None else xop.dense)
 
     def run(self, G, H1, W2, scale, want_gw1, want_gb1, want_gw2, want_gb2, stream):
         """(gW1, gb1, gW2, gb2), each None unless wanted."""
@@ -274,56 +218,63 @@ class BackwardRecord:
 _lock = threading.Lock()
 
 
-def get_backward(adj, xop, F, P, device):
+# adj._records maps what a record was built for (tag "fwd" / "bwd", X's id, widths, stream)
+# and the knobs it was built under (ops.FACTOR_GC1, ops.FUSE_PROJECTION, ops.DENSE_AX,
+# factor.XHUB_DENSE; variant: fwd, X[hubs] in its training form; bwd, gW1 from the
+# forward's A-hat X) to the record and the operand and versions it was built from.
+RecordKey = namedtuple("RecordKey", "tag src_id F P stream factor_gc1 fuse_projection dense_ax xhub_dense variant")
+Cached = namedtuple("Cached", "src versions rec")
+
+
+def get_backward(adj, xop, F, P, device, dax=None):
     """(record, stream): the BackwardRecord of (adj, X, F, P) for torch's
-    current stream, built on first use, and that stream."""
-    return _get(adj, xop, F, P, device, BackwardRecord, "bwd")
+    current stream, built on first use, and that stream.  ``dax``: the DenseAX
+    the forward ran on, if it did (GCNFn's ctx.dax)."""
+    return _get(adj, xop, F, P, device, BackwardRecord, "bwd", dax is not None, dax)
 
 
 def get(adj, xop, F, P, device, train=False):
     """(record, stream): the ForwardRecord of (adj, X, F, P) for torch's current
     stream, built on first use, and that stream.  ``train``: a forward whose H1
     the backward keeps (its X_hubs W1 may take another form, factor.hub_operand)."""
-    return _get(adj, xop, F, P, device, ForwardRecord, "fwd", train)
+    return _get(adj, xop, F, P, device, ForwardRecord, "fwd", bool(train) and factor.XHUB_TRAIN_TILE, train)
 
 
-def _get(adj, xop, F, P, device, cls, tag, train=False):
+def _get(adj, xop, F, P, device, cls, tag, variant, arg):
     """A record's launches bake in raw pointers to its scratch buffers, so a
     record is rebuilt when either operand's values change in place (the
     factored operands and plans are derived from them) and a record that was
     used while a hipGraph was being captured is never evicted: the graph keeps
     replaying into its buffers.  A record's scratch (S1, S2, H1) is shared by
-    every launch on its stream; a graph captured on that stream replays into
-    it, so two graphs of the same record must not replay concurrently."""
+    every launch on its stream; a graph captured on that stream replays into it, so two
+    graphs of the same record must not replay concurrently.  ``arg``: cls's last argument."""
     stream = torch.cuda.current_stream(device).cuda_stream
     src = xop.csr if xop.csr is not None else xop.dense
-    key = (tag, id(src), F, P, stream, ops.FACTOR_GC1, ops.FUSE_PROJECTION, ops.DENSE_AX, factor.XHUB_DENSE,
-           bool(train) and factor.XHUB_TRAIN_TILE)
+    # RecordKey's fields as a plain tuple: it finds the stored RecordKey (equal,
+    # same hash) without building one on every call
+    key = (tag, id(src), F, P, stream, ops.FACTOR_GC1, ops.FUSE_PROJECTION, ops.DENSE_AX, factor.XHUB_DENSE, variant)
     recs = getattr(adj, "_records", None)
     if recs is None:
-        with _lock:
-            recs = getattr(adj, "_records", None)
-            if recs is None:
-                recs = adj._records = {}
+        recs = adj.__dict__.setdefault("_records", {})   # (atomic: two threads get one dict)
     capturing = torch.cuda.is_current_stream_capturing()
     ver = (_version(src), _version(adj))
     hit = recs.get(key)
-    if hit is not None and hit[0] is src and ver == hit[1]:
+    if hit is not None and hit.src is src and ver == hit.versions:
         if capturing:
-            hit[2].pinned = True
-        return hit[2], stream
+            hit.rec.pinned = True
+        return hit.rec, stream
     with _lock:
-        rec = cls(adj, xop, F, P, device, train) if cls is ForwardRecord else cls(adj, xop, F, P, device)
+        rec = cls(adj, xop, F, P, device, arg)
         rec.pinned = capturing
         old = recs.get(key)
-        if old is not None and old[2].pinned:
-            _PINNED.append(old[2])   # replaced (operands changed) but still referenced by a graph
+        if old is not None and old.rec.pinned:
+            _PINNED.append(old.rec)   # replaced (operands changed) but still referenced by a graph
         while len(recs) >= 8:
-            victim = next((k for k, v in recs.items() if not v[2].pinned), None)
+            victim = next((k for k, v in recs.items() if not v.rec.pinned), None)
             if victim is None:
                 break
             recs.pop(victim)
-        recs[key] = (src, ver, rec)
+        recs[RecordKey(*key)] = Cached(src, ver, rec)
         return rec, stream
 
 

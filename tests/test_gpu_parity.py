@@ -842,8 +842,8 @@ def test_gcn_20ng_shaped_forward_matches_oracle(mode, monkeypatch):
             with torch.no_grad():
                 got = m(X, A)
             outs[name] = (got.cpu().numpy(), {})
-            kinds = {r[2].kind for k, r in as_csr(A)._records.items()
-                     if isinstance(r[2], record.ForwardRecord) and k[5] == ops.FACTOR_GC1 and k[7] == ops.DENSE_AX}
+            kinds = {c.rec.kind for k, c in as_csr(A)._records.items()
+                     if k.tag == "fwd" and k.factor_gc1 == ops.FACTOR_GC1 and k.dense_ax == ops.DENSE_AX}
             assert kind in kinds, (name, kinds)
             if want is None:
                 ref = gcn_ref.RefGCN(nfeat=g["nfeat"], nhid=200, nclass=20, dropout=0.5).eval()
@@ -1452,7 +1452,7 @@ def test_dense_ax_forward_backward_matches_spmm_path(r8, mode, graph, monkeypatc
         torch.manual_seed(9)
         lg = m(X, A)
         if dax:
-            kinds = {r[2].kind for r in as_csr(A)._records.values() if isinstance(r[2], record.ForwardRecord)}
+            kinds = {c.rec.kind for k, c in as_csr(A)._records.items() if k.tag == "fwd"}
             assert record.DENSE_AX in kinds, kinds
         if mode == "eval":
             assert torch.equal(lg, m(X, A))
@@ -1548,6 +1548,41 @@ def test_forward_record_is_bitwise_the_per_op_path(r8, path, mode, monkeypatch):
             "spmm_gemm": record.SPMM_GEMM, "dense_ax": record.DENSE_AX}.get(path)
     if want is not None:
         assert want in kinds, kinds
+
+
+def test_forward_record_is_bitwise_the_per_op_path_on_dense_tile_blocks(monkeypatch):
+    """An adjacency whose lanes-64 plan has dense tile blocks, at widths where the
+    fused projection would otherwise apply (F = 64, P = 4): the record takes
+    SpMM + GEMM on the lanes-0 plan (the fused projection runs on no tile
+    blocks), and the per-op path, choosing through the same ops.choose_forward,
+    issues the same launches -- eval logits, train-mode logits (device dropout)
+    and every gradient bitwise equal.  (R8's adjacency has no tile blocks.)"""
+    from graph_convolutional_networks_for_text_classification_amd import ops, record
+    monkeypatch.setattr(ops, "DENSE_AX", False)
+    monkeypatch.setattr(ops, "FACTOR_GC1", False)
+    monkeypatch.setattr(ops, "FUSE_PROJECTION", True)
+    monkeypatch.setattr(ops, "FUSE_MAX_P", 8)
+    rng = np.random.default_rng(900)
+    rp, ci, v = _mixed_density_csr(rng, 900, 900)
+    adj = from_arrays(rp, ci, v, (900, 900), DEV)
+    X = torch.from_numpy(rng.standard_normal((900, 40)).astype(np.float32)).to(DEV)
+    assert ops.plan_for(adj, 64, 64).ntile > 0
+    outs = {}
+    for use in (True, False):
+        monkeypatch.setattr(ops, "USE_RECORD", use)
+        torch.manual_seed(77)
+        m = GCN(nfeat=40, nhid=64, nclass=4, dropout=0.5, dropout_rng="device").to(DEV)
+        m.eval()
+        with torch.no_grad():
+            ev = m(X, adj)
+        m.train()
+        lg = m(X, adj)
+        lg.square().sum().backward()
+        outs[use] = {"eval": ev.cpu(), "train": lg.detach().cpu(), **{k: p.grad.cpu() for k, p in m.named_parameters()}}
+    assert record.get(adj, ops.Operand(X), 64, 4, DEV)[0].kind == record.SPMM_GEMM
+    assert len(outs[True]) == 6 and not torch.equal(outs[True]["eval"], outs[True]["train"])
+    for k in outs[True]:
+        assert torch.equal(outs[True][k], outs[False][k]), k
 
 
 def test_forward_record_follows_in_place_feature_updates(r8):

@@ -484,7 +484,7 @@ def test_gcn_wires_seed_base_and_advance(wiring, path, monkeypatch):
             assert int(m._rng_base.item()) == (t + 1) * M * NHID
             want = wiring["Ad"] @ (ref["Z1b"] @ ref["W2"]) + ref["b2"]
             assert np.abs(ev - want).max() <= 1e-5 * max(1.0, float(np.abs(want).max()))
-    recs = [r[2] for r in getattr(as_csr(A), "_records", {}).values()]
+    recs = [c.rec for c in getattr(as_csr(A), "_records", {}).values()]
     kinds = {r.kind for r in recs if isinstance(r, record.ForwardRecord)}
     assert any(isinstance(r, record.BackwardRecord) for r in recs)
     want_kind = {"factored": record.FACTORED, "dense_factored": record.FACTORED, "spmm_proj": record.SPMM_PROJ,
