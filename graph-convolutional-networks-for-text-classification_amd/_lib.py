@@ -31,7 +31,7 @@ def _resolve_lib():
 
 
 LIB_PATH = _resolve_lib()
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 # C-ABI return codes (gcnk.h)
 OK, EARG, EUNSUP, EHIP = 0, -1, -2, -3
@@ -40,6 +40,10 @@ OK, EARG, EUNSUP, EHIP = 0, -1, -2, -3
 EPI_NONE, EPI_BIAS, EPI_BIAS_RELU, EPI_BIAS_RELU_DROP, EPI_BIAS_RELU_HASH = 0, 1, 2, 3, 4
 # GEMM epilogues (gcnk.h GCNK_GEMM_EPI_*)
 GEMM_EPI_NONE, GEMM_EPI_BIAS, GEMM_EPI_BIAS_RELU, GEMM_EPI_MASK_POS = 0, 1, 2, 5
+# gcnk_gemm_route's families and flags (gcnk.h GCNK_GEMM_ROUTE_*)
+(GEMM_ROUTE_NARROW, GEMM_ROUTE_SKINNY, GEMM_ROUTE_SHORTK, GEMM_ROUTE_SMALLM, GEMM_ROUTE_TILED_N16,
+ GEMM_ROUTE_TILED) = 1, 2, 3, 4, 5, 6
+GEMM_ROUTE_SPLIT, GEMM_ROUTE_PTR_FETCH = 1, 2
 
 _vp, _i32, _i64, _u64, _f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float
 
@@ -101,6 +105,8 @@ SIGNATURES = {
         _vp, _i32, _vp, _i64, _f32,     # bias, epilogue, R, ldr, scale
         _i32, _vp, _i64, _vp,           # split_k, workspace, workspace_bytes, stream
     ]),
+    # transA, transB, M, N, K, lda, ldb, a_aligned16, b_aligned16, split_k, out4
+    "gcnk_gemm_route": (ctypes.c_int, [_i32, _i32, _i32, _i32, _i32, _i64, _i64, _i32, _i32, _i32, _vp]),
     "gcnk_colsum_workspace_bytes": (_i64, [_i32, _i32]),
     "gcnk_colsum_f32": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _i64, _vp]),
     "gcnk_gcn_bwd2_workspace_bytes": (_i64, [_i32, _i32, _i32]),

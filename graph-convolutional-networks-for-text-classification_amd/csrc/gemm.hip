@@ -43,6 +43,9 @@ __device__ __forceinline__ float gemm_epi(const GemmEpi& e, float acc, int64_t m
 }
 
 constexpr int BK = 16;
+// An operand of the tiled kernel is read through a buffer resource while its span in bytes stays below this
+// (32-bit offsets); the kernel's use_buf and the host's tiled_ptr_fetch (the route's flag) both test against it.
+constexpr int64_t kBufSpanLimit = 0x7ff00000;
 
 template <int WM, int WN, int FM, int FN, bool TA, bool TB>
 __global__ void __launch_bounds__(256)
@@ -80,7 +83,7 @@ gemm_f32_mfma_kernel(int32_t M, int32_t N, int32_t K, int32_t kchunk, const floa
   // loads compiled into a branch with its own vmcnt(0): the double buffer's
   // next tile arrived one load at a time)
   const int64_t a_bytes = (TA ? (int64_t)K : (int64_t)M) * lda * 4, b_bytes = (TB ? (int64_t)N : (int64_t)K) * ldb * 4;
-  const bool use_buf = a_bytes < 0x7ff00000 && b_bytes < 0x7ff00000;   // (uniform)
+  const bool use_buf = a_bytes < kBufSpanLimit && b_bytes < kBufSpanLimit;   // (uniform)
   const __amdgpu_buffer_rsrc_t rsa =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(A), (short)0, use_buf ? (int)a_bytes : 0, 0x00020000);
   const __amdgpu_buffer_rsrc_t rsb =
@@ -539,15 +542,23 @@ __global__ void gemm_splitk_reduce_kernel(int32_t M, int32_t N, int32_t S, const
   C[m * ldc + n] = gemm_epi(epi, acc, m, n);
 }
 
+// The tiled kernel's K slabs for `split` requested ones: whole BK-deep k tiles
+// per slab, so fewer slabs than asked for where K is short.
+inline int32_t tiled_slabs(int32_t K, int32_t split, int32_t* kchunk_out) {
+  int32_t kchunk = (K + split - 1) / split;
+  kchunk = (kchunk + BK - 1) / BK * BK;
+  if (kchunk <= 0) kchunk = BK;
+  *kchunk_out = kchunk;
+  return (K + kchunk - 1) / kchunk > 0 ? (K + kchunk - 1) / kchunk : 1;
+}
+
 template <int WM, int WN, int FM, int FN>
 int launch_gemm(bool ta, bool tb, int32_t M, int32_t N, int32_t K, const float* A, int64_t lda,
                 const float* B, int64_t ldb, float* C, int64_t ldc, const GemmEpi& e, int32_t split,
                 float* ws, hipStream_t s) {
   constexpr int BM = WM * FM * 16, BN = WN * FN * 16;
-  int32_t kchunk = (K + split - 1) / split;
-  kchunk = (kchunk + BK - 1) / BK * BK;
-  if (kchunk <= 0) kchunk = BK;
-  const int32_t nsplit = (K + kchunk - 1) / kchunk > 0 ? (K + kchunk - 1) / kchunk : 1;
+  int32_t kchunk;
+  const int32_t nsplit = tiled_slabs(K, split, &kchunk);
   dim3 grid((unsigned)((M + BM - 1) / BM), (unsigned)((N + BN - 1) / BN), (unsigned)nsplit);
   float* slab = nsplit > 1 ? ws : nullptr;
 #define GCNK_GEMM_LAUNCH(TA_, TB_)                                                                      \
@@ -604,6 +615,81 @@ __global__ void colsum_pass2_kernel(const float* __restrict__ part, int32_t nblk
   out[n] = acc;
 }
 
+// ---------------------------------------------------------------------------
+// The dispatch.  gemm_route decides, from the arguments alone, which kernel
+// gcnk_gemm_f32 launches; gcnk_gemm_f32 switches on its result and
+// gcnk_gemm_route (include/gcnk.h) reports it to tests.
+//
+// Every instantiation the library compiles -- tests/gemm_cases.py holds the
+// same list (INSTANTIATIONS) and a case for each entry, so a kernel added
+// here needs an entry there and a case that reaches it:
+//
+//   NARROW     gemm_shortk_kernel<KCH, 2>          KCH in {13, 16}
+//   SKINNY     gemm_skinny_ksplit_kernel<KB, NT>   KB in {1, 2, 4, 8, 16} x NT in {1, 2, 4}
+//   SHORTK     gemm_shortk_kernel<KCH, 3>          KCH in 1 .. 8
+//   SMALLM     gemm_smallm_wk_kernel<2, 2> + gemm_slab_reduce4_kernel (always split)
+//   TILED_N16  gemm_f32_mfma_kernel<4, 1, 2, 1, TA, TB>   the four transposes,
+//   TILED      gemm_f32_mfma_kernel<2, 2, 2, 2, TA, TB>   each whole or split
+//              (+ gemm_splitk_reduce_kernel), through buffer or pointer loads
+#ifndef GCNK_WK_KBW   // small-M kernel: 16-deep k blocks per wave (a slab is 8 waves of them)
+#define GCNK_WK_KBW 2
+#endif
+#ifndef GCNK_WK_NTG   // small-M kernel: 16-column n-tiles per workgroup
+#define GCNK_WK_NTG 2
+#endif
+
+struct GemmRoute {
+  int32_t family, p0, p1, flags;   // GCNK_GEMM_ROUTE_* (include/gcnk.h)
+};
+
+// the small-M kernel's slabs: 8 waves x 16 KBW k each
+inline int64_t smallm_slabs(int32_t K) { return ((int64_t)K + 8 * 16 * GCNK_WK_KBW - 1) / (8 * 16 * GCNK_WK_KBW); }
+
+// the tiled kernel's use_buf (computed again on the device), negated: an
+// operand spans more than the 32-bit offsets of a buffer resource
+inline bool tiled_ptr_fetch(bool ta, bool tb, int32_t M, int32_t N, int32_t K, int64_t lda, int64_t ldb) {
+  const int64_t a_bytes = (ta ? (int64_t)K : (int64_t)M) * lda * 4, b_bytes = (tb ? (int64_t)N : (int64_t)K) * ldb * 4;
+  return !(a_bytes < kBufSpanLimit && b_bytes < kBufSpanLimit);
+}
+
+inline GemmRoute gemm_route(bool ta, bool tb, int32_t M, int32_t N, int32_t K, int64_t lda, int64_t ldb, bool a16,
+                            bool b16, int32_t split_k) {
+  if (split_k < 1) split_k = 1;
+  const bool nn = !ta && !tb;
+  // gc2's support H1 W2 at many rows ([nodes x 200] x [200 x classes]):
+  // 64-row workgroups, each wave one whole K chain per output (no cross-wave
+  // sum), W2's slice staged in LDS once per workgroup.  Against the skinny
+  // K-split kernel (profiles/r04_narrow.log): [18846 x 200] x [200 x 20] 8.9 ->
+  // 8.2 us, but [4000 x ..] 4.6 -> 5.5 and [7724 x 200] x [200 x 8] 3.5 -> 4.2:
+  // only past 16k rows and 16 columns
+  if (nn && M >= 16384 && N > 16 && N <= 32 && N % 4 == 0 && K > 128 && K <= 256 && K % 4 == 0 && lda % 4 == 0 &&
+      ldb % 4 == 0 && a16 && b16 && split_k == 1)
+    return {GCNK_GEMM_ROUTE_NARROW, K <= 208 ? 13 : 16, 2, 0};   // N in (16, 32]: two n-tiles
+  // 16 rows per workgroup, K split over its 4 waves (k blocks of 16 per wave),
+  // every column tile of N from the same A registers
+  if (nn && N <= 64 && K <= 1024 && lda % 4 == 0 && a16 && split_k == 1) {
+    const int kbw = ((K + 15) / 16 + 3) / 4;
+    const int nt = (N + 15) / 16;
+    return {GCNK_GEMM_ROUTE_SKINNY, kbw <= 1 ? 1 : kbw <= 2 ? 2 : kbw <= 4 ? 4 : kbw <= 8 ? 8 : 16,
+            nt == 1 ? 1 : nt == 2 ? 2 : 4, 0};
+  }
+  if (nn && K > 0 && K <= 128 && K % 4 == 0 && N > 64 && N % 4 == 0 && lda % 4 == 0 && ldb % 4 == 0 && a16 && b16 &&
+      split_k == 1) {
+    const int kch = (K + 15) / 16;
+    return {GCNK_GEMM_ROUTE_SHORTK, kch < 8 ? kch : 8, kShortkNT, 0};
+  }
+  // small M, long K: the in-workgroup K split (gemm_smallm_wk_kernel), slabs of
+  // 8 waves x 16 KBW k, summed by gemm_slab_reduce4_kernel
+  const int64_t wk_S = smallm_slabs(K);
+  if (nn && M <= 64 && K >= 512 && N % 4 == 0 && lda % 4 == 0 && a16 && split_k > 1 && wk_S <= split_k &&
+      wk_S <= 65535 && (int64_t)M * lda * 4 < INT32_MAX && ((int64_t)K + 16) * ldb * 4 < INT32_MAX)   // (its buffer offsets)
+    return {GCNK_GEMM_ROUTE_SMALLM, GCNK_WK_KBW, GCNK_WK_NTG, GCNK_GEMM_ROUTE_SPLIT};
+  int32_t kchunk;
+  const int32_t flags = (tiled_slabs(K, split_k, &kchunk) > 1 ? GCNK_GEMM_ROUTE_SPLIT : 0) |
+                        (tiled_ptr_fetch(ta, tb, M, N, K, lda, ldb) ? GCNK_GEMM_ROUTE_PTR_FETCH : 0);
+  return {N <= 16 ? GCNK_GEMM_ROUTE_TILED_N16 : GCNK_GEMM_ROUTE_TILED, ta ? 1 : 0, tb ? 1 : 0, flags};
+}
+
 }  // namespace
 }  // namespace gcnk
 
@@ -651,90 +737,87 @@ extern "C" int gcnk_gemm_f32(int32_t transA, int32_t transB, int32_t M, int32_t 
   GemmEpi e{bias, R, ldr, scale, epilogue};
   hipStream_t s = (hipStream_t)stream;
   const bool ta = transA != 0, tb = transB != 0;
-  if (!ta && !tb && M >= 16384 && N > 16 && N <= 32 && N % 4 == 0 && K > 128 &&
-      K <= 256 && K % 4 == 0 && lda % 4 == 0 && ldb % 4 == 0 && aligned16(A) && aligned16(B) && split_k == 1) {
-    // gc2's support H1 W2 at many rows ([nodes x 200] x [200 x classes]):
-    // 64-row workgroups, each wave one whole K chain per output (no cross-wave
-    // sum), W2's slice staged in LDS once per workgroup.  Against the skinny
-    // K-split kernel (profiles/r04_narrow.log): [18846 x 200] x [200 x 20] 8.9 ->
-    // 8.2 us, but [4000 x ..] 4.6 -> 5.5 and [7724 x 200] x [200 x 8] 3.5 -> 4.2:
-    // only past 16k rows and 16 columns
-    const int64_t nrb8 = ((int64_t)M + 64 * 8 - 1) / (64 * 8);
-    const dim3 grid((unsigned)(nrb8 * 8));
+  const GemmRoute rt = gemm_route(ta, tb, M, N, K, lda, ldb, aligned16(A), aligned16(B), split_k);
+  switch (rt.family) {
+    case GCNK_GEMM_ROUTE_NARROW: {
+      const int64_t nrb8 = ((int64_t)M + 64 * 8 - 1) / (64 * 8);
+      const dim3 grid((unsigned)(nrb8 * 8));
 #define GCNK_NARROW(KCH_, NT_) \
   hipLaunchKernelGGL((gemm_shortk_kernel<KCH_, NT_>), grid, dim3(256), 0, s, M, N, K, A, lda, B, ldb, C, ldc, e)
-    if (K <= 208)  // N in (16, 32]: two n-tiles
-      GCNK_NARROW(13, 2);
-    else GCNK_NARROW(16, 2);
+      if (rt.p0 == 13) GCNK_NARROW(13, 2);
+      else GCNK_NARROW(16, 2);
 #undef GCNK_NARROW
-    return launch_check("gemm_shortk_kernel");
-  }
-  if (!ta && !tb && N <= 64 && K <= 1024 && lda % 4 == 0 && aligned16(A) && split_k == 1) {
-    // 16 rows per workgroup, K split over its 4 waves (k blocks of 16 per wave),
-    // every column tile of N from the same A registers
-    const int kbw = ((K + 15) / 16 + 3) / 4;
-    const int nt = (N + 15) / 16;
-    const unsigned blocks = (unsigned)(((int64_t)M + 15) / 16);
+      return launch_check("gemm_shortk_kernel");
+    }
+    case GCNK_GEMM_ROUTE_SKINNY: {
+      const unsigned blocks = (unsigned)(((int64_t)M + 15) / 16);
 #define GCNK_SKINNY_KS(KB_, NT_)                                                                              \
   hipLaunchKernelGGL((gemm_skinny_ksplit_kernel<KB_, NT_>), dim3(blocks), dim3(256), 0, s, M, N, K, A, lda, B, \
                      ldb, C, ldc, e)
-#define GCNK_SKINNY_NT(NT_)              \
-  if (kbw <= 1) GCNK_SKINNY_KS(1, NT_);  \
-  else if (kbw <= 2) GCNK_SKINNY_KS(2, NT_); \
-  else if (kbw <= 4) GCNK_SKINNY_KS(4, NT_); \
-  else if (kbw <= 8) GCNK_SKINNY_KS(8, NT_); \
+#define GCNK_SKINNY_NT(NT_)                      \
+  if (rt.p0 == 1) GCNK_SKINNY_KS(1, NT_);        \
+  else if (rt.p0 == 2) GCNK_SKINNY_KS(2, NT_);   \
+  else if (rt.p0 == 4) GCNK_SKINNY_KS(4, NT_);   \
+  else if (rt.p0 == 8) GCNK_SKINNY_KS(8, NT_);   \
   else GCNK_SKINNY_KS(16, NT_);
-    if (nt == 1) { GCNK_SKINNY_NT(1) }
-    else if (nt == 2) { GCNK_SKINNY_NT(2) }
-    else { GCNK_SKINNY_NT(4) }
+      if (rt.p1 == 1) { GCNK_SKINNY_NT(1) }
+      else if (rt.p1 == 2) { GCNK_SKINNY_NT(2) }
+      else { GCNK_SKINNY_NT(4) }
 #undef GCNK_SKINNY_NT
 #undef GCNK_SKINNY_KS
-    return launch_check("gemm_skinny_ksplit_kernel");
-  }
-  if (!ta && !tb && K > 0 && K <= 128 && K % 4 == 0 && N > 64 && N % 4 == 0 && lda % 4 == 0 &&
-      ldb % 4 == 0 && aligned16(A) && aligned16(B) && split_k == 1) {
-    const int64_t nrb8 = ((int64_t)M + 64 * 8 - 1) / (64 * 8);  // groups of 8 row blocks
-    const dim3 grid((unsigned)(nrb8 * 8 * ((N + 16 * kShortkNT - 1) / (16 * kShortkNT))));
-    const int kch = (K + 15) / 16;
+      return launch_check("gemm_skinny_ksplit_kernel");
+    }
+    case GCNK_GEMM_ROUTE_SHORTK: {
+      const int64_t nrb8 = ((int64_t)M + 64 * 8 - 1) / (64 * 8);  // groups of 8 row blocks
+      const dim3 grid((unsigned)(nrb8 * 8 * ((N + 16 * kShortkNT - 1) / (16 * kShortkNT))));
 #define GCNK_SHORTK(KCH_) \
   hipLaunchKernelGGL((gemm_shortk_kernel<KCH_>), grid, dim3(256), 0, s, M, N, K, A, lda, B, ldb, C, ldc, e)
-    switch (kch) {
-      case 1: GCNK_SHORTK(1); break;
-      case 2: GCNK_SHORTK(2); break;
-      case 3: GCNK_SHORTK(3); break;
-      case 4: GCNK_SHORTK(4); break;
-      case 5: GCNK_SHORTK(5); break;
-      case 6: GCNK_SHORTK(6); break;
-      case 7: GCNK_SHORTK(7); break;
-      default: GCNK_SHORTK(8); break;
-    }
+      switch (rt.p0) {
+        case 1: GCNK_SHORTK(1); break;
+        case 2: GCNK_SHORTK(2); break;
+        case 3: GCNK_SHORTK(3); break;
+        case 4: GCNK_SHORTK(4); break;
+        case 5: GCNK_SHORTK(5); break;
+        case 6: GCNK_SHORTK(6); break;
+        case 7: GCNK_SHORTK(7); break;
+        default: GCNK_SHORTK(8); break;
+      }
 #undef GCNK_SHORTK
-    return launch_check("gemm_shortk_kernel");
+      return launch_check("gemm_shortk_kernel");
+    }
+    case GCNK_GEMM_ROUTE_SMALLM: {
+      const int64_t wk_S = smallm_slabs(K);
+      const dim3 grid((unsigned)wk_S, (unsigned)((N + 16 * GCNK_WK_NTG - 1) / (16 * GCNK_WK_NTG)));
+      hipLaunchKernelGGL((gemm_smallm_wk_kernel<GCNK_WK_KBW, GCNK_WK_NTG>), grid, dim3(512), 0, s, M, N, K, A, lda,
+                         B, ldb, workspace);
+      int rc = launch_check("gemm_smallm_wk_kernel");
+      if (rc) return rc;
+      const int64_t total4 = (int64_t)M * N / 4;
+      hipLaunchKernelGGL(gemm_slab_reduce4_kernel, dim3((unsigned)((total4 + kRedItems - 1) / kRedItems)),
+                         dim3(kRedItems * kRedGroups), 0, s, M, N, (int32_t)wk_S, workspace, C, ldc, e);
+      return launch_check("gemm_slab_reduce4_kernel");
+    }
+    case GCNK_GEMM_ROUTE_TILED_N16:
+      return launch_gemm<4, 1, 2, 1>(ta, tb, M, N, K, A, lda, B, ldb, C, ldc, e, split_k, workspace, s);
+    default:
+      return launch_gemm<2, 2, 2, 2>(ta, tb, M, N, K, A, lda, B, ldb, C, ldc, e, split_k, workspace, s);
   }
-#ifndef GCNK_WK_KBW   // 16-deep k blocks per wave (a slab is 8 waves of them)
-#define GCNK_WK_KBW 2
-#endif
-#ifndef GCNK_WK_NTG   // 16-column n-tiles per workgroup
-#define GCNK_WK_NTG 2
-#endif
-  // small M, long K: the in-workgroup K split (gemm_smallm_wk_kernel), slabs of
-  // 8 waves x 16 KBW k, summed by gemm_slab_reduce4_kernel
-  const int64_t wk_S = ((int64_t)K + 8 * 16 * GCNK_WK_KBW - 1) / (8 * 16 * GCNK_WK_KBW);
-  if (!ta && !tb && M <= 64 && K >= 512 && N % 4 == 0 && lda % 4 == 0 && aligned16(A) &&
-      split_k > 1 && wk_S <= split_k && wk_S <= 65535 &&
-      (int64_t)M * lda * 4 < INT32_MAX && ((int64_t)K + 16) * ldb * 4 < INT32_MAX) {   // (its buffer offsets)
-    const dim3 grid((unsigned)wk_S, (unsigned)((N + 16 * GCNK_WK_NTG - 1) / (16 * GCNK_WK_NTG)));
-    hipLaunchKernelGGL((gemm_smallm_wk_kernel<GCNK_WK_KBW, GCNK_WK_NTG>), grid, dim3(512), 0, s, M, N, K, A, lda, B,
-                       ldb, workspace);
-    int rc = launch_check("gemm_smallm_wk_kernel");
-    if (rc) return rc;
-    const int64_t total4 = (int64_t)M * N / 4;
-    hipLaunchKernelGGL(gemm_slab_reduce4_kernel, dim3((unsigned)((total4 + kRedItems - 1) / kRedItems)),
-                       dim3(kRedItems * kRedGroups), 0, s, M, N, (int32_t)wk_S, workspace, C, ldc, e);
-    return launch_check("gemm_slab_reduce4_kernel");
+}
+
+extern "C" int gcnk_gemm_route(int32_t transA, int32_t transB, int32_t M, int32_t N, int32_t K, int64_t lda,
+                               int64_t ldb, int32_t a_aligned16, int32_t b_aligned16, int32_t split_k,
+                               int32_t* out4) {
+  if (!out4 || M <= 0 || N <= 0 || K < 0) {
+    set_error("gcnk_gemm_route: null out4 or bad sizes");
+    return GCNK_EARG;
   }
-  if (N <= 16) return launch_gemm<4, 1, 2, 1>(ta, tb, M, N, K, A, lda, B, ldb, C, ldc, e, split_k, workspace, s);
-  return launch_gemm<2, 2, 2, 2>(ta, tb, M, N, K, A, lda, B, ldb, C, ldc, e, split_k, workspace, s);
+  const GemmRoute rt = gemm_route(transA != 0, transB != 0, M, N, K, lda, ldb, a_aligned16 != 0, b_aligned16 != 0,
+                                  split_k);
+  out4[0] = rt.family;
+  out4[1] = rt.p0;
+  out4[2] = rt.p1;
+  out4[3] = rt.flags;
+  return GCNK_OK;
 }
 
 extern "C" int64_t gcnk_colsum_workspace_bytes(int32_t M, int32_t N) {

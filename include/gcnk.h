@@ -50,7 +50,7 @@
 extern "C" {
 #endif
 
-#define GCNK_ABI_VERSION 12
+#define GCNK_ABI_VERSION 13
 
 #define GCNK_OK 0
 #define GCNK_EARG (-1)
@@ -215,6 +215,28 @@ int gcnk_gemm_f32(int32_t transA, int32_t transB, int32_t M, int32_t N, int32_t 
                   float* C, int64_t ldc,
                   const float* bias, int32_t epilogue, const float* R, int64_t ldr, float scale,
                   int32_t split_k, float* workspace, int64_t workspace_bytes, void* stream);
+/* Test aid (ABI 13): the kernel gcnk_gemm_f32 launches for these arguments,
+ * decided by the one host function the launch itself switches on (nothing is
+ * launched here).  a_aligned16 / b_aligned16: A's / B's base pointer is 16-B
+ * aligned.  out4 = {family, p0, p1, flags}:
+ *   family   GCNK_GEMM_ROUTE_*; p0, p1 its template parameters -- NARROW and
+ *            SHORTK {KCH, NT}, SKINNY {KB, NT}, SMALLM {KBW, NTG} -- or, for the
+ *            two TILED families, {transA, transB} as 0 / 1
+ *   flags    GCNK_GEMM_ROUTE_SPLIT: K is reduced in more than one slab (a
+ *            reduce kernel applies the epilogue); GCNK_GEMM_ROUTE_PTR_FETCH: an
+ *            operand of a TILED family spans more than its 32-bit buffer
+ *            offsets, so the kernel loads through 64-bit pointers.
+ * M, N > 0 (gcnk_gemm_f32 launches nothing otherwise). */
+#define GCNK_GEMM_ROUTE_NARROW 1     /* gemm_shortk_kernel<13|16, 2>: gc2's H1 W2 past 16k rows */
+#define GCNK_GEMM_ROUTE_SKINNY 2     /* gemm_skinny_ksplit_kernel<KB, NT> */
+#define GCNK_GEMM_ROUTE_SHORTK 3     /* gemm_shortk_kernel<1..8, 3> */
+#define GCNK_GEMM_ROUTE_SMALLM 4     /* gemm_smallm_wk_kernel + gemm_slab_reduce4_kernel */
+#define GCNK_GEMM_ROUTE_TILED_N16 5  /* gemm_f32_mfma_kernel, 128 x 16 tile (N <= 16) */
+#define GCNK_GEMM_ROUTE_TILED 6      /* gemm_f32_mfma_kernel, 64 x 64 tile */
+#define GCNK_GEMM_ROUTE_SPLIT 1
+#define GCNK_GEMM_ROUTE_PTR_FETCH 2
+int gcnk_gemm_route(int32_t transA, int32_t transB, int32_t M, int32_t N, int32_t K, int64_t lda, int64_t ldb,
+                    int32_t a_aligned16, int32_t b_aligned16, int32_t split_k, int32_t* out4);
 
 /* ---------------------------------------------------------------------------
  * out[n] = sum_m X[m, n]  (bias gradient, autograd of layer.py:110).
