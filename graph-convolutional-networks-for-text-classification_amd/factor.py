@@ -21,11 +21,11 @@ of the SpMM never run.  The association differs from A (X W1) only in fp32
 rounding (checked against the reference's goldens to 1e-4, tests/).
 """
 import os
-import threading
 
 import numpy as np
 import torch
 
+from .derived import cache_of
 from .sparse import CSR
 
 MAX_HUBS = 128    # hub rows staged in LDS (S_T [hubs x F]; the kernel checks the LDS budget)
@@ -62,14 +62,12 @@ ROWS_PER_BLOCK = 32   # csrc/factor.hip kRB
 REC_HEAD = 68
 REC_ROW = 36
 
-_lock = threading.Lock()
-
 
 class HubFactor:
     """The (A-hat, X)-fixed operands of the factored gc1, resident on the device."""
 
     __slots__ = ("M", "H", "K", "hubs", "k0", "Kc", "U", "perm", "rec", "rec_words", "nblk", "x_hub",
-                 "x_hub_dense", "_src")
+                 "x_hub_dense")
 
     def hub_operand(self, train=False):
         """'csr' or 'dense': which form of X[hubs] the product S_T = X[hubs] W1
@@ -239,28 +237,5 @@ def get(adj, xop):
     """The cached HubFactor of (adj, X), built on first use; None when the
     operands do not factor (the caller runs the generic SpMM path)."""
     src = xop.csr if xop.csr is not None else xop.dense
-    # U and A_H bake in A-hat's values too: an in-place change of either
-    # operand's values is a new key (ADVICE r3)
-    key = (id(src), src.data_ptr() if isinstance(src, torch.Tensor) else src.rowptr.data_ptr(),
-           src._version if isinstance(src, torch.Tensor) else src.val._version,
-           adj.val.data_ptr(), adj.val._version)
-    cache = getattr(adj, "_factors", None)
-    if cache is None:
-        with _lock:
-            cache = getattr(adj, "_factors", None)
-            if cache is None:
-                cache = adj._factors = {}
-    hit = cache.get(key)
-    if hit is not None:
-        return hit[1]
-    with _lock:
-        hit = cache.get(key)
-        if hit is not None:
-            return hit[1]
-        f = build(adj, xop)
-        if f is not None:
-            f._src = src
-        while len(cache) >= 4:
-            cache.pop(next(iter(cache)))
-        cache[key] = (src, f)   # the entry holds the operand: its id cannot be recycled while cached
-        return f
+    # (U and A_H bake in A-hat's values as well as X's: both are sources)
+    return cache_of(adj, "_factors", 4).get(id(src), (adj, src), build, adj, xop)

@@ -34,6 +34,7 @@ from torch.nn import Module, Parameter
 
 from . import _lib
 from . import ops
+from .derived import parts, stamp
 from .ops import Epilogue, GCNFn, GraphConvFn, Operand
 from .sparse import as_csr
 
@@ -181,21 +182,6 @@ def _host_keep_mask_locked(shape, p, n, pinned):
     return out
 
 
-def _aliases(t):
-    """The tensors whose version counters track in-place changes of t's data."""
-    if isinstance(t, torch.Tensor):
-        if t.layout == torch.sparse_coo:
-            return (t._indices(), t._values())
-        if t.layout == torch.sparse_csr:
-            return (t.crow_indices(), t.col_indices(), t.values())
-        return (t,)
-    return ()
-
-
-def _vkey(t, aliases):
-    return (getattr(t, "_version", None),) + tuple(p._version for p in aliases)
-
-
 _NO_DROPOUT = Epilogue(_lib.EPI_BIAS_RELU)
 
 
@@ -244,7 +230,7 @@ class GCN(Module):
         self.dropout_rng = dropout_rng
         # hash-dropout stream position, read and advanced on the device (not in state_dict)
         self.register_buffer("_rng_base", torch.zeros(1, dtype=torch.int64), persistent=False)
-        self._memo = None   # (x, adj, version keys, Operand, CSR) of the last call
+        self._memo = None   # (x, adj, their parts and stamps, Operand, CSR) of the last call
 
     def _dropout_args(self, nrows, device):
         """gc1's ops.Epilogue for layer.py:185 (ATen dropout semantics)."""
@@ -269,12 +255,12 @@ class GCN(Module):
         call: the trainer passes the same two tensors every epoch
         (trainer.py:357,382), and re-deriving the cache keys cost ~10 us."""
         m = self._memo
-        if m is not None and m[0] is x and m[1] is adj and m[2] == _vkey(x, m[5]) and m[3] == _vkey(adj, m[6]):
-            return m[4], m[7]
+        if m is not None and m[0] is x and m[1] is adj and m[3] == stamp(of=m[2]):
+            return m[4], m[5]
         a = as_csr(adj)
         xop = Operand(x)
-        xa, aa = _aliases(x), _aliases(adj)
-        self._memo = (x, adj, _vkey(x, xa), _vkey(adj, aa), xop, xa, aa, a)
+        held = parts(x, adj)
+        self._memo = (x, adj, held, stamp(of=held), xop, a)
         return xop, a
 
     def forward(self, x, adj):

@@ -11,6 +11,7 @@ from typing import NamedTuple, Optional
 import torch
 
 from . import _lib, factor
+from .derived import cache_of
 from .sparse import CSR, DENSE_THRESHOLD, as_csr, require_device
 
 _NULL = ctypes.c_void_p(0)
@@ -300,7 +301,19 @@ class DenseAX:
     per (A-hat, X) pair: float64 row sums in CSR order rounded once
     (gcnk_aggregate_f32, the factored path's U kernel with every row light)."""
 
-    __slots__ = ("AX", "K", "_src")
+    __slots__ = ("AX", "K")
+
+    def __init__(self, adj, x):
+        K = x.shape[1]
+        if x.stride(1) != 1:
+            x = x.contiguous()
+        Kp = (K + 3) // 4 * 4
+        AX = torch.empty((adj.shape[0], Kp), dtype=torch.float32, device=adj.device)
+        with torch.cuda.device(adj.device):
+            _lib.check(_lib.load().gcnk_aggregate_f32(_ptr(adj.rowptr), _ptr(adj.colind), _ptr(adj.val), adj.shape[0],
+                                                      _ptr(x), x.stride(0), K, _ptr(AX), Kp, Kp,
+                                                      _stream(adj.device)), "gcnk_aggregate_f32")
+        self.AX, self.K = AX, K
 
 
 def dense_ax_for(adj, xop, F=None, P=None):
@@ -313,27 +326,7 @@ def dense_ax_for(adj, xop, F=None, P=None):
     if not fused_range(F or 0, P or 0):   # (csrc/dense_gc1.hip's range)
         return None
     src = xop.dense
-    key = (id(src), src.data_ptr(), src._version, adj.val.data_ptr(), adj.val._version)
-    cache = getattr(adj, "_dense_ax", None)
-    if cache is None:
-        cache = adj._dense_ax = {}
-    hit = cache.get(key)
-    if hit is not None:
-        return hit
-    if src.stride(1) != 1:
-        src = src.contiguous()
-    Kp = (K + 3) // 4 * 4
-    AX = torch.empty((adj.shape[0], Kp), dtype=torch.float32, device=adj.device)
-    with torch.cuda.device(adj.device):
-        _lib.check(_lib.load().gcnk_aggregate_f32(_ptr(adj.rowptr), _ptr(adj.colind), _ptr(adj.val), adj.shape[0],
-                                                  _ptr(src), src.stride(0), K, _ptr(AX), Kp, Kp,
-                                                  _stream(adj.device)), "gcnk_aggregate_f32")
-    d = DenseAX()
-    d.AX, d.K, d._src = AX, K, xop.dense   # (holds the operand: its id cannot be recycled while cached)
-    while len(cache) >= 4:
-        cache.pop(next(iter(cache)))
-    cache[key] = d
-    return d
+    return cache_of(adj, "_dense_ax", 4).get(id(src), (adj, src), DenseAX, adj, src)
 
 
 def dense_gc1(d, W1, b1, W2, epilogue=_lib.EPI_BIAS_RELU, mask=None, scale=1.0, keep_prob=1.0, seed=0, offset=0,
@@ -501,14 +494,15 @@ DENSE_OPERAND_MAX_BYTES = 1 << 30
 
 def dense_copy(a):
     """The dense [M, K] fp32 copy of CSR ``a`` (gcnk_csr_to_dense), cached on it."""
-    d = getattr(a, "_dense", None)
-    if d is None:
-        M, K = a.shape
-        d = torch.empty((M, K), dtype=torch.float32, device=a.device)
-        with torch.cuda.device(a.device):
-            _lib.check(_lib.load().gcnk_csr_to_dense(_ptr(a.rowptr), _ptr(a.colind), _ptr(a.val), M, K, _ptr(d),
-                                                     d.stride(0), _stream(a.device)), "gcnk_csr_to_dense")
-        a._dense = d
+    return cache_of(a, "_dense").get(None, (a,), _to_dense, a)
+
+
+def _to_dense(a):
+    M, K = a.shape
+    d = torch.empty((M, K), dtype=torch.float32, device=a.device)
+    with torch.cuda.device(a.device):
+        _lib.check(_lib.load().gcnk_csr_to_dense(_ptr(a.rowptr), _ptr(a.colind), _ptr(a.val), M, K, _ptr(d),
+                                                 d.stride(0), _stream(a.device)), "gcnk_csr_to_dense")
     return d
 
 

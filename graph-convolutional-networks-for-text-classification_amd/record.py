@@ -18,12 +18,11 @@ and ops.GCNFn's per-op path dispatches on the same value, so the launches,
 their arguments and their order agree and results are bitwise the same.
 """
 import ctypes
-import threading
 from collections import namedtuple
 
 import torch
 
-from . import _lib, factor, ops
+from . import _lib, derived, factor, ops
 from .sparse import CSR
 
 _c = ctypes
@@ -152,6 +151,7 @@ class ForwardRecord:
         s.s2, s.lds2 = _matrix(M, P, device, keep)
         _fill_plan(s.aP, p.plan_p, P, 0, device, keep)   # gc2's aggregation A S2 + b2 (ops.spmm, lanes 0)
         self.s, self.keep, self.kind, self.dax, self.M, self.F, self.P = s, keep, p.kind, p.dax, M, F, P
+        self.pinned = False   # (set once a hipGraph is captured through this record: derived.py)
 
     def run(self, W1, b1, W2, b2, epi, store_h1, stream):
         """(out, H1, self.dax) of one forward with ops.Epilogue `epi`; H1 is None unless store_h1."""
@@ -199,6 +199,7 @@ class BackwardRecord:
             s.gS1 = _matrix(rows, F, device, keep)[0]
         s.bwd2_ws, s.bwd2_ws_bytes = _scratch(int(_lib.load().gcnk_gcn_bwd2_workspace_bytes(M, F, P)), device, keep)
         self.s, self.keep, self.M, self.F, self.P, self.x_cols = s, keep, M, F, P, cols
+        self.pinned = False
 
     def run(self, G, H1, W2, scale, want_gw1, want_gb1, want_gw2, want_gb2, stream):
         """(gW1, gb1, gW2, gb2), each None unless wanted."""
@@ -215,15 +216,18 @@ class BackwardRecord:
         return gW1, gb1, gW2, gb2
 
 
-_lock = threading.Lock()
-
-
-# adj._records maps what a record was built for (tag "fwd" / "bwd", X's id, widths, stream)
-# and the knobs it was built under (ops.FACTOR_GC1, ops.FUSE_PROJECTION, ops.DENSE_AX,
-# factor.XHUB_DENSE; variant: fwd, X[hubs] in its training form; bwd, gW1 from the
-# forward's A-hat X) to the record and the operand and versions it was built from.
+# adj._records (a derived.Cache of 8) maps what a record was built for (tag "fwd" /
+# "bwd", X's id, widths, stream) and the knobs it was built under (ops.FACTOR_GC1,
+# ops.FUSE_PROJECTION, ops.DENSE_AX, factor.XHUB_DENSE; variant: fwd, a training
+# forward where X[hubs] may take its training form; bwd, gW1 from the forward's
+# A-hat X) to the record built from (adj, X); values() and items() show an entry as
+# Cached (the sources (adj, X), their stamp, the record).
 RecordKey = namedtuple("RecordKey", "tag src_id F P stream factor_gc1 fuse_projection dense_ax xhub_dense variant")
-Cached = namedtuple("Cached", "src versions rec")
+Cached = namedtuple("Cached", "srcs stamp rec")
+
+# records (and plans) displaced from their cache while a captured graph still
+# points into them, and the call that drops them once those graphs are gone
+_PINNED, release_pinned = derived.PINNED, derived.release_pinned
 
 
 def get_backward(adj, xop, F, P, device, dax=None):
@@ -237,64 +241,37 @@ def get(adj, xop, F, P, device, train=False):
     """(record, stream): the ForwardRecord of (adj, X, F, P) for torch's current
     stream, built on first use, and that stream.  ``train``: a forward whose H1
     the backward keeps (its X_hubs W1 may take another form, factor.hub_operand)."""
-    return _get(adj, xop, F, P, device, ForwardRecord, "fwd", bool(train) and factor.XHUB_TRAIN_TILE, train)
+    return _get(adj, xop, F, P, device, _forward_record, "fwd", bool(train) and factor.XHUB_TRAIN_TILE, train)
 
 
-def _get(adj, xop, F, P, device, cls, tag, variant, arg):
+def _forward_record(adj, xop, F, P, device, train):
+    """The training forward's record is the eval forward's wherever the mode
+    does not change the path (all but a factored gc1 whose X[hubs] has both
+    forms): one set of S1 / S2 / H1 scratch, filed under both keys."""
+    if train and factor.XHUB_TRAIN_TILE:
+        p = ops.choose_forward(adj, xop, F, P, True)
+        if p.kind != FACTORED or p.fac.hub_operand(True) == p.fac.hub_operand(False):
+            return get(adj, xop, F, P, device)[0]
+    return ForwardRecord(adj, xop, F, P, device, train)
+
+
+def _get(adj, xop, F, P, device, build, tag, variant, arg):
     """A record's launches bake in raw pointers to its scratch buffers, so a
     record is rebuilt when either operand's values change in place (the
     factored operands and plans are derived from them) and a record that was
-    used while a hipGraph was being captured is never evicted: the graph keeps
+    used while a hipGraph was being captured is pinned (derived.py): the graph keeps
     replaying into its buffers.  A record's scratch (S1, S2, H1) is shared by
     every launch on its stream; a graph captured on that stream replays into it, so two
-    graphs of the same record must not replay concurrently.  ``arg``: cls's last argument."""
+    graphs of the same record must not replay concurrently.  ``arg``: build's last argument."""
     stream = torch.cuda.current_stream(device).cuda_stream
     src = xop.csr if xop.csr is not None else xop.dense
     # RecordKey's fields as a plain tuple: it finds the stored RecordKey (equal,
     # same hash) without building one on every call
     key = (tag, id(src), F, P, stream, ops.FACTOR_GC1, ops.FUSE_PROJECTION, ops.DENSE_AX, factor.XHUB_DENSE, variant)
-    recs = getattr(adj, "_records", None)
+    recs = adj.__dict__.get("_records")
     if recs is None:
-        recs = adj.__dict__.setdefault("_records", {})   # (atomic: two threads get one dict)
-    capturing = torch.cuda.is_current_stream_capturing()
-    ver = (_version(src), _version(adj))
-    hit = recs.get(key)
-    if hit is not None and hit.src is src and ver == hit.versions:
-        if capturing:
-            hit.rec.pinned = True
-        return hit.rec, stream
-    with _lock:
-        rec = cls(adj, xop, F, P, device, arg)
-        rec.pinned = capturing
-        old = recs.get(key)
-        if old is not None and old.rec.pinned:
-            _PINNED.append(old.rec)   # replaced (operands changed) but still referenced by a graph
-        while len(recs) >= 8:
-            victim = next((k for k, v in recs.items() if not v.rec.pinned), None)
-            if victim is None:
-                break
-            recs.pop(victim)
-        recs[RecordKey(*key)] = Cached(src, ver, rec)
-        return rec, stream
-
-
-# records displaced from a cache while a captured graph still points into them:
-# kept alive (a replay writes into their buffers through raw pointers, which
-# no reference count sees), so this list grows by one record each time the
-# operands of a captured forward change in place; release_pinned() drops them
-# once the caller's graphs are gone
-_PINNED = []
-
-
-def release_pinned():
-    """Drop the records kept alive for hipGraphs captured before their operands
-    changed (call after those graphs are destroyed; replaying one afterwards
-    writes into freed memory).  Returns how many were dropped."""
-    with _lock:
-        n = len(_PINNED)
-        _PINNED.clear()
-    return n
-
-
-def _version(src):
-    return src._version if isinstance(src, torch.Tensor) else (src.val._version, src.val.data_ptr())
+        recs = derived.cache_of(adj, "_records", 8, RecordKey, Cached)
+    rec = recs.get(key, (adj, src), build, adj, xop, F, P, device, arg)
+    if torch.cuda.is_current_stream_capturing():
+        rec.pinned = True
+    return rec, stream

@@ -21,6 +21,7 @@ import threading
 import torch
 
 from . import _lib
+from .derived import Cache, stamp
 
 _INT32_MAX = 2**31 - 1
 
@@ -84,7 +85,11 @@ class Plan(PlanHeader):
     captured into a hipGraph take one region per capturing stream (every
     graph captured there shares it: their replays must not run concurrently
     on two streams), handed out from SPARE_REGIONS regions zeroed when the
-    plan is built, so a captured graph holds no memset node."""
+    plan is built, so a captured graph holds no memset node.
+
+    A captured launch holds raw pointers into `buf` as well, so a plan used
+    during a capture is `pinned` (derived.py): displaced from its CSR's cache,
+    it is kept alive for the graph's replays."""
 
     __slots__ = ("buf", "_counters", "_spares", "_captured", "_lock")
     SPARE_REGIONS = 16   # pre-zeroed regions handed to capturing streams
@@ -99,6 +104,10 @@ class Plan(PlanHeader):
     @property
     def header(self):
         return list(self.hdr)
+
+    @property
+    def pinned(self):
+        return bool(self._captured)
 
     def workspace_bytes(self, F):
         return int(_lib.load().gcnk_spmm_workspace_bytes(ctypes.cast(self.hdr, ctypes.c_void_p), int(F)))
@@ -119,11 +128,14 @@ class Plan(PlanHeader):
         """The counter region for a call on torch's current stream (None when the
         plan needs none); see the class docstring."""
         n = self.counter_bytes()
+        key = torch.cuda.current_stream(device).cuda_stream
+        capturing = torch.cuda.is_current_stream_capturing()
         if n <= 0:
+            if capturing:
+                self._captured.setdefault(key, None)   # (no region, but the graph points into `buf`)
             return None
         words = (n + 7) // 8 * 2
-        key = torch.cuda.current_stream(device).cuda_stream
-        if torch.cuda.is_current_stream_capturing():
+        if capturing:
             c = self._captured.get(key)
             if c is None:
                 with self._lock:
@@ -154,9 +166,8 @@ class CSR:
         self.shape = (int(shape[0]), int(shape[1]))
         self.nnz = int(self.colind.numel())
         self.device = self.rowptr.device
-        self._plans = {}
-        self._t = None
-        self._lock = threading.Lock()
+        self._plans = Cache()   # (derived.py: rebuilt when `val` changes in place)
+        self._t = Cache()
 
     def __repr__(self):
         return f"CSR(shape={self.shape}, nnz={self.nnz}, device={self.device})"
@@ -165,43 +176,37 @@ class CSR:
     def plan(self, ipc, groups, dense_threshold=DENSE_THRESHOLD):
         """Returns a Plan (device buffer + host header); built once per key (setup sync)."""
         key = (ipc, groups, float(dense_threshold))
-        p = self._plans.get(key)
-        if p is not None:
-            return p
-        with self._lock:
-            p = self._plans.get(key)
-            if p is not None:
-                return p
-            lib = _lib.load()
-            M, K = self.shape
-            with torch.cuda.device(self.device):
-                s = _stream_ptr(self.device)
-                nbytes = lib.gcnk_spmm_plan_bytes(self.rowptr.data_ptr(), self.colind.data_ptr(), M, K, self.nnz,
-                                                  ipc, groups, float(dense_threshold), s)
-                if nbytes < 0:
-                    _lib.check(int(nbytes), "gcnk_spmm_plan_bytes")
-                buf = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=self.device)
-                _lib.check(lib.gcnk_spmm_plan_build(self.rowptr.data_ptr(), self.colind.data_ptr(),
-                                                    self.val.data_ptr(), M, K, self.nnz, ipc, groups,
-                                                    float(dense_threshold), buf.data_ptr(), nbytes, s),
-                           "gcnk_spmm_plan_build")
-                hdr = (ctypes.c_int32 * 16)()
-                _lib.check(lib.gcnk_spmm_plan_query(buf.data_ptr(), ctypes.cast(hdr, ctypes.c_void_p), s),
-                           "gcnk_spmm_plan_query")
-                p = Plan(buf, hdr)
-                p.prime(self.device)
-            self._plans[key] = p
-            return p
+        return self._plans.get(key, (self,), self._build_plan, *key)
+
+    def _build_plan(self, ipc, groups, dense_threshold):
+        lib = _lib.load()
+        M, K = self.shape
+        with torch.cuda.device(self.device):
+            s = _stream_ptr(self.device)
+            nbytes = lib.gcnk_spmm_plan_bytes(self.rowptr.data_ptr(), self.colind.data_ptr(), M, K, self.nnz,
+                                              ipc, groups, dense_threshold, s)
+            if nbytes < 0:
+                _lib.check(int(nbytes), "gcnk_spmm_plan_bytes")
+            buf = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=self.device)
+            _lib.check(lib.gcnk_spmm_plan_build(self.rowptr.data_ptr(), self.colind.data_ptr(),
+                                                self.val.data_ptr(), M, K, self.nnz, ipc, groups,
+                                                dense_threshold, buf.data_ptr(), nbytes, s),
+                       "gcnk_spmm_plan_build")
+            hdr = (ctypes.c_int32 * 16)()
+            _lib.check(lib.gcnk_spmm_plan_query(buf.data_ptr(), ctypes.cast(hdr, ctypes.c_void_p), s),
+                       "gcnk_spmm_plan_query")
+            p = Plan(buf, hdr)
+            p.prime(self.device)
+        return p
 
     # -- transpose (gcnk_csr_transpose), cached ---------------------------------------
     def t(self):
-        if self._t is not None:
-            return self._t
-        with self._lock:
-            if self._t is None:
-                self._t = transpose(self)
-                self._t._t = self
-            return self._t
+        return self._t.get(None, (self,), self._transposed)
+
+    def _transposed(self):
+        t = transpose(self)
+        t._t.put(None, (t, self), self)   # (its transpose is this matrix while both keep their values)
+        return t
 
 
 def transpose(a):
@@ -342,12 +347,7 @@ class _Cache:
 
     @staticmethod
     def key(t):
-        if t.layout == torch.sparse_csr:
-            parts = (t.crow_indices(), t.col_indices(), t.values())
-        else:
-            parts = (t._indices(), t._values())
-        return (t.layout, tuple(t.shape), t.device.index,
-                tuple(p.data_ptr() for p in parts), tuple(p._version for p in parts))
+        return (t.layout, tuple(t.shape), t.device.index, stamp(t, storage=True))
 
     def get(self, t):
         k = self.key(t)

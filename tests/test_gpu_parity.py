@@ -1255,6 +1255,9 @@ def test_xhub_product_per_mode(r8):
     assert rec_e.kind == rec_t.kind == record.FACTORED
     assert rec_e.s.x_dense and not rec_e.s.x.plan
     assert bool(rec_t.s.x.plan) == (f.hub_operand(True) == "csr")
+    # two records only because X[hubs] takes another form in training here
+    fwd = {id(c.rec) for k, c in adj._records.items() if k.tag == "fwd"}
+    assert (rec_e is not rec_t) == bool(factor.XHUB_TRAIN_TILE) and len(fwd) == (2 if factor.XHUB_TRAIN_TILE else 1)
 
 
 @pytest.mark.parametrize("F,P,ndoc", [(52, 3, 2000), (200, 20, 2000), (36, 32, 2000), (200, 20, 12000)])
@@ -1600,6 +1603,157 @@ def test_forward_record_follows_in_place_feature_updates(r8):
         ref = m(torch.sparse_coo_tensor(X._indices(), X._values().clone(), X.shape).coalesce(), A)
     assert not torch.equal(a, b)
     assert torch.equal(b, ref)
+
+
+def _sym_random_csr(n, nnz, rng, full_row):
+    """Symmetric, duplicate-free random CSR arrays of ~nnz nonzeros; row (and
+    column) ``full_row`` holds every column: n nonzeros, the most a row of a
+    duplicate-free n x n matrix can hold, a heavy row of its SpMM plans."""
+    r, c = rng.integers(0, n, nnz // 2), rng.integers(0, n, nnz // 2)
+    r = np.concatenate([r, np.full(n, full_row)])
+    c = np.concatenate([c, np.arange(n)])
+    key = np.unique(np.concatenate([r * n + c, c * n + r]))
+    rows, cols = key // n, key % n
+    lo, hi = np.minimum(rows, cols), np.maximum(rows, cols)
+    vals = (0.05 + ((lo * 31 + hi * 17) % 97) / 97.0).astype(np.float32)   # (symmetric in (row, col))
+    return csr_ref.coo_to_csr(rows, cols, vals, (n, n))
+
+
+@pytest.fixture(scope="module")
+def inplace_graphs():
+    """name -> (A's CSR arrays, n, {X name: CSR arrays or dense array}, nfeat):
+    the smallest graphs that reach each cache of derived state.  doc_topic
+    takes the dense-AX path and, with that off, factors; its X is dense, or a
+    CSR full enough (38 %) to be multiplied through its dense copy.  random
+    does neither, and its X stays sparse at 5 % fill and goes through its
+    dense copy at 50 %."""
+    g = datasets.doc_topic_graph(2000, 40, 5, seed=4)
+    a = from_torch(g["adj"].to(DEV))
+    x = from_torch(g["features"].to(DEV))
+    arrays = lambda m: tuple(t.cpu().numpy() for t in (m.rowptr, m.colind, m.val))   # noqa: E731
+    out = {"doc_topic": (arrays(a), g["nodes"], {"csr": arrays(x), "dense": g["features_dense"]}, g["nfeat"])}
+    rng = np.random.default_rng(77)
+    n, k = 300, 64
+    xs = {}
+    for name, fill in (("sparse", 0.05), ("half", 0.5)):
+        keep = rng.random((n, k)) < fill
+        r, c = np.nonzero(keep)
+        xs[name] = csr_ref.coo_to_csr(r, c, rng.standard_normal(len(r)).astype(np.float32), (n, k))
+    out["random"] = (_sym_random_csr(n, 2400, rng, full_row=7), n, xs, k)
+    return out
+
+
+def _inplace_operands(graphs, graph, xname):
+    (rp, ci, v), n, xs, nfeat = graphs[graph]
+    A = from_arrays(rp, ci, v, (n, n), DEV)
+    x = xs[xname]
+    X = torch.from_numpy(x).to(DEV) if isinstance(x, np.ndarray) else from_arrays(*x, (n, nfeat), DEV)
+    return A, X, nfeat
+
+
+def _clone_operand(o):
+    from graph_convolutional_networks_for_text_classification_amd.sparse import CSR
+    return o.clone() if isinstance(o, torch.Tensor) else CSR(o.rowptr.clone(), o.colind.clone(), o.val.clone(), o.shape)
+
+
+def _inplace_run(m, X, A, mode):
+    """(logits, the four gradients or None) of one forward (and backward)."""
+    if mode == "eval":
+        m.eval()
+        with torch.no_grad():
+            return m(X, A).clone(), None
+    m.train()
+    m.zero_grad()
+    out = m(X, A)
+    out.square().sum().backward()
+    return out.detach().clone(), {k: p.grad.clone() for k, p in m.named_parameters()}
+
+
+# (graph, X, the operand whose val changes, the forward's path)
+INPLACE_CASES = [("doc_topic", "dense", "adj", "dense_ax"), ("doc_topic", "dense", "adj", "factored"),
+                 ("random", "sparse", "adj", "spmm"), ("random", "sparse", "x", "spmm"),
+                 ("random", "half", "x", "spmm"), ("doc_topic", "csr", "x", "factored")]
+
+
+@pytest.mark.parametrize("mode", ["eval", "train", "per_op"])
+@pytest.mark.parametrize("graph,xname,mutate,path", INPLACE_CASES)
+def test_in_place_change_of_a_csr_operand_rebuilds_everything_derived(inplace_graphs, graph, xname, mutate, path,
+                                                                      mode, monkeypatch):
+    """A CSR passed as adj or x whose ``val`` changes in place: every object
+    built from its values (plans, transposes, the dense copy, the hub factor,
+    A-hat X, the launch records, GCN's memo) is rebuilt, so the next forward and
+    backward are bitwise those of a fresh CSR of the same arrays -- through the
+    records in eval and in training (no dropout, so the runs compare), and op
+    by op (training, so the backward's transposes and their plans count too)."""
+    from graph_convolutional_networks_for_text_classification_amd import ops, record
+    monkeypatch.setattr(ops, "USE_RECORD", mode != "per_op")
+    monkeypatch.setattr(ops, "DENSE_AX", path == "dense_ax")
+    A, X, nfeat = _inplace_operands(inplace_graphs, graph, xname)
+    torch.manual_seed(11)
+    m = GCN(nfeat=nfeat, nhid=16, nclass=4, dropout=0.0).to(DEV)
+    first, _ = _inplace_run(m, X, A, mode)
+    (A if mutate == "adj" else X).val.mul_(0.5)
+    got, grads = _inplace_run(m, X, A, mode)
+    want, want_grads = _inplace_run(m, _clone_operand(X), _clone_operand(A), mode)
+    assert torch.equal(got, want)
+    assert not torch.equal(got, first)
+    if mode != "eval":
+        assert len(grads) == 4
+        for k in grads:
+            assert torch.equal(grads[k], want_grads[k]), k
+    if mode != "per_op":   # the forward took the path whose cached operands this case is about
+        kinds = {c.rec.kind for k, c in A._records.items() if k.tag == "fwd"}
+        assert kinds <= {"dense_ax": {record.DENSE_AX}, "factored": {record.FACTORED},
+                         "spmm": {record.SPMM_PROJ, record.SPMM_GEMM}}[path], kinds
+
+
+def test_train_and_eval_forwards_share_one_record_where_the_mode_changes_nothing(inplace_graphs):
+    """On a graph that does not factor the training forward's record is the
+    eval forward's (one S1 / S2 / H1 scratch, not two), under both keys."""
+    from graph_convolutional_networks_for_text_classification_amd import factor, record
+    A, X, nfeat = _inplace_operands(inplace_graphs, "random", "sparse")
+    torch.manual_seed(11)
+    m = GCN(nfeat=nfeat, nhid=16, nclass=4, dropout=0.0).to(DEV)
+    _inplace_run(m, X, A, "train")
+    _inplace_run(m, X, A, "eval")
+    fwd = [(k, c.rec) for k, c in A._records.items() if k.tag == "fwd"]
+    assert len({id(r) for _, r in fwd}) == 1 and isinstance(fwd[0][1], record.ForwardRecord)
+    assert len(fwd) == (2 if factor.XHUB_TRAIN_TILE else 1)
+
+
+def test_captured_per_op_graph_keeps_its_plans_after_an_in_place_change(inplace_graphs, monkeypatch):
+    """A per-op forward captured into a hipGraph holds raw pointers into its
+    plans.  After an in-place change of the adjacency an eager forward builds
+    new plans; the displaced ones are pinned, so they stay on the keep-alive
+    list and the graph's replay still computes from the old values, until
+    record.release_pinned() drops them (no replay after that)."""
+    from graph_convolutional_networks_for_text_classification_amd import ops, record
+    monkeypatch.setattr(ops, "USE_RECORD", False)
+    A, X, nfeat = _inplace_operands(inplace_graphs, "random", "sparse")
+    torch.manual_seed(11)
+    m = GCN(nfeat=nfeat, nhid=16, nclass=4, dropout=0.0).to(DEV).eval()
+    record.release_pinned()
+    with torch.no_grad():
+        eager = m(X, A).clone()            # builds the plans outside the capture
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            out = m(X, A)
+        g.replay()
+        torch.cuda.synchronize()
+        before = out.clone()
+        assert torch.equal(before, eager)
+        old = [p for p in A._plans.values() if p.pinned]   # the ones the captured launches ran on
+        assert old
+        A.val.mul_(0.5)
+        changed = m(X, A).clone()          # displaces the plans
+        assert not torch.equal(changed, eager)
+        assert not any(p in old for p in A._plans.values())
+        out.zero_()
+        g.replay()
+        torch.cuda.synchronize()
+        assert torch.equal(out, before)
+    del g
+    assert record.release_pinned() >= 1
 
 
 # ------------------------------------------------------------------------------ device factor build
