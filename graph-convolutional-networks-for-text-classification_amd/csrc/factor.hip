@@ -22,7 +22,7 @@
 // F columns):
 //   0. every operand of the block in one round of loads: W1[Kc] and S_T into LDS,
 //      the block's U rows into LDS (16-B DMA; or its U fragments into registers),
-//      its A_H record and W2 into LDS;
+//      its A_H record into LDS, the wave's W2 fragments into registers;
 //   1. Z_strip = U_strip W1[Kc] on v_mfma_f32_16x16x4_f32 (exact fp32 FMA chains);
 //   2. Z through LDS to row-major; + A_H S_T, + b1, ReLU, dropout (mask or hash,
 //      the row kernel's epilogue); H1 stored only when a backward needs it;
@@ -95,7 +95,7 @@ hubfactor_gc1_kernel(FactorArgs a) {
   const int blk = (int)blockIdx.x;
   const int64_t m0 = (int64_t)blk * kRB;  // position in the block order (U's rows)
   // LDS: region1 = s_B [Kr][F] + bpad zeros (phase 1), then s_Z [kRB][Fz]
-  //      | s_S [nhub][F] | s_W2 [F][P] | s_bias [F] | s_rec | s_red [NP][3][2][64][4]
+  //      | s_S [nhub][F] | s_bias [F] | s_rec | s_red [NP][3][2][64][4]
   // Every global operand is staged here in the one round of loads that opens the
   // kernel: a global load behind an LDS-read index costs a full memory round trip
   // under load (~1-2 us each, measured), so nothing after the first wait touches
@@ -104,8 +104,7 @@ hubfactor_gc1_kernel(FactorArgs a) {
   float* s_B = smem;
   float* s_Z = smem;
   float* s_S = smem + r1;
-  float* s_W2 = s_S + a.nhub * F;
-  float* s_bias = s_W2 + ((F * a.P + 3) & ~3);
+  float* s_bias = s_S + a.nhub * F;
   int32_t* s_rec = reinterpret_cast<int32_t*>(s_bias + F);
   float* s_red = reinterpret_cast<float*>(s_rec + a.rec_words);
   // u_lds: U's 32 rows [kRB][KPU] after s_red; row stride = 4 (mod 64), so lane
@@ -115,8 +114,8 @@ hubfactor_gc1_kernel(FactorArgs a) {
 
   // ---- 0. loads, all issued before the first wait: zeros first (no LDS-DMA in
   //      flight yet), then LDS-DMA of W1[Kc] (flat), U's rows (u_lds; else the
-  //      U fragments straight into registers below), the block's record, S_T,
-  //      W2 and b1
+  //      U fragments straight into registers below), the block's record, S_T
+  //      and b1; phase 3's W2 fragments straight into registers
   for (int e = a.Kc * F + tid; e < Kr * F + bpad(F, NTQ); e += kThreads) s_B[e] = 0.f;
   if (!a.epi.bias)
     for (int e = tid; e < F; e += kThreads) s_bias[e] = 0.f;
@@ -140,12 +139,32 @@ hubfactor_gc1_kernel(FactorArgs a) {
     const int s4 = a.nhub * Q;  // S_T [nhub x F] flat (lds == F)
     for (int e0 = wv * 64; e0 < s4; e0 += kThreads)
       if (e0 + lane < s4) lds_dma16(a.S + 4 * (e0 + lane), s_S + 4 * e0);
-    const int w1 = F * a.P;     // W2 [F x P] flat (ldw2 == P), dword pieces
-    for (int e0 = wv * 64; e0 < w1; e0 += kThreads)
-      if (e0 + lane < w1) lds_dma4(a.W2 + e0 + lane, s_W2 + e0);
     if (a.epi.bias)
       for (int e0 = wv * 64; e0 < Q; e0 += kThreads)
         if (e0 + lane < Q) lds_dma16(a.epi.bias + 4 * (e0 + lane), s_bias + 4 * e0);
+  }
+  // Phase 3's B fragments, W2[k][16 t + n] for this wave's quarter of the K = F
+  // sum (ldw2 == P), through a buffer resource over exactly W2's F P floats: a
+  // row k >= F lies past it and reads 0 with no compare.  A column 16 t + n >= P
+  // would land inside the next row, so its lane starts from an offset past the
+  // resource, chosen once per n-tile.  W2 depends on nothing the kernel
+  // computes: read from LDS after the phase-2 barrier, each fragment sat behind
+  // its own compare, exec mask and 32-bit multiply (~150 instructions a wave on
+  // the block's serial path).
+  constexpr int kq = Fp / 16;  // k-steps per quarter
+  float bw[NP][kq];
+  {
+    const __amdgpu_buffer_rsrc_t rw =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.W2), (short)0, F * a.P * 4, 0x00020000);
+    const int kstep = 16 * a.P;   // bytes between the lane's consecutive k (4 rows of P floats)
+#pragma unroll
+    for (int t = 0; t < NP; ++t) {
+      const int col = 16 * t + (lane & 15);
+      int off = col < a.P ? ((4 * quarter * kq + (lane >> 4)) * a.P + col) * 4 : 0x7ff00000;
+#pragma unroll
+      for (int j = 0; j < kq; ++j, off += kstep)
+        bw[t][j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rw, off, 0, 0));
+    }
   }
   float af[KS];
   const int64_t urow = m0 + 16 * strip + (lane & 15);
@@ -309,24 +328,16 @@ hubfactor_gc1_kernel(FactorArgs a) {
   //      added in order
   f32x4 pc[NP];
   {
-    const int n = lane & 15;
-    constexpr int kq = Fp / 16;  // k-steps per quarter
     float av[kq];
 #pragma unroll
     for (int j = 0; j < kq; ++j) av[j] = s_Z[(16 * strip + (lane & 15)) * Fz + 4 * (quarter * kq + j) + (lane >> 4)];
 #pragma unroll
     for (int t = 0; t < NP; ++t) {
-      float bw[kq];
-#pragma unroll
-      for (int j = 0; j < kq; ++j) {
-        const int k = 4 * (quarter * kq + j) + (lane >> 4);
-        bw[j] = (k < F && 16 * t + n < a.P) ? s_W2[k * a.P + 16 * t + n] : 0.f;
-      }
       f32x4 p0 = f32x4{0.f, 0.f, 0.f, 0.f}, p1 = p0;
 #pragma unroll
       for (int j = 0; j < kq; j += 2) {
-        p0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j], bw[j], p0, 0, 0, 0);
-        p1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j + 1], bw[j + 1], p1, 0, 0, 0);
+        p0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j], bw[t][j], p0, 0, 0, 0);
+        p1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j + 1], bw[t][j + 1], p1, 0, 0, 0);
       }
       pc[t] = p0 + p1;
     }
@@ -387,7 +398,7 @@ static int pick_np(int32_t P) { return P <= 16 ? 1 : 2; }
 static int64_t hubfactor_lds_bytes(int32_t F, int32_t Kc, int32_t nhub, int32_t rec_words, int32_t P) {
   const int64_t Fz = 64 * pick_ntq(F) + 4, Kr = 4 * pick_ks(Kc);
   const int64_t r1 = std::max<int64_t>(Kr * F + bpad(F, pick_ntq(F)), (int64_t)kRB * Fz);
-  return 4 * (r1 + (int64_t)nhub * F + (((int64_t)F * P + 3) & ~3LL) + F + rec_words + pick_np(P) * 3 * 2 * 64 * 4);
+  return 4 * (r1 + (int64_t)nhub * F + F + rec_words + pick_np(P) * 3 * 2 * 64 * 4);
 }
 
 // U's staged rows (u_lds): kRB rows of 4 KS floats at a stride of 4 (mod 64)

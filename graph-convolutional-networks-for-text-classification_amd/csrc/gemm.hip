@@ -14,6 +14,8 @@
 // fragment read is 16 consecutive floats per k row.
 #include "gcnk_common.h"
 
+#include <type_traits>
+
 namespace gcnk {
 namespace {
 
@@ -385,11 +387,28 @@ gemm_shortk_kernel(int32_t M, int32_t N, int32_t K, const float* __restrict__ A,
 // A's 16-deep k block is read as one float4 per lane (k = 16 c + 4 q + j for
 // quadrant q, step j) and B's rows in the same permuted order, so each MFMA
 // still pairs A[row][k] with B[k][col].  Fixed-order sums: reproducible.
-template <int KBW, int NTG>
+// A last row tile of only 1 .. kWkRem rows (R8's 50 hubs: 2) takes no MFMAs: a
+// 16-row tile is 16 of them a wave -- 512 cycles of the matrix pipe, 1/4 of the
+// kernel's at M = 50 -- for those few rows.  The kernel is compiled per (NM,
+// VREM): NM row tiles on the MFMA path, and with VREM the M % 16 rows after them
+// on the VALU (straight-line code either way: as a run-time switch the MFMA
+// bodies each waited for every load, and the remainder rows' loads sank into
+// their branch, a second round trip).  Every lane reads the remainder rows' 16-B
+// k slices of its own quadrant (16 lanes the same address) and multiplies them
+// into its own B values: per row and n-tile the lane's k ascending (2-wide FMAs
+// over a pair of n-tiles), then the four quadrants of a column added as
+// (q0 + q1) + (q2 + q3) by two lane swaps -- a fixed order, reproducible, but not
+// the MFMA's, so these rows differ from an MFMA tile's in the last bits.  Every
+// lane then holds row 16 NM + i, column r; in the MFMA's C/D layout that is
+// register i of the tile's quadrant 0 (the other quadrants' rows lie past M).
+constexpr int kWkRem = 2;
+template <int KBW, int NTG, int NM, bool VREM>
 __global__ void __launch_bounds__(512)
 gemm_smallm_wk_kernel(int32_t M, int32_t N, int32_t K, const float* __restrict__ A, int64_t lda,
                       const float* __restrict__ B, int64_t ldb, float* __restrict__ slab) {
-  constexpr int kW = 8, RT = 4;   // waves, 16-row tiles (M <= 64)
+  constexpr int kW = 8, RT = NM + (VREM ? 1 : 0);   // waves, 16-row tiles (M <= 64: RT <= 4)
+  constexpr int NMA = NM > 0 ? NM : 1;              // (array extents)
+  static_assert(RT >= 1 && RT <= 4 && NTG % 2 == 0 && kWkRem <= 4, "M <= 64; n-tiles in pairs; rows in one quadrant");
   __shared__ __attribute__((aligned(16))) f32x4 s_acc[kW][RT * NTG][64];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int r = lane & 15, q = lane >> 4;
@@ -405,15 +424,26 @@ gemm_smallm_wk_kernel(int32_t M, int32_t N, int32_t K, const float* __restrict__
       __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(A), (short)0, M * (int)lda * 4, 0x00020000);
   const __amdgpu_buffer_rsrc_t rb =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(B), (short)0, K * (int)ldb * 4, 0x00020000);
-  f32x4 a4[RT][KBW];
+  f32x4 a4[NMA][KBW];
 #pragma unroll
-  for (int t = 0; t < RT; ++t)
+  for (int t = 0; t < NM; ++t)
 #pragma unroll
     for (int c = 0; c < KBW; ++c) {
       const int row = 16 * t + r, k = 16 * ((int)kb0 + c) + 4 * q;
       a4[t][c] = __builtin_bit_cast(
           f32x4, __builtin_amdgcn_raw_buffer_load_b128(ra, (row * (int)lda + (k < K ? k : 0)) * 4, 0, 0));
     }
+  f32x4 r4[kWkRem][KBW];   // VREM: rows 16 NM + i, i < M % 16 (a row past M lies past the resource: 0)
+  if (VREM) {
+#pragma unroll
+    for (int i = 0; i < kWkRem; ++i)
+#pragma unroll
+      for (int c = 0; c < KBW; ++c) {
+        const int k = 16 * ((int)kb0 + c) + 4 * q;
+        r4[i][c] = __builtin_bit_cast(
+            f32x4, __builtin_amdgcn_raw_buffer_load_b128(ra, ((16 * NM + i) * (int)lda + (k < K ? k : 0)) * 4, 0, 0));
+      }
+  }
   float b[KBW][4][NTG];
 #pragma unroll
   for (int c = 0; c < KBW; ++c)
@@ -429,9 +459,9 @@ gemm_smallm_wk_kernel(int32_t M, int32_t N, int32_t K, const float* __restrict__
   // serial round trips; left to itself the scheduler also spread the loads
   // over the MFMAs, each waited for right after it left)
   __builtin_amdgcn_sched_barrier(0);
-  float4 a[RT][KBW];
+  float4 a[NMA][KBW];
 #pragma unroll
-  for (int t = 0; t < RT; ++t)
+  for (int t = 0; t < NM; ++t)
 #pragma unroll
     for (int c = 0; c < KBW; ++c) {
       const int k = 16 * ((int)kb0 + c) + 4 * q;
@@ -440,9 +470,9 @@ gemm_smallm_wk_kernel(int32_t M, int32_t N, int32_t K, const float* __restrict__
                             __int_as_float(__float_as_int(a4[t][c][2]) & (k + 2 < K ? -1 : 0)),
                             __int_as_float(__float_as_int(a4[t][c][3]) & (k + 3 < K ? -1 : 0)));
     }
-  f32x4 acc[RT][NTG];
+  f32x4 acc[NMA][NTG];
 #pragma unroll
-  for (int t = 0; t < RT; ++t)
+  for (int t = 0; t < NM; ++t)
 #pragma unroll
     for (int u = 0; u < NTG; ++u) acc[t][u] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -450,16 +480,47 @@ gemm_smallm_wk_kernel(int32_t M, int32_t N, int32_t K, const float* __restrict__
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
 #pragma unroll
-      for (int t = 0; t < RT; ++t) {
+      for (int t = 0; t < NM; ++t) {
         const float av = j == 0 ? a[t][c].x : j == 1 ? a[t][c].y : j == 2 ? a[t][c].z : a[t][c].w;
 #pragma unroll
         for (int u = 0; u < NTG; ++u) acc[t][u] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b[c][j][u], acc[t][u], 0, 0, 0);
       }
     }
+  f32x4 vt[NTG];
+  if (VREM) {
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
 #pragma unroll
-  for (int t = 0; t < RT; ++t)
+    for (int u = 0; u < NTG; ++u) vt[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < kWkRem; ++i)
+#pragma unroll
+      for (int u = 0; u < NTG; u += 2) {
+        f32x2 p = {0.f, 0.f};
+#pragma unroll
+        for (int c = 0; c < KBW; ++c)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const int k = 16 * ((int)kb0 + c) + 4 * q + j;
+            const float av = __int_as_float(__float_as_int(r4[i][c][j]) & (k < K ? -1 : 0));
+            p = __builtin_elementwise_fma(f32x2{av, av}, f32x2{b[c][j][u], b[c][j][u + 1]}, p);
+          }
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const auto s16 = __builtin_amdgcn_permlane16_swap(__float_as_uint(p[h]), __float_as_uint(p[h]), false, false);
+          const float y = __uint_as_float(s16[0]) + __uint_as_float(s16[1]);
+          const auto s32 = __builtin_amdgcn_permlane32_swap(__float_as_uint(y), __float_as_uint(y), false, false);
+          vt[u + h][i] = __uint_as_float(s32[0]) + __uint_as_float(s32[1]);
+        }
+      }
+  }
+#pragma unroll
+  for (int t = 0; t < NM; ++t)
 #pragma unroll
     for (int u = 0; u < NTG; ++u) s_acc[w][t * NTG + u][lane] = acc[t][u];
+  if (VREM) {
+#pragma unroll
+    for (int u = 0; u < NTG; ++u) s_acc[w][NM * NTG + u][lane] = vt[u];
+  }
   __syncthreads();
   // the eight waves' tiles summed in wave order; thread e owns (tile e / 64, lane e % 64)
   float* out = slab + (int64_t)blockIdx.x * M * N;
@@ -521,6 +582,81 @@ gemm_slab_reduce4_kernel(int32_t M, int32_t N, int32_t S, const float* __restric
   c[1] = gemm_epi(epi, t.y, m, n + 1);
   c[2] = gemm_epi(epi, t.z, m, n + 2);
   c[3] = gemm_epi(epi, t.w, m, n + 3);
+}
+
+// The same sums in the same order for the common case (the slab array within a
+// buffer resource's 32-bit byte offsets, C's rows 16-B aligned: slab_reduce_buf
+// below), with the launch's serial instruction path cut down; the kernel is one
+// memory round trip and one barrier, so every instruction a wave issues before
+// its loads leave or after the sum is time.
+//   - 32-bit offsets into a buffer resource over exactly the S slabs: no 64-bit
+//     index arithmetic ahead of the first load.
+//   - `per` slabs a group, in batches of B <= per loads issued unconditionally:
+//     a slab past the group's end or an item past the output gets an offset
+//     past the resource and reads +0, and acc + (+0) keeps acc's bits (acc
+//     starts as +0 and can never become -0), so nothing is selected afterwards.
+//   - the output coordinates (a 32-bit division) and C's address are computed
+//     while the first batch is in flight, not between the sum and the store
+//     (pinned there as integers: a pointer through the asm loses its address
+//     space and the store becomes a flat one).
+//   - one 16-B store.
+template <int B>
+__global__ void __launch_bounds__(256)
+gemm_slab_reduce4_buf_kernel(int32_t M, int32_t N, int32_t S, int32_t per, const float* __restrict__ slab,
+                             float* __restrict__ C, int64_t ldc, GemmEpi epi) {
+  __shared__ f32x4 s_part[kRedGroups][kRedItems];
+  const uint32_t i = threadIdx.x % kRedItems, g = threadIdx.x / kRedItems;
+  const uint32_t total4 = (uint32_t)(M * N) / 4, stride = total4 * 16;   // float4 per slab, bytes per slab
+  const uint32_t o = blockIdx.x * kRedItems + i;
+  const uint32_t s0 = g * per, s1 = min((uint32_t)S, s0 + per);
+  const __amdgpu_buffer_rsrc_t rs =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(slab), (short)0, (int)(S * stride), 0x00020000);
+  constexpr uint32_t kPast = 0x7ff00000;   // past any resource the host admits
+  const bool ook = o < total4;
+  uint32_t off = s0 * stride + o * 16;
+  f32x4 v[B];
+  auto fetch = [&](uint32_t s) __attribute__((always_inline)) {
+#pragma unroll
+    for (int j = 0; j < B; ++j)
+      v[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
+                                           rs, (int)(ook && s + j < s1 ? off + j * stride : kPast), 0, 0));
+  };
+  f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+  fetch(s0);
+  __builtin_amdgcn_sched_barrier(0);
+  // (N % 4 == 0: the four outputs lie in one row)
+  uint32_t m = o / ((uint32_t)N / 4), n = 4 * (o - m * ((uint32_t)N / 4));
+  int64_t co = (int64_t)m * ldc + n;
+  asm volatile("" : "+v"(m), "+v"(n), "+v"(co));   // computed here, in the loads' shadow, not sunk to the store
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int j = 0; j < B; ++j) acc += v[j];
+  for (uint32_t sb = B; sb < (uint32_t)per; sb += B) {
+    off += B * stride;
+    fetch(s0 + sb);
+#pragma unroll
+    for (int j = 0; j < B; ++j) acc += v[j];
+  }
+  s_part[g][i] = acc;
+  __syncthreads();
+  if (g != 0 || !ook) return;
+  f32x4 t = s_part[0][i];
+#pragma unroll
+  for (int gg = 1; gg < kRedGroups; ++gg) t += s_part[gg][i];
+  if (epi.code != GCNK_GEMM_EPI_NONE) {   // tested once, around the element work
+    t[0] = gemm_epi(epi, t[0], m, n + 0);
+    t[1] = gemm_epi(epi, t[1], m, n + 1);
+    t[2] = gemm_epi(epi, t[2], m, n + 2);
+    t[3] = gemm_epi(epi, t[3], m, n + 3);
+  }
+  *reinterpret_cast<f32x4*>(C + co) = t;
+}
+
+// Whether the slab sum may take gemm_slab_reduce4_buf_kernel: every offset it
+// forms ((s0 + per + B) slabs at most, s0 + per <= S + 15) below kBufSpanLimit,
+// 16-B rows of C for the one store.
+inline bool slab_reduce_buf(int32_t M, int32_t N, int32_t S, const float* slab, const float* C, int64_t ldc) {
+  return ((int64_t)S + 2 * kRedGroups) * M * N * 4 < kBufSpanLimit && ldc % 4 == 0 && aligned16(C) && aligned16(slab);
 }
 
 // Sum split-K slabs in slab order, then apply the epilogue.
@@ -627,7 +763,9 @@ __global__ void colsum_pass2_kernel(const float* __restrict__ part, int32_t nblk
 //   NARROW     gemm_shortk_kernel<KCH, 2>          KCH in {13, 16}
 //   SKINNY     gemm_skinny_ksplit_kernel<KB, NT>   KB in {1, 2, 4, 8, 16} x NT in {1, 2, 4}
 //   SHORTK     gemm_shortk_kernel<KCH, 3>          KCH in 1 .. 8
-//   SMALLM     gemm_smallm_wk_kernel<2, 2> + gemm_slab_reduce4_kernel (always split)
+//   SMALLM     gemm_smallm_wk_kernel<2, 2, NM, VREM> (by M: NM MFMA row tiles, VREM a last tile of 1 or 2
+//              rows on the VALU) + gemm_slab_reduce4_buf_kernel<B> (B in {1, 2, 4, 8} by the
+//              slab count), or gemm_slab_reduce4_kernel where slab_reduce_buf refuses (always split)
 //   TILED_N16  gemm_f32_mfma_kernel<4, 1, 2, 1, TA, TB>   the four transposes,
 //   TILED      gemm_f32_mfma_kernel<2, 2, 2, 2, TA, TB>   each whole or split
 //              (+ gemm_splitk_reduce_kernel), through buffer or pointer loads
@@ -788,13 +926,41 @@ extern "C" int gcnk_gemm_f32(int32_t transA, int32_t transB, int32_t M, int32_t 
     case GCNK_GEMM_ROUTE_SMALLM: {
       const int64_t wk_S = smallm_slabs(K);
       const dim3 grid((unsigned)wk_S, (unsigned)((N + 16 * GCNK_WK_NTG - 1) / (16 * GCNK_WK_NTG)));
-      hipLaunchKernelGGL((gemm_smallm_wk_kernel<GCNK_WK_KBW, GCNK_WK_NTG>), grid, dim3(512), 0, s, M, N, K, A, lda,
-                         B, ldb, workspace);
+      // NM full-height MFMA row tiles, and a last tile of 1 .. kWkRem rows on the VALU (else on the MFMAs too)
+      const bool vrem = M % 16 >= 1 && M % 16 <= kWkRem;
+      const int nm = vrem ? M / 16 : (M + 15) / 16;
+#define GCNK_WK(NM_, VREM_)                                                                                       \
+  hipLaunchKernelGGL((gemm_smallm_wk_kernel<GCNK_WK_KBW, GCNK_WK_NTG, NM_, VREM_>), grid, dim3(512), 0, s, M, N, K, \
+                     A, lda, B, ldb, workspace)
+      if (vrem) {
+        if (nm == 0) GCNK_WK(0, true);
+        else if (nm == 1) GCNK_WK(1, true);
+        else if (nm == 2) GCNK_WK(2, true);
+        else GCNK_WK(3, true);
+      } else {
+        if (nm == 1) GCNK_WK(1, false);
+        else if (nm == 2) GCNK_WK(2, false);
+        else if (nm == 3) GCNK_WK(3, false);
+        else GCNK_WK(4, false);
+      }
+#undef GCNK_WK
       int rc = launch_check("gemm_smallm_wk_kernel");
       if (rc) return rc;
       const int64_t total4 = (int64_t)M * N / 4;
-      hipLaunchKernelGGL(gemm_slab_reduce4_kernel, dim3((unsigned)((total4 + kRedItems - 1) / kRedItems)),
-                         dim3(kRedItems * kRedGroups), 0, s, M, N, (int32_t)wk_S, workspace, C, ldc, e);
+      const dim3 rgrid((unsigned)((total4 + kRedItems - 1) / kRedItems)), rblock(kRedItems * kRedGroups);
+      if (slab_reduce_buf(M, N, (int32_t)wk_S, workspace, C, ldc)) {
+        // loads in flight per batch sized to the slabs a group holds (R8: 30 slabs over 16 groups, 2)
+        const int32_t per = ((int32_t)wk_S + kRedGroups - 1) / kRedGroups;
+#define GCNK_RED_BUF(B_) \
+  hipLaunchKernelGGL(gemm_slab_reduce4_buf_kernel<B_>, rgrid, rblock, 0, s, M, N, (int32_t)wk_S, per, workspace, C, ldc, e)
+        if (per <= 1) GCNK_RED_BUF(1);
+        else if (per <= 2) GCNK_RED_BUF(2);
+        else if (per <= 4) GCNK_RED_BUF(4);
+        else GCNK_RED_BUF(8);
+#undef GCNK_RED_BUF
+        return launch_check("gemm_slab_reduce4_buf_kernel");
+      }
+      hipLaunchKernelGGL(gemm_slab_reduce4_kernel, rgrid, rblock, 0, s, M, N, (int32_t)wk_S, workspace, C, ldc, e);
       return launch_check("gemm_slab_reduce4_kernel");
     }
     case GCNK_GEMM_ROUTE_TILED_N16:

@@ -230,7 +230,7 @@ int gcnk_gemm_f32(int32_t transA, int32_t transB, int32_t M, int32_t N, int32_t 
 #define GCNK_GEMM_ROUTE_NARROW 1     /* gemm_shortk_kernel<13|16, 2>: gc2's H1 W2 past 16k rows */
 #define GCNK_GEMM_ROUTE_SKINNY 2     /* gemm_skinny_ksplit_kernel<KB, NT> */
 #define GCNK_GEMM_ROUTE_SHORTK 3     /* gemm_shortk_kernel<1..8, 3> */
-#define GCNK_GEMM_ROUTE_SMALLM 4     /* gemm_smallm_wk_kernel + gemm_slab_reduce4_kernel */
+#define GCNK_GEMM_ROUTE_SMALLM 4     /* gemm_smallm_wk_kernel + gemm_slab_reduce4_buf_kernel (or gemm_slab_reduce4_kernel) */
 #define GCNK_GEMM_ROUTE_TILED_N16 5  /* gemm_f32_mfma_kernel, 128 x 16 tile (N <= 16) */
 #define GCNK_GEMM_ROUTE_TILED 6      /* gemm_f32_mfma_kernel, 64 x 64 tile */
 #define GCNK_GEMM_ROUTE_SPLIT 1

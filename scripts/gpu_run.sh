@@ -7,6 +7,7 @@
 #   micro:<binary>[:<args>]   prebuilt scripts/micro/<binary> on the R8 A-hat (NS_ONLY, PROF honoured)
 #   test:<pytest -k expr>     GPU tests matching the expression (-m gpu)
 #   tests                     the whole GPU suite
+#   smoke                     __graft_entry__.smoke()
 #   bench[:<args>]            python bench.py --full <args> (default --steps 200 --warmup 20) -> bench.json
 #   benchn:<name>:<args>      python bench.py <args> -> bench_<name>.json (a plain run unless <args> holds --full)
 #   prof:<script>[:<args>]    rocprofv3 --kernel-trace --stats over python scripts/<script> -> <script>_stats/
@@ -45,6 +46,9 @@ for step in "$@"; do
       timeout -k 10 1000 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread \
         > "$out/pytest_gpu.log" 2>&1
       rc=$?; tail -n 15 "$out/pytest_gpu.log"; [ $rc -eq 0 ] || { echo "rc=$rc"; exit 1; } ;;
+    smoke)
+      timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$out/smoke.log" 2>&1
+      rc=$?; tail -n 5 "$out/smoke.log"; [ $rc -eq 0 ] || { echo "rc=$rc"; exit 1; } ;;
     bench)
       args="${rest:---steps 200 --warmup 20}"
       timeout -k 10 900 python -u bench.py --full $args --rocprof-dir "$out/bench_prof" > "$out/bench.json" 2> "$out/bench.err"
