@@ -127,6 +127,13 @@ SIGNATURES = {
         _f32, _u64, _u64, _vp,            # keep_prob, seed, offset, rng_base
         _vp, _i64, _vp, _i64, _vp, _i64,  # W2, ldw2, H, ldh, C2, ldc2
         _vp]),                            # stream
+    "gcnk_hubfactor_gc2_f32": (ctypes.c_int, [
+        _i32, _i32, _i32, _vp, _i32,      # M, H, P, rec, rec_words
+        _vp, _vp, _vp, _vp, _vp, _vp,     # diag, pre, hub_ids (host), hub_rp (host), hub_ci, hub_val
+        _vp, _i64, _vp, _vp, _i64,        # S2, lds2, b2, out, ldo
+        _vp]),                            # stream
+    # rowptr, colind, val, M, hub_index, perm, diag, pre, stream
+    "gcnk_factor_diag_f32": (ctypes.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "gcnk_dense_gc1_f32": (ctypes.c_int, [
         _i32, _i32, _i32, _i32,           # M, K, F, P
         _vp, _i64, _vp, _i64,             # AX, ldax, W1, ldw1
@@ -167,6 +174,9 @@ SIGNATURES = {
     "gcnk_csr_transpose": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
 }
 
+# added within ABI 13 (gc2 from the hub factor): absent from variants of an older tree
+NEWER_THAN_SOME_VARIANTS = ("gcnk_hubfactor_gc2_f32", "gcnk_factor_diag_f32")
+
 _lock = threading.Lock()
 _lib = None
 
@@ -189,7 +199,13 @@ def load():
                 "or `make -C <package>/csrc` (hipcc --offload-arch=gfx950). There is no CPU fallback.")
         lib = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
-            fn = getattr(lib, name)
+            fn = getattr(lib, name, None)
+            if fn is None:
+                # an experiment variant built from an older csrc (an A/B's parent library)
+                # may lack the newest entry points: their callers test for them
+                if LIB_PATH == PRODUCT_LIB or name not in NEWER_THAN_SOME_VARIANTS:
+                    raise RuntimeError(f"{LIB_PATH} does not export {name}")
+                continue
             fn.restype = res
             fn.argtypes = args
         v = lib.gcnk_abi_version()

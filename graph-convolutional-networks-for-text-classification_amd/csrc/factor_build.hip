@@ -284,6 +284,36 @@ __global__ void __launch_bounds__(256) factor_xl_kernel(const int32_t* __restric
   }
 }
 
+// thread per position p of the block order (gc2 from the factor, csrc/factor_gc2.hip):
+// diag[p] = A-hat_rr of r = perm[p] (0: no diagonal, a hub row, p >= M) and
+// pre[p] = the row's hub items whose column precedes r (-1 for a hub row: its
+// sum has a workgroup of its own; 0 past M)
+__global__ void __launch_bounds__(256) factor_diag_kernel(const int32_t* __restrict__ rowptr,
+                                                          const int32_t* __restrict__ colind,
+                                                          const float* __restrict__ val, int32_t M, int32_t npos,
+                                                          const int32_t* __restrict__ hub_index,
+                                                          const int32_t* __restrict__ perm, float* __restrict__ diag,
+                                                          int32_t* __restrict__ pre) {
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= npos) return;
+  float d = 0.f;
+  int32_t n = 0;
+  if (p < M) {
+    const int r = perm[p];
+    if (hub_index[r] >= 0) {
+      n = -1;
+    } else {
+      for (int j = rowptr[r]; j < rowptr[r + 1]; ++j) {
+        const int c = colind[j];
+        if (c == r) d = val[j];
+        else if (c < r && hub_index[c] >= 0) ++n;
+      }
+    }
+  }
+  diag[p] = d;
+  pre[p] = n;
+}
+
 // workgroup per selected row i: out row i = in row rows[i] (CSR: at the offset
 // of the lengths of rows[0 .. i), summed in order; block 0 also writes the end)
 __global__ void __launch_bounds__(256) csr_gather_rows_kernel(const int32_t* __restrict__ rowptr,
@@ -425,6 +455,20 @@ extern "C" int gcnk_aggregate_f32(const int32_t* rowptr, const int32_t* colind, 
   hipLaunchKernelGGL(factor_u_kernel, dim3(grid), dim3(64 * kBuildRows), 0, reinterpret_cast<hipStream_t>(stream),
                      rowptr, colind, val, M, nullptr, nullptr, X, ldx, K, out, ldo, Kp);
   return launch_check("factor_u_kernel");
+}
+
+extern "C" int gcnk_factor_diag_f32(const int32_t* rowptr, const int32_t* colind, const float* val, int32_t M,
+                                    const int32_t* hub_index, const int32_t* perm, float* diag, int32_t* pre,
+                                    void* stream) {
+  if (M <= 0 || !rowptr || !colind || !val || !hub_index || !perm || !diag || !pre) {
+    set_error("gcnk_factor_diag_f32: bad sizes or null operand (M=%d)", M);
+    return GCNK_EARG;
+  }
+  const int64_t npos = ((int64_t)M + kRecRows - 1) / kRecRows * kRecRows;
+  hipLaunchKernelGGL(factor_diag_kernel, dim3((unsigned)((npos + 255) / 256)), dim3(256), 0,
+                     reinterpret_cast<hipStream_t>(stream), rowptr, colind, val, M, (int32_t)npos, hub_index, perm,
+                     diag, pre);
+  return launch_check("factor_diag_kernel");
 }
 
 extern "C" int gcnk_factor_records(const int32_t* rowptr, const int32_t* colind, const float* val, int32_t M,

@@ -91,7 +91,13 @@ extern "C" int gcnk_gcn_forward_f32(const gcnk_gcn_fwd* rec, const float* W1, co
       return GCNK_EARG;
   }
   if (rc != GCNK_OK) return rc;
-  // gc2: logits = A-hat S2 + b2  (layer.py:106,110)
+  // gc2: logits = A-hat S2 + b2  (layer.py:106,110); factored: from the hub
+  // factor, the SpMM where that kernel refuses the shapes (nothing was launched)
+  if (r.kind == GCNK_FWD_FACTORED && r.gc2_diag) {
+    rc = gcnk_hubfactor_gc2_f32(r.M, r.nhub, r.P, r.rec, r.rec_words, r.gc2_diag, r.gc2_pre, r.gc2_hub_ids,
+                                r.gc2_hub_rp, r.gc2_hub_ci, r.gc2_hub_val, r.s2, r.lds2, b2, out, ldo, stream);
+    if (rc != GCNK_EUNSUP) return rc;
+  }
   return spmm_ref(r.aP, r.s2, r.lds2, r.P, out, ldo, b2, b2 ? GCNK_EPI_BIAS : GCNK_EPI_NONE, nullptr, 0, 1.f, 1.f, 0, 0,
                   nullptr, stream);
 }
@@ -103,7 +109,7 @@ extern "C" int32_t gcnk_gcn_fwd_layout(int64_t* out, int32_t n) {
                        (int64_t)offsetof(gcnk_gcn_fwd, aF), (int64_t)offsetof(gcnk_gcn_fwd, aP),
                        (int64_t)offsetof(gcnk_gcn_fwd, ld_h1_tmp), (int64_t)offsetof(gcnk_plan_ref, lanes_hint),
                        (int64_t)sizeof(gcnk_gcn_bwd), (int64_t)offsetof(gcnk_gcn_bwd, xT),
-                       (int64_t)offsetof(gcnk_gcn_bwd, bwd2_ws_bytes)};
+                       (int64_t)offsetof(gcnk_gcn_bwd, bwd2_ws_bytes), (int64_t)offsetof(gcnk_gcn_fwd, gc2_diag)};
   const int32_t m = (int32_t)(sizeof(v) / sizeof(v[0]));
   for (int32_t i = 0; i < n && i < m; ++i) out[i] = v[i];
   return m;

@@ -66,8 +66,12 @@ REC_ROW = 36
 class HubFactor:
     """The (A-hat, X)-fixed operands of the factored gc1, resident on the device."""
 
+    # diag, pre, a_hub_*: gc2's aggregation from the factor (csrc/factor_gc2.hip), fixed by
+    # A-hat alone -- per position of the block order the row's diagonal value and how
+    # many of its hub items precede it; A-hat's hub rows as a CSR in hub order, its row
+    # pointers and the hub row ids also as host int32 arrays (kernel arguments)
     __slots__ = ("M", "H", "K", "hubs", "k0", "Kc", "U", "perm", "rec", "rec_words", "nblk", "x_hub",
-                 "x_hub_dense")
+                 "x_hub_dense", "diag", "pre", "a_hub_rp", "a_hub_ci", "a_hub_val", "hub_ids_h", "a_hub_rp_h")
 
     def hub_operand(self, train=False):
         """'csr' or 'dense': which form of X[hubs] the product S_T = X[hubs] W1
@@ -94,6 +98,36 @@ def _perm(hubs, M):
     perm = np.insert(lights, np.minimum(pos - np.arange(H), len(lights)), hubs)
     assert len(perm) == M
     return perm
+
+
+def _gc2_operands(f, lib, adj, M, hubs_h, hubs_d, hub_index, perm_d, nblk, stream):
+    """gc2 from the factor (csrc/factor_gc2.hip), fixed by A-hat alone: the
+    diagonal and its place among each row's hub items per position of the block
+    order, and A-hat's hub rows as a CSR (their lengths: one copy of the row
+    pointers to the host; no torch kernel).  All None on a library that lacks
+    the entry points (an A/B's parent variant): gc2 then stays on the SpMM."""
+    from . import _lib
+    f.diag = f.pre = f.a_hub_rp = f.a_hub_ci = f.a_hub_val = f.hub_ids_h = f.a_hub_rp_h = None
+    if not hasattr(lib, "gcnk_factor_diag_f32"):
+        return
+    dev, H = adj.device, len(hubs_h)
+    rp, ci, v = adj.rowptr, adj.colind, adj.val
+    npos = nblk * ROWS_PER_BLOCK
+    f.diag = torch.empty(npos, dtype=torch.float32, device=dev)
+    f.pre = torch.empty(npos, dtype=torch.int32, device=dev)
+    _lib.check(lib.gcnk_factor_diag_f32(rp.data_ptr(), ci.data_ptr(), v.data_ptr(), M, hub_index.data_ptr(),
+                                        perm_d.data_ptr(), f.diag.data_ptr(), f.pre.data_ptr(), stream),
+               "gcnk_factor_diag_f32")
+    rp_h = rp.cpu().numpy()
+    f.a_hub_rp_h = np.concatenate([[0], np.cumsum(rp_h[hubs_h + 1] - rp_h[hubs_h])]).astype(np.int32)
+    f.hub_ids_h = np.ascontiguousarray(hubs_h, dtype=np.int32)
+    atot = int(f.a_hub_rp_h[-1])
+    f.a_hub_rp = torch.empty(H + 1, dtype=torch.int32, device=dev)
+    f.a_hub_ci = torch.empty(max(atot, 1), dtype=torch.int32, device=dev)
+    f.a_hub_val = torch.empty(max(atot, 1), dtype=torch.float32, device=dev)
+    _lib.check(lib.gcnk_csr_gather_rows(rp.data_ptr(), ci.data_ptr(), v.data_ptr(), hubs_d.data_ptr(), H,
+                                        f.a_hub_rp.data_ptr(), f.a_hub_ci.data_ptr(), f.a_hub_val.data_ptr(),
+                                        stream), "gcnk_csr_gather_rows")
 
 
 def build(adj, xop):
@@ -177,6 +211,7 @@ def build(adj, xop):
                                            perm_d.data_ptr(), rec.data_ptr(), rec_words, overflow.data_ptr(), stream),
                    "gcnk_factor_records")
         f = HubFactor()
+        _gc2_operands(f, lib, adj, M, hubs_h, hubs_d, hub_index, perm_d, nblk, stream)
         if x is not None:
             # X's hub rows as a CSR (rows in hub order)
             hrp = torch.empty(H + 1, dtype=torch.int32, device=dev)

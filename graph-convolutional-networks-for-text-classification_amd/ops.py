@@ -287,6 +287,35 @@ def hubfactor_gc1(f, W1, b1, W2, epilogue=_lib.EPI_BIAS_RELU, mask=None, scale=1
     return H1, S2
 
 
+# gc2's aggregation A-hat S2 + b2 of a factored forward through the factor too
+# (csrc/factor_gc2.hip: the records' items, the diagonal and A-hat's hub rows,
+# no row-unit -> item-range -> items chain); GCNK_FACTOR_GC2=0 keeps the SpMM's
+# row kernel (A/B timing).
+FACTOR_GC2 = os.environ.get("GCNK_FACTOR_GC2", "1") != "0"
+
+
+def hubfactor_gc2(f, S2, b2=None):
+    """out = A-hat S2 + b2 (reference layer.py:106,110 of gc2) through the hub
+    factorisation ``f`` (gcnk_hubfactor_gc2_f32), or None where the kernel
+    refuses the shapes (GCNK_EUNSUP: the caller runs the SpMM)."""
+    S2 = _dense_f32(S2, "gc2 support")
+    P = S2.shape[1]
+    if S2.shape[0] != f.M:
+        raise RuntimeError(f"hubfactor_gc2 shape mismatch: factor of {f.M} rows, support {tuple(S2.shape)}")
+    out = torch.empty((f.M, P), dtype=torch.float32, device=S2.device)
+    if b2 is not None:
+        b2 = b2.contiguous()
+    with torch.cuda.device(S2.device):
+        rc = _lib.load().gcnk_hubfactor_gc2_f32(
+            f.M, f.H, P, _ptr(f.rec), f.rec_words, _ptr(f.diag), _ptr(f.pre), f.hub_ids_h.ctypes.data,
+            f.a_hub_rp_h.ctypes.data, _ptr(f.a_hub_ci), _ptr(f.a_hub_val), _ptr(S2), S2.stride(0), _ptr(b2),
+            _ptr(out), P, _stream(S2.device))
+    if rc == _lib.EUNSUP:
+        return None
+    _lib.check(rc, "gcnk_hubfactor_gc2_f32")
+    return out
+
+
 # gc1 from a cached A-hat X (csrc/dense_gc1.hip) for a dense, narrow X (at most
 # DENSE_AX_MAX_K features: the gensim-shaped topic features of README.md:77,95):
 # one launch (A-hat X) W1 + b1, ReLU, dropout and gc2's H1 W2 instead of the
@@ -659,7 +688,7 @@ def record_backward(ctx, g, W2, H1, need):
 
 
 def _gc1_per_op(adj, xop, W1, b1, W2, epi, keep_h1, exclude=()):
-    """(H1, S2, DenseAX or None) op by op: the launches choose_forward's path
+    """(H1, S2, DenseAX or None, HubFactor or None) op by op: the launches choose_forward's path
     issues from one C call through its record."""
     path = choose_forward(adj, xop, W1.shape[1], W2.shape[1], keep_h1, exclude)
     kw = epi._asdict()
@@ -676,7 +705,7 @@ def _gc1_per_op(adj, xop, W1, b1, W2, epi, keep_h1, exclude=()):
             res = H1, gemm(H1, W2)
     if res is None:   # the kernel refused these operands (dense-AX, factored): ask again without its kind
         return _gc1_per_op(adj, xop, W1, b1, W2, epi, keep_h1, exclude + (path.kind,))
-    return res + (path.dax,)
+    return res + (path.dax, path.fac)
 
 
 class GCNFn(torch.autograd.Function):
@@ -705,8 +734,11 @@ class GCNFn(torch.autograd.Function):
         if res is not None:
             out, H1, ctx.dax = res
         else:
-            H1, S2, ctx.dax = _gc1_per_op(adj, xop, W1, b1, W2, epi, keep_h1)
-            out = spmm(adj, S2, bias=b2, epilogue=_lib.EPI_BIAS if b2 is not None else _lib.EPI_NONE)
+            H1, S2, ctx.dax, fac = _gc1_per_op(adj, xop, W1, b1, W2, epi, keep_h1)
+            # gc2's aggregation: from the factor on the factored path (the record's last launch), else the SpMM
+            out = hubfactor_gc2(fac, S2, b2) if fac is not None and fac.diag is not None and FACTOR_GC2 else None
+            if out is None:
+                out = spmm(adj, S2, bias=b2, epilogue=_lib.EPI_BIAS if b2 is not None else _lib.EPI_NONE)
         ctx.xop, ctx.adj, ctx.scale = xop, adj, float(epi.scale)
         ctx.has_b1, ctx.has_b2 = b1 is not None, b2 is not None
         ctx.save_for_backward(W2, H1)

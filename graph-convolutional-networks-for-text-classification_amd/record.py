@@ -44,7 +44,9 @@ class GcnFwd(_c.Structure):
                 ("Kc", _c.c_int32), ("nhub", _c.c_int32), ("k0", _c.c_int32), ("rec_words", _c.c_int32),
                 ("U", _c.c_void_p), ("ldu", _c.c_int64), ("rec", _c.c_void_p),
                 ("aF", PlanRef), ("aP", PlanRef), ("s2", _c.c_void_p), ("lds2", _c.c_int64),
-                ("h1_tmp", _c.c_void_p), ("ld_h1_tmp", _c.c_int64)]
+                ("h1_tmp", _c.c_void_p), ("ld_h1_tmp", _c.c_int64),
+                ("gc2_diag", _c.c_void_p), ("gc2_pre", _c.c_void_p), ("gc2_hub_ids", _c.c_void_p),
+                ("gc2_hub_rp", _c.c_void_p), ("gc2_hub_ci", _c.c_void_p), ("gc2_hub_val", _c.c_void_p)]
 
 
 class GcnBwd(_c.Structure):
@@ -68,7 +70,7 @@ def layout_ok():
     n = _lib.load().gcnk_gcn_fwd_layout(buf, 16)
     want = [_c.sizeof(PlanRef), _c.sizeof(GcnFwd), GcnFwd.x.offset, GcnFwd.U.offset, GcnFwd.aF.offset,
             GcnFwd.aP.offset, GcnFwd.ld_h1_tmp.offset, PlanRef.lanes_hint.offset, _c.sizeof(GcnBwd),
-            GcnBwd.xT.offset, GcnBwd.bwd2_ws_bytes.offset]
+            GcnBwd.xT.offset, GcnBwd.bwd2_ws_bytes.offset, GcnFwd.gc2_diag.offset]
     return n == len(want) and list(buf)[:n] == want
 
 
@@ -134,6 +136,11 @@ class ForwardRecord:
             s.Kc, s.nhub, s.k0, s.rec_words = fac.Kc, fac.H, fac.k0, fac.rec_words
             s.U, s.ldu, s.rec = fac.U.data_ptr(), fac.U.stride(0), fac.rec.data_ptr()
             keep += [fac.U, fac.rec]
+            if ops.FACTOR_GC2 and fac.diag is not None:   # gc2's aggregation from the factor too (hub ids / row pointers: host arrays)
+                s.gc2_diag, s.gc2_pre = fac.diag.data_ptr(), fac.pre.data_ptr()
+                s.gc2_hub_ids, s.gc2_hub_rp = fac.hub_ids_h.ctypes.data, fac.a_hub_rp_h.ctypes.data
+                s.gc2_hub_ci, s.gc2_hub_val = fac.a_hub_ci.data_ptr(), fac.a_hub_val.data_ptr()
+                keep += [fac.diag, fac.pre, fac.hub_ids_h, fac.a_hub_rp_h, fac.a_hub_ci, fac.a_hub_val]
         else:
             # H1 scratch for an eval forward: the unfused path's intermediate, and
             # the fused path's fallback where the library refuses the fusion (an
@@ -218,9 +225,9 @@ class BackwardRecord:
 
 # adj._records (a derived.Cache of 8) maps what a record was built for (tag "fwd" /
 # "bwd", X's id, widths, stream) and the knobs it was built under (ops.FACTOR_GC1,
-# ops.FUSE_PROJECTION, ops.DENSE_AX, factor.XHUB_DENSE; variant: fwd, a training
-# forward where X[hubs] may take its training form; bwd, gW1 from the forward's
-# A-hat X) to the record built from (adj, X); values() and items() show an entry as
+# ops.FUSE_PROJECTION, ops.DENSE_AX, factor.XHUB_DENSE; variant: fwd, the pair (a
+# training forward where X[hubs] may take its training form, ops.FACTOR_GC2); bwd,
+# gW1 from the forward's A-hat X) to the record built from (adj, X); values() and items() show an entry as
 # Cached (the sources (adj, X), their stamp, the record).
 RecordKey = namedtuple("RecordKey", "tag src_id F P stream factor_gc1 fuse_projection dense_ax xhub_dense variant")
 Cached = namedtuple("Cached", "srcs stamp rec")
@@ -241,7 +248,8 @@ def get(adj, xop, F, P, device, train=False):
     """(record, stream): the ForwardRecord of (adj, X, F, P) for torch's current
     stream, built on first use, and that stream.  ``train``: a forward whose H1
     the backward keeps (its X_hubs W1 may take another form, factor.hub_operand)."""
-    return _get(adj, xop, F, P, device, _forward_record, "fwd", bool(train) and factor.XHUB_TRAIN_TILE, train)
+    return _get(adj, xop, F, P, device, _forward_record, "fwd",
+                (bool(train) and factor.XHUB_TRAIN_TILE, ops.FACTOR_GC2), train)
 
 
 def _forward_record(adj, xop, F, P, device, train):

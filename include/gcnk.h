@@ -50,6 +50,9 @@
 extern "C" {
 #endif
 
+/* ABI note: 13 also covers gcnk_factor_diag_f32, gcnk_hubfactor_gc2_f32 and the
+ * gc2_* fields at the end of gcnk_gcn_fwd (additions only: no existing symbol,
+ * field offset or meaning changed, so the number stayed). */
 #define GCNK_ABI_VERSION 13
 
 #define GCNK_OK 0
@@ -294,6 +297,27 @@ int gcnk_hubfactor_gc1_f32(int32_t M, int32_t F, int32_t Kc, int32_t nhub, int32
                            uint64_t offset, const uint64_t* rng_base, const float* W2, int64_t ldw2, float* H,
                            int64_t ldh, float* C2, int64_t ldc2, void* stream);
 /* ---------------------------------------------------------------------------
+ * gc2's aggregation from the hub factor (csrc/factor_gc2.hip; layer.py:106,110
+ * of gc2):  out[r, :P] = sum over row r's items of A-hat, in CSR column order,
+ * of val * S2[col, :P]  + b2  -- for the same (A-hat, X) structure as above.
+ * One launch: a workgroup per hub row (its full CSR row: hub_rp[H + 1], hub_ci,
+ * hub_val in hub order, hub_ids[H] the rows they are) and a workgroup per
+ * 32-row block record of gcnk_hubfactor_gc1_f32 (`rec`: a light row's hub-column
+ * items), with diag / pre of gcnk_factor_diag_f32 placing the row's diagonal
+ * among them; positions with pre < 0 or row id < 0 are skipped.  hub_ids and
+ * hub_rp are HOST arrays: they travel in the kernel's arguments.  b2 nullable.
+ * A light row is one fma chain from +0 in column order, then + b2: bitwise the
+ * SpMM's result for a row of one unit; a hub row is summed by 256 / (P / 4) lane
+ * groups that meet in a fixed order.  No workspace, no counters, no atomics.
+ * P % 4 == 0, P <= 32, H <= 128, lds2 % 4 == ldo % 4 == 0, S2 / out / rec / b2
+ * 16-B aligned, operands below 2 GiB, record + S2[hubs] within 64 KiB of LDS:
+ * otherwise GCNK_EUNSUP before any launch (callers run gcnk_spmm_csr_f32).
+ * ------------------------------------------------------------------------- */
+int gcnk_hubfactor_gc2_f32(int32_t M, int32_t H, int32_t P, const int32_t* rec, int32_t rec_words,
+                           const float* diag, const int32_t* pre, const int32_t* hub_ids /* host */,
+                           const int32_t* hub_rp /* host */, const int32_t* hub_ci, const float* hub_val,
+                           const float* S2, int64_t lds2, const float* b2, float* out, int64_t ldo, void* stream);
+/* ---------------------------------------------------------------------------
  * Narrow-feature gc1 (csrc/dense_gc1.hip; GCN.forward layer.py:164-190 through
  * layer.py:102,106,110,182,185 and gc2's support layer.py:102) for a dense X
  * with at most 128 features (the gensim-shaped topic features, README.md:77,95):
@@ -348,6 +372,15 @@ int gcnk_aggregate_f32(const int32_t* rowptr, const int32_t* colind, const float
 int gcnk_factor_u_f32(const int32_t* rowptr, const int32_t* colind, const float* val, int32_t M,
                       const int32_t* hub_index, const int32_t* perm, const float* Xl, int64_t ldxl, int32_t Kc,
                       float* U, int64_t ldu, int32_t Kcp, void* stream);
+/*   gcnk_factor_diag_f32: for each position p of the block order (32 * ceil(M / 32)
+ *                        of them), diag[p] = A-hat_rr of r = perm[p] (0 for a
+ *                        missing diagonal, a hub row, p >= M) and pre[p] = how
+ *                        many of the row's hub-column items have a column below
+ *                        r (-1 for a hub row, 0 for p >= M): where the diagonal
+ *                        sits among the record's items in CSR column order.
+ *                        Fixed by A-hat alone (gcnk_hubfactor_gc2_f32 reads them). */
+int gcnk_factor_diag_f32(const int32_t* rowptr, const int32_t* colind, const float* val, int32_t M,
+                         const int32_t* hub_index, const int32_t* perm, float* diag, int32_t* pre, void* stream);
 int gcnk_factor_records(const int32_t* rowptr, const int32_t* colind, const float* val, int32_t M,
                         const int32_t* hub_index, const int32_t* perm, int32_t* rec, int32_t rec_words,
                         int32_t* overflow, void* stream);
@@ -428,6 +461,15 @@ typedef struct gcnk_gcn_fwd {
   int64_t lds2;
   float* h1_tmp;               /* SPMM_GEMM scratch H1 when H1 == NULL */
   int64_t ld_h1_tmp;
+  /* FACTORED: gc2's aggregation through gcnk_hubfactor_gc2_f32 when gc2_diag != NULL
+   * (aP's SpMM where that entry answers GCNK_EUNSUP).  Added at the end of the
+   * struct within ABI 13: a zero-filled tail means "the SpMM", as before. */
+  const float* gc2_diag;
+  const int32_t* gc2_pre;
+  const int32_t* gc2_hub_ids;  /* host */
+  const int32_t* gc2_hub_rp;   /* host */
+  const int32_t* gc2_hub_ci;
+  const float* gc2_hub_val;
 } gcnk_gcn_fwd;
 
 int gcnk_gcn_forward_f32(const gcnk_gcn_fwd* rec,
@@ -474,8 +516,8 @@ int gcnk_gcn_backward_f32(const gcnk_gcn_bwd* rec, const float* G, const float* 
 
 /* Layout of the record structs for bindings that mirror them: writes up to n
  * of {sizeof plan_ref, sizeof gcn_fwd, offsetof x, U, aF, aP, ld_h1_tmp,
- * plan_ref.lanes_hint, sizeof gcn_bwd, gcn_bwd.xT, gcn_bwd.bwd2_ws_bytes} to
- * out and returns how many exist. */
+ * plan_ref.lanes_hint, sizeof gcn_bwd, gcn_bwd.xT, gcn_bwd.bwd2_ws_bytes,
+ * gcn_fwd.gc2_diag} to out and returns how many exist. */
 int32_t gcnk_gcn_fwd_layout(int64_t* out, int32_t n);
 
 /* ---------------------------------------------------------------------------

@@ -1,6 +1,7 @@
 """Per-op timing of the factored forward (warm, hipGraph of back-to-back
 launches, HIP events per call): X_hubs W1 (tile SpMM or GEMM),
-hubfactor_gc1, A-hat S2, and the whole record forward, on R8 and the
+hubfactor_gc1, A-hat S2 (the SpMM's row kernel and gcnk_hubfactor_gc2_f32), and
+the whole record forward (GCNK_FACTOR_GC2 picks its last launch), on R8 and the
 20ng-shaped graph.  One JSON line per (graph, op).  Run it under
 GCNK_LIB=<variant .so> to compare kernel builds.
 
@@ -58,6 +59,9 @@ def main():
             line("hubfactor_gc1", time_graph([lambda: ops.hubfactor_gc1(f, W1, b1, W2, store_h1=False, S=S_T)],
                                              args.reps))
             line("A S2", time_graph([lambda: ops.spmm(a, S2, bias=b2, epilogue=_lib.EPI_BIAS)], args.reps))
+            if f.diag is not None and ops.hubfactor_gc2(f, S2, b2) is not None:   # (None: a variant library without it)
+                line("A S2 (factored gc2)", time_graph([lambda: ops.hubfactor_gc2(f, S2, b2)], args.reps),
+                     in_forward=bool(ops.FACTOR_GC2))
             line("forward (record)", time_graph([lambda: m(x, adj)], args.reps))
     torch.cuda.synchronize()
 

@@ -3,7 +3,10 @@
 (replays a hipGraph of 10 forwards 20 times; GCNK_TRACE_GRAPH=20ng traces the
 BASELINE config-3 graph instead), then
 `python scripts/fwd_trace.py --report DIR` prints, per kernel position in the
-forward, its median duration and the median gap before it (us)."""
+forward, its median duration and the median gap before it (us).  The factored
+forward's last launch is factored_spmm_row_kernel (csrc/factor_gc2.hip);
+GCNK_FACTOR_GC2=0 in the environment of the traced run puts the SpMM's
+spmm_row_kernel back there for a side-by-side trace."""
 import argparse
 import glob
 import json
