@@ -115,6 +115,8 @@ SIGNATURES = {
         _vp, _i64, _i32, _i32, _i32, _f32,  # G, ldg, M, N, P, scale
         _vp, _i64, _vp, _vp, _vp,          # gZ1, ldz, gW, gb1, gb2
         _vp, _i64, _vp]),                  # workspace, bytes, stream
+    # M, N, P, ldh, ldz, h_align, z_align, ldgs, has_g, ldg, ldw, w_aligned16, out9
+    "gcnk_gcn_bwd2_route": (ctypes.c_int, [_i32, _i32, _i32, _i64, _i64, _i32, _i32, _i64, _i32, _i64, _i64, _i32, _vp]),
     "gcnk_stream_copy_f32": (ctypes.c_int, [_vp, _vp, _i64, _vp]),
     "gcnk_debug_poison_lds": (ctypes.c_int, [ctypes.c_uint32, _vp]),
     "gcnk_hubfactor_lds_bytes": (_i64, [_i32, _i32, _i32, _i32, _i32]),
@@ -174,8 +176,8 @@ SIGNATURES = {
     "gcnk_csr_transpose": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
 }
 
-# added within ABI 13 (gc2 from the hub factor): absent from variants of an older tree
-NEWER_THAN_SOME_VARIANTS = ("gcnk_hubfactor_gc2_f32", "gcnk_factor_diag_f32")
+# added within ABI 13 (gc2 from the hub factor, the backward's route report): absent from variants of an older tree
+NEWER_THAN_SOME_VARIANTS = ("gcnk_hubfactor_gc2_f32", "gcnk_factor_diag_f32", "gcnk_gcn_bwd2_route")
 
 _lock = threading.Lock()
 _lib = None

@@ -91,6 +91,22 @@ struct Bwd2Args {
   Epi stamps;                     // (debug timeline of a -DGCNK_STAMPS build only: .stamps)
 };
 
+// The kernel's run-time branches, as functions of its arguments alone: the
+// kernel takes them through these and gcnk_gcn_bwd2_route (include/gcnk.h)
+// reports them to tests, so the report cannot drift from the kernel.
+// gS2 (and, in column slice 0, G) staged by LDS-DMA: unpadded contiguous rows
+__host__ __device__ __forceinline__ bool bwd2_stage_dma(const Bwd2Args& a, int PM, bool with_g) {
+  return a.P == PM && a.ldgs == PM && (!with_g || a.ldg == PM);
+}
+// a lane's VEC rows of W2 loaded as one run of VEC PM floats in 16-B pieces
+__host__ __device__ __forceinline__ bool bwd2_w_row_runs(const Bwd2Args& a, int PM) {
+  return a.ldw == PM && a.P == PM && (reinterpret_cast<uintptr_t>(a.W) & 15) == 0;
+}
+// the row lanes summed as float4 pieces (16-B stores to the workspace's rows)
+__host__ __device__ __forceinline__ bool bwd2_vec_reduce(const Bwd2Args& a, int VEC, int PM) {
+  return VEC == 4 && a.P == PM && (a.part_ld & 3) == 0 && (a.N * a.P) % 4 == 0;
+}
+
 template <int VEC, int PM>
 __global__ void __launch_bounds__(kBwdBlock) gcn_bwd2_kernel(Bwd2Args a) {
   constexpr int KE = VEC * (PM + 1);  // accumulators per lane: gW2 terms + gb1
@@ -124,7 +140,7 @@ __global__ void __launch_bounds__(kBwdBlock) gcn_bwd2_kernel(Bwd2Args a) {
   // gS2 (and G) rows of the workgroup -> LDS, padded to PM columns with zeros.
   // Unpadded contiguous rows (P == PM == ld, R8): LDS-DMA, no register round
   // trip before the barrier (a load -> LDS store pair waits on its load)
-  const bool g_dma = a.P == PM && a.ldgs == PM && (!with_g || a.ldg == PM);
+  const bool g_dma = bwd2_stage_dma(a, PM, with_g);
   if (g_dma) {
     const int n = nr * PM, lane = tid & 63;
     for (int e0 = tid & ~63; e0 < n; e0 += kBwdBlock) {   // (wave-uniform base)
@@ -145,7 +161,7 @@ __global__ void __launch_bounds__(kBwdBlock) gcn_bwd2_kernel(Bwd2Args a) {
   // (W2 rows are ldw apart; with ldw == P == PM a lane's VEC rows are one run
   // of VEC PM floats: 16-B loads instead of VEC PM 4-B loads 32 lanes apart)
   float w[VEC][PM];
-  if (a.ldw == PM && a.P == PM && (reinterpret_cast<uintptr_t>(a.W) & 15) == 0) {
+  if (bwd2_w_row_runs(a, PM)) {
     // (clamped row, value masked by bits: the guarded load compiled to a branch
     // per load with its own vmcnt(0) -- eight serialised round trips)
 #pragma unroll
@@ -226,7 +242,7 @@ __global__ void __launch_bounds__(kBwdBlock) gcn_bwd2_kernel(Bwd2Args a) {
   // [N x P] row-major | gb1 [N] | gb2 [P]).  (The per-float form below spends
   // ~7 dword iterations of index math, eight LDS reads and a 4-B store per
   // element: the phase measured ~3.7 us at R8, profiles/r05_bwd2_stamps_v2.log.)
-  if (VEC == 4 && a.P == PM && (a.part_ld & 3) == 0 && (a.N * a.P) % 4 == 0) {
+  if (bwd2_vec_reduce(a, VEC, PM)) {
     constexpr int KE4 = KE / 4;   // VEC (PM + 1) / 4 float4 per thread (PM % 4 == 0)
     f32x4v* mine = reinterpret_cast<f32x4v*>(s_red) + tid * KE4;
 #pragma unroll
@@ -329,6 +345,47 @@ bool bwd2_geometry(int32_t M, int32_t N, int32_t P, bool vec4_ok, bool vec2_ok, 
   return true;
 }
 
+// Every compiled instantiation -- tests/bwd2_cases.py holds the same list
+// (INSTANTIATIONS) and a case for each entry:
+//   gcn_bwd2_kernel<VEC, PM>   VEC in {4, 2, 1} x PM in {8, 16, 32}, without <4, 32>
+//   (bwd2_geometry: more than 16 classes leave the float4 column path)
+
+// Largest alignment of a base pointer the column paths ask about: 16, 8 or 4 bytes.
+inline int ptr_align(const void* p) {
+  const uintptr_t u = reinterpret_cast<uintptr_t>(p);
+  return (u & 15u) == 0 ? 16 : (u & 7u) == 0 ? 8 : 4;
+}
+// the float4 / float2 column paths: N columns of H (ldh) and gZ1 (ldz) in whole vectors
+inline bool bwd2_vec4_ok(int32_t N, int64_t ldh, int64_t ldz, int h_align, int z_align) {
+  return N % 4 == 0 && ldh % 4 == 0 && ldz % 4 == 0 && h_align >= 16 && z_align >= 16;
+}
+inline bool bwd2_vec2_ok(int32_t N, int64_t ldh, int64_t ldz, int h_align, int z_align) {
+  return N % 2 == 0 && ldh % 2 == 0 && ldz % 2 == 0 && h_align >= 8 && z_align >= 8;
+}
+
+// What gcn_bwd2_main launches for these arguments: the instantiation and grid
+// (g) and the branches column slice 0 takes inside the kernel.  gcn_bwd2_main
+// launches from g and gcnk_gcn_bwd2_route reports all of it.
+struct Bwd2Route {
+  Bwd2Geom g;
+  bool dma, w_runs, vec_reduce;
+};
+
+bool bwd2_route(int32_t M, int32_t N, int32_t P, int64_t ldh, int64_t ldz, int h_align, int z_align, int64_t ldgs,
+                bool has_g, int64_t ldg, int64_t ldw, bool w_aligned16, Bwd2Route& r) {
+  if (!bwd2_geometry(M, N, P, bwd2_vec4_ok(N, ldh, ldz, h_align, z_align),
+                     bwd2_vec2_ok(N, ldh, ldz, h_align, z_align), r.g))
+    return false;
+  // the fields the predicates read (W stands for its alignment alone)
+  Bwd2Args a{};
+  a.ldgs = ldgs; a.ldw = ldw; a.ldg = ldg; a.M = M; a.N = N; a.P = P; a.part_ld = r.g.part_ld;
+  a.W = reinterpret_cast<const float*>(static_cast<uintptr_t>(w_aligned16 ? 16 : 4));
+  r.dma = bwd2_stage_dma(a, r.g.pm, has_g);
+  r.w_runs = bwd2_w_row_runs(a, r.g.pm);
+  r.vec_reduce = bwd2_vec_reduce(a, r.g.vec, r.g.pm);
+  return true;
+}
+
 }  // namespace
 }  // namespace gcnk
 
@@ -338,6 +395,29 @@ extern "C" int64_t gcnk_gcn_bwd2_workspace_bytes(int32_t M, int32_t N, int32_t P
   Bwd2Geom g;
   if (!bwd2_geometry(M, N, P, true, true, g)) return 0;
   return (int64_t)g.nblk * g.part_ld * 4;
+}
+
+extern "C" int gcnk_gcn_bwd2_route(int32_t M, int32_t N, int32_t P, int64_t ldh, int64_t ldz, int32_t h_align,
+                                   int32_t z_align, int64_t ldgs, int32_t has_g, int64_t ldg, int64_t ldw,
+                                   int32_t w_aligned16, int64_t* out9) {
+  const auto align_ok = [](int32_t a) { return a == 16 || a == 8 || a == 4; };
+  Bwd2Route rt;
+  if (!out9 || !align_ok(h_align) || !align_ok(z_align) || ldh < N || ldz < N || ldgs < P || ldw < P ||
+      (has_g && ldg < P) ||
+      !bwd2_route(M, N, P, ldh, ldz, h_align, z_align, ldgs, has_g != 0, ldg, ldw, w_aligned16 != 0, rt)) {
+    set_error("gcnk_gcn_bwd2_route: null out9, bad sizes (1 <= P <= 32, M, N >= 1), alignment or leading dimension");
+    return GCNK_EARG;
+  }
+  out9[0] = rt.g.vec;
+  out9[1] = rt.g.pm;
+  out9[2] = rt.g.slices;
+  out9[3] = rt.g.nblk;
+  out9[4] = rt.g.rpb;
+  out9[5] = rt.g.part_ld;
+  out9[6] = rt.dma;
+  out9[7] = rt.w_runs;
+  out9[8] = rt.vec_reduce;
+  return GCNK_OK;
 }
 
 int gcnk::side_reduce_launch(const SideReduce& side, void* stream) {
@@ -376,13 +456,17 @@ int gcnk::gcn_bwd2_main(const float* H, int64_t ldh, const float* gS, int64_t ld
     set_error("gcnk_gcn_bwd2_f32: null operand or leading dimension too small");
     return GCNK_EARG;
   }
-  const bool v4 = N % 4 == 0 && ldh % 4 == 0 && ldz % 4 == 0 && aligned16(H) && aligned16(Z);
-  const bool v2 = N % 2 == 0 && ldh % 2 == 0 && ldz % 2 == 0 && ((uintptr_t)H & 7u) == 0 && ((uintptr_t)Z & 7u) == 0;
-  Bwd2Geom g;
-  bwd2_geometry(M, N, P, v4, v2, g);
+  Bwd2Route rt;
+  bwd2_route(M, N, P, ldh, ldz, ptr_align(H), ptr_align(Z), ldgs, G != nullptr, ldg, ldw, aligned16(W), rt);
+  const Bwd2Geom& g = rt.g;
   const int64_t need = (int64_t)g.nblk * g.part_ld * 4;
   if (!workspace || workspace_bytes < need) {
     set_error("gcnk_gcn_bwd2_f32: workspace %lld B < %lld B", (long long)workspace_bytes, (long long)need);
+    return GCNK_EARG;
+  }
+  // (the float4 lane sum stores 16-B pieces to the workgroups' rows, part_ld % 4 == 0 floats apart)
+  if (!aligned16(workspace)) {
+    set_error("gcnk_gcn_bwd2_f32: workspace %p is not 16-byte aligned", workspace);
     return GCNK_EARG;
   }
   Bwd2Args a{H, ldh, gS, ldgs, W, ldw, G, ldg, M, N, P, scale, Z, ldz, (float*)workspace, g.part_ld, g.rpb, Epi{}};

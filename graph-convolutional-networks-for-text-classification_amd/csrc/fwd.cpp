@@ -126,6 +126,10 @@ extern "C" int gcnk_gcn_backward_f32(const gcnk_gcn_bwd* rec, const float* G, co
     set_error("gcnk_gcn_backward_f32: null record/operand or incomplete record");
     return GCNK_EARG;
   }
+  if (!aligned16(rec->bwd2_ws)) {   // (gcn_bwd2_main's own check, made here before the first launch)
+    set_error("gcnk_gcn_backward_f32: bwd2_ws %p is not 16-byte aligned", rec->bwd2_ws);
+    return GCNK_EARG;
+  }
   const gcnk_gcn_bwd& r = *rec;
   int rc;
   // gS2 = A-hat^T G  (autograd of layer.py:106 in gc2)

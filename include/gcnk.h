@@ -261,13 +261,35 @@ int gcnk_colsum_f32(const float* X, int64_t ldx, int32_t M, int32_t N, float* ou
  * H = gc1's output after ReLU + dropout [M x N], gS = A^T G [M x P], W = W2
  * [N x P].  gW / gb1 / gb2 are nullable (not stored).  P <= 32 (else
  * GCNK_EUNSUP).  Two launches; sums in a fixed order (bitwise reproducible).
- * Workspace: gcnk_gcn_bwd2_workspace_bytes(M, N, P).
+ * Workspace: gcnk_gcn_bwd2_workspace_bytes(M, N, P) bytes at a 16-byte aligned
+ * address (the kernel stores 16-B pieces into it; GCNK_EARG otherwise, before
+ * any launch -- gcnk_gcn_backward_f32's bwd2_ws likewise).
  * ------------------------------------------------------------------------- */
 int64_t gcnk_gcn_bwd2_workspace_bytes(int32_t M, int32_t N, int32_t P);
 int gcnk_gcn_bwd2_f32(const float* H, int64_t ldh, const float* gS, int64_t ldgs, const float* W, int64_t ldw,
                       const float* G, int64_t ldg, int32_t M, int32_t N, int32_t P, float scale,
                       float* gZ1, int64_t ldz, float* gW, float* gb1, float* gb2,
                       void* workspace, int64_t workspace_bytes, void* stream);
+/* Test aid (within ABI 13, an addition only): what gcnk_gcn_bwd2_f32 launches
+ * for these arguments and which run-time branches its kernel takes, from the
+ * host function the launch itself is made from and the predicates the kernel
+ * itself evaluates (nothing is launched here, no GPU is needed).
+ * h_align / z_align: the largest of 16, 8, 4 bytes that H's / gZ1's base pointer
+ * is aligned to; has_g: G is given (ldg is ignored otherwise); w_aligned16: W's
+ * base pointer is 16-B aligned.  out9 =
+ *   0 vec, 1 pm   the instantiation gcn_bwd2_kernel<vec, pm>: vec columns per
+ *                 lane (4, 2, 1), pm = P padded to 8, 16 or 32
+ *   2 slices      256-column slices (grid y)      3 nblk  workgroups per slice (grid x)
+ *   4 rpb         rows per workgroup              5 part_ld  floats per workspace row
+ *   6 gS / G rows staged by LDS-DMA (else by scalar loads, zero-padded to pm);
+ *     for column slice 0 -- the later slices stage gS alone, whatever ldg is
+ *   7 W's rows loaded as 16-B row runs (else guarded 4-B loads)
+ *   8 the row lanes' partials summed as float4 pieces (else per float)
+ * 1 <= P <= 32, M, N >= 1, leading dimensions as gcnk_gcn_bwd2_f32 takes them
+ * (GCNK_EARG otherwise). */
+int gcnk_gcn_bwd2_route(int32_t M, int32_t N, int32_t P, int64_t ldh, int64_t ldz, int32_t h_align,
+                        int32_t z_align, int64_t ldgs, int32_t has_g, int64_t ldg, int64_t ldw,
+                        int32_t w_aligned16, int64_t* out9);
 
 /* ---------------------------------------------------------------------------
  * Hub-factored gc1 (csrc/factor.hip; GCN.forward layer.py:164-190 through

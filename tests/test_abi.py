@@ -77,6 +77,15 @@ def test_argument_validation_without_gpu():
     rc = lib.gcnk_spmm_csr_f32(ctypes.c_void_p(16), h, ctypes.c_void_p(16), 200, 200,
                                ctypes.c_void_p(16), 200, None, 0, None, 0, 1.0, 1.0, 0, 0, None, None, 0, None, 0, 0, None)
     assert rc == _lib.EARG and b"workspace" in lib.gcnk_last_error()
+    # the fused backward's workspace: large enough but not 16-byte aligned (its kernel stores 16-B pieces)
+    need = lib.gcnk_gcn_bwd2_workspace_bytes(10, 200, 8)
+    bwd2 = [ctypes.c_void_p(16), 200, ctypes.c_void_p(16), 8, ctypes.c_void_p(16), 8, None, 0, 10, 200, 8, 1.0,
+            ctypes.c_void_p(16), 200, None, None, None]
+    for ws in (20, 24, 17):
+        rc = lib.gcnk_gcn_bwd2_f32(*bwd2, ctypes.c_void_p(ws), need, None)
+        assert rc == _lib.EARG and b"not 16-byte aligned" in lib.gcnk_last_error()
+    rc = lib.gcnk_gcn_bwd2_f32(*bwd2, ctypes.c_void_p(32), need - 4, None)
+    assert rc == _lib.EARG and b"workspace" in lib.gcnk_last_error() and b"aligned" not in lib.gcnk_last_error()
     # empty problems are no-ops that succeed without touching the device
     h, _keep = _hdr(M=0)
     assert lib.gcnk_spmm_csr_f32(ctypes.c_void_p(16), h, None, 8, 8, None, 8, None,
@@ -150,5 +159,8 @@ def test_backward_record_validation():
     assert b"incomplete record" in lib.gcnk_last_error()
     r.aTF.plan, r.gS1 = 16, 16
     assert lib.gcnk_gcn_backward_f32(ctypes.byref(r), *args) == _lib.EARG   # neither X^T plan nor dense X
+    r.bwd2_ws, r.bwd2_ws_bytes = 24, 1 << 20                                  # a misaligned bwd2 workspace
+    assert lib.gcnk_gcn_backward_f32(ctypes.byref(r), p, p, 200, p, 1.0, None, None, p, None, None) == _lib.EARG
+    assert b"not 16-byte aligned" in lib.gcnk_last_error()
     r.M = 0
     assert lib.gcnk_gcn_backward_f32(ctypes.byref(r), p, p, 200, p, 1.0, None, None, p, None, None) == _lib.EARG
