@@ -46,6 +46,14 @@ GEMM_EPI_NONE, GEMM_EPI_BIAS, GEMM_EPI_BIAS_RELU, GEMM_EPI_MASK_POS = 0, 1, 2, 5
 GEMM_ROUTE_SPLIT, GEMM_ROUTE_PTR_FETCH = 1, 2
 
 _vp, _i32, _i64, _u64, _f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float
+_f64 = ctypes.c_double
+# gcnk_adam_f32 (gcnk.h GCNK_ADAM_*)
+ADAM_MAX_TENSORS, ADAM_CHUNK, ADAM_ZERO_GRAD, ADAM_HOLD_STEP = 8, 2048, 1, 2
+
+
+class AdamTensor(ctypes.Structure):
+    """gcnk.h gcnk_adam_tensor"""
+    _fields_ = [("p", _vp), ("g", _vp), ("m", _vp), ("v", _vp), ("numel", _i64)]
 
 # name -> (restype, argtypes); every symbol include/gcnk.h declares
 SIGNATURES = {
@@ -162,6 +170,15 @@ SIGNATURES = {
     "gcnk_dense_gather_rows_f32": (ctypes.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _i64, _vp]),
     "gcnk_gcn_backward_f32": (ctypes.c_int, [_vp, _vp, _vp, _i64, _vp, _f32, _vp, _vp, _vp, _vp, _vp]),
     "gcnk_class_stats": (ctypes.c_int, [_vp, _i64, _vp, _vp, _i64, _i32, _vp, _vp]),
+    # idx, n, M, counts, stream
+    "gcnk_ce_row_counts": (ctypes.c_int, [_vp, _i64, _i32, _vp, _vp]),
+    "gcnk_ce_workspace_bytes": (_i64, [_i32, _i32]),
+    # logits, ld, M, P, target, counts, n, loss, lse, workspace, workspace_bytes, stream
+    "gcnk_ce_forward_f32": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
+    # logits, ld, M, P, target, counts, n, lse, grad_out, dlogits, ldd, stream
+    "gcnk_ce_backward_f32": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
+    # tensor table (host, AdamTensor[ntensors]), ntensors, lr, beta1, beta2, eps, weight_decay, state, flags, stream
+    "gcnk_adam_f32": (ctypes.c_int, [_vp, _i32, _f64, _f64, _f64, _f64, _f64, _vp, _i32, _vp]),
     "gcnk_edgelist_size": (ctypes.c_int, [ctypes.c_char_p, _vp, _vp]),
     "gcnk_edgelist_csr": (ctypes.c_int, [ctypes.c_char_p, _i64, _i64, _vp, _vp, _vp]),
     "gcnk_csr_to_dense": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp]),

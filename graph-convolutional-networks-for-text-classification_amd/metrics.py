@@ -17,9 +17,10 @@ from . import _lib
 from .sparse import require_device
 
 
-def class_stats(pred, targ, idx=None):
+def class_stats(pred, targ, idx=None, out=None):
     """int32 device tensor [3*nclass + 1] = TP | FP | FN | correct over the rows
-    ``idx`` (all rows when None) of logits ``pred`` [rows x nclass]."""
+    ``idx`` (all rows when None) of logits ``pred`` [rows x nclass].  ``out``: an
+    int32 device buffer of at least that length to write them to."""
     require_device(pred, "pred")
     if pred.dtype != torch.float32 or pred.dim() != 2 or pred.stride(1) != 1:
         pred = pred.float().contiguous()
@@ -28,7 +29,7 @@ def class_stats(pred, targ, idx=None):
         idx = idx.to(device=pred.device, dtype=torch.int64).contiguous()
     nclass = pred.shape[1]
     n = idx.numel() if idx is not None else pred.shape[0]
-    counts = torch.empty(3 * nclass + 1, dtype=torch.int32, device=pred.device)
+    counts = out if out is not None else torch.empty(3 * nclass + 1, dtype=torch.int32, device=pred.device)
     lib = _lib.load()
     with torch.cuda.device(pred.device):
         _lib.check(lib.gcnk_class_stats(pred.data_ptr(), pred.stride(0), targ.data_ptr(),
@@ -61,6 +62,24 @@ def evaluate(pred, targ, idx=None, num_classes=None):
     counts = class_stats(pred, targ, idx).cpu().numpy().astype(np.int64)
     n = idx.numel() if idx is not None else pred.shape[0]
     return _from_counts(counts, pred.shape[1], num_classes, n)
+
+
+def evaluate_with_loss(pred, targ, idx=None, num_classes=None):
+    """(accuracy, macro_f1, precision, recall, loss) of TopicGCNTrainer.val
+    (trainer.py:378-398: the validation loss of trainer.py:383 and the metrics,
+    two .item() sites there): the stats launch and the loss forward
+    (train.cross_entropy's kernel) on one stream, then ONE device->host copy."""
+    from . import train
+    with torch.no_grad():
+        pred, targ, rc = train._prepare(pred, targ, idx)
+        nclass = pred.shape[1]
+        buf = torch.empty(3 * nclass + 2, dtype=torch.int32, device=pred.device)   # the counts | the loss's bits
+        class_stats(pred, targ, idx, out=buf)
+        train._forward(pred, targ, rc, False, loss=buf[3 * nclass + 1:].view(torch.float32))
+        host = buf.cpu().numpy()
+    n = idx.numel() if idx is not None else pred.shape[0]
+    loss = float(host[3 * nclass + 1:].view(np.float32)[0])
+    return _from_counts(host[:3 * nclass + 1].astype(np.int64), nclass, num_classes, n) + (loss,)
 
 
 def macro_f1(pred, targ, num_classes=None):

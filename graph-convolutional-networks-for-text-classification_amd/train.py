@@ -1,0 +1,292 @@
+"""The trainer's loss and optimiser on the GPU in three launches (an opt-in swap
+outside the module drop-in, like ``metrics``):
+
+  trainer.py:307      criterion = nn.CrossEntropyLoss()     -> IndexedCrossEntropy()
+  trainer.py:308      optimizer = th.optim.Adam(...)        -> train.Adam(...)
+  trainer.py:358      criterion(logits[idx], target[idx])   -> criterion(logits, target, idx)
+
+``cross_entropy(logits, target, idx)`` is the mean cross-entropy of the rows
+``idx`` of ``logits`` with labels ``target`` (indexed like the rows of
+``logits``): ``F.cross_entropy(logits[idx], target[idx])`` without the gather
+and, in the backward, without the sort + scatter behind ``logits[idx]``.  The
+index set is turned once into per-row multiplicities (kept under the
+``derived`` rule: same tensor object, same stamp); the forward and the
+backward are then dense passes over the rows, with fixed-order float64 sums
+(bitwise reproducible).  The gradient is the dense ``dlogits`` the GCN's own
+backward takes.
+
+``Adam`` is ``torch.optim.Adam`` (amsgrad=False, maximize=False) with one
+launch per 8 tensors of a parameter group and its step count on the device, so
+a step captured in a hipGraph advances on every replay.  Checkpoints
+interchange with ``torch.optim.Adam`` (``step`` / ``exp_avg`` / ``exp_avg_sq``).
+"""
+import ctypes
+
+import torch
+
+from . import _lib, derived
+from .sparse import require_device
+
+
+def _stream(device):
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+class RowCounts:
+    """Multiplicities of an index set over M rows: ``counts`` int32 [M + 1] on the
+    device (gcnk_ce_row_counts; counts[M], the entries out of range, checked to
+    be 0 when built) and ``n`` = len(idx)."""
+    __slots__ = ("counts", "n", "pinned")
+
+    def __init__(self, counts, n):
+        self.counts, self.n, self.pinned = counts, n, False
+
+
+_COUNTS = derived.Cache(capacity=16)
+
+
+def _build_counts(idx, M, T, device):
+    i = idx.to(device=device, dtype=torch.int64).contiguous().view(-1)
+    # counted over the T <= M rows that have a label: the rows past them stay 0 (never scored, so their
+    # missing labels are never read), and counts[T] collects the entries outside [0, T)
+    counts = torch.zeros(M + 1, dtype=torch.int32, device=device)
+    with torch.cuda.device(device):
+        _lib.check(_lib.load().gcnk_ce_row_counts(i.data_ptr(), i.numel(), T, counts.data_ptr(), _stream(device)),
+                   "gcnk_ce_row_counts")
+    bad = int(counts[T].item())   # the one-time synchronising check, like a plan build
+    if bad:
+        raise IndexError(f"cross_entropy: {bad} of the {i.numel()} entries of idx are outside [0, {T})")
+    return RowCounts(counts, i.numel())
+
+
+def row_counts(idx, M, device, labels=None):
+    """The RowCounts of ``idx`` over M rows (of which the first ``labels`` have a
+    label: all by default), built on first use of this tensor object with these
+    values and reused while it is unchanged (anything but a tensor is
+    converted, and so rebuilt, on every call)."""
+    if not isinstance(idx, torch.Tensor):
+        idx = torch.as_tensor(idx)
+    T = M if labels is None else labels
+    rc = _COUNTS.get((id(idx), M, T, str(device)), (idx,), _build_counts, idx, M, T, device)
+    if not rc.pinned and torch.cuda.is_current_stream_capturing():
+        rc.pinned = True   # a captured graph points into counts
+    return rc
+
+
+def _forward(logits, target, rc, want_lse, loss=None):
+    """Launch the loss forward on the current stream: (loss [1] fp32, lse [M] or None)."""
+    M, P = logits.shape
+    dev = logits.device
+    lib = _lib.load()
+    if loss is None:
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+    if M == 0:
+        return loss.fill_(float("nan")), None
+    lse = torch.empty(M, dtype=torch.float32, device=dev) if want_lse else None
+    nb = lib.gcnk_ce_workspace_bytes(M, P)
+    if nb < 0:
+        _lib.check(int(nb), "gcnk_ce_workspace_bytes")
+    ws = torch.empty(max(1, nb // 8), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.gcnk_ce_forward_f32(
+            logits.data_ptr(), logits.stride(0), M, P, target.data_ptr(),
+            rc.counts.data_ptr() if rc is not None else None, rc.n if rc is not None else M,
+            loss.data_ptr(), lse.data_ptr() if lse is not None else None, ws.data_ptr(), nb, _stream(dev)),
+            "gcnk_ce_forward_f32")
+    return loss, lse
+
+
+class _CrossEntropyFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, target, rc, need):
+        loss, lse = _forward(logits, target, rc, need)
+        if need:
+            ctx.save_for_backward(logits, target, lse)
+            ctx.rc = rc
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        logits, target, lse = ctx.saved_tensors
+        rc = ctx.rc
+        M, P = logits.shape
+        dev = logits.device
+        dlogits = torch.empty(M, P, dtype=torch.float32, device=dev)
+        if M == 0:
+            return dlogits, None, None, None
+        g = grad_out.to(device=dev, dtype=torch.float32).contiguous()
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().gcnk_ce_backward_f32(
+                logits.data_ptr(), logits.stride(0), M, P, target.data_ptr(),
+                rc.counts.data_ptr() if rc is not None else None, rc.n if rc is not None else M,
+                lse.data_ptr(), g.data_ptr(), dlogits.data_ptr(), P, _stream(dev)),
+                "gcnk_ce_backward_f32")
+        return dlogits, None, None, None
+
+
+def _prepare(logits, target, idx):
+    require_device(logits, "logits")
+    if logits.dim() != 2:
+        raise ValueError(f"cross_entropy: logits must be [rows x classes] (got {tuple(logits.shape)})")
+    if logits.dtype != torch.float32 or logits.stride(1) != 1 or logits.stride(0) < logits.shape[1]:
+        logits = logits.float().contiguous()
+    target = target.to(device=logits.device, dtype=torch.int64).contiguous()
+    M, T = logits.shape[0], target.numel()
+    if T > M or (T < M and idx is None):
+        raise ValueError(f"cross_entropy: target has {T} labels for {M} rows of logits (target is indexed like the "
+                         "rows of logits, not like idx; it may be shorter only when idx names labelled rows)")
+    rc = row_counts(idx, M, logits.device, T) if idx is not None else None
+    return logits, target, rc
+
+
+def cross_entropy(logits, target, idx=None):
+    """Mean cross-entropy of the rows ``idx`` (all rows when None; duplicates
+    count as often as they occur) of ``logits`` [rows x classes] against
+    ``target`` (labels of the rows; as in the reference it may stop short of
+    the last rows when ``idx`` names none of those): F.cross_entropy(logits[idx],
+    target[idx]) of trainer.py:358, and under no_grad the validation loss of trainer.py:383."""
+    logits, target, rc = _prepare(logits, target, idx)
+    # lse is kept only when a backward can follow (grad mode is off inside Function.forward: decided here)
+    return _CrossEntropyFn.apply(logits, target, rc, torch.is_grad_enabled() and logits.requires_grad)
+
+
+class IndexedCrossEntropy(torch.nn.Module):
+    """nn.CrossEntropyLoss of trainer.py:307 taking the node set as an argument:
+    ``criterion(logits, target, idx)`` for ``criterion(logits[idx], target[idx])``."""
+
+    def forward(self, logits, target, idx=None):
+        return cross_entropy(logits, target, idx)
+
+
+class Adam(torch.optim.Optimizer):
+    """torch.optim.Adam(params, lr, betas, eps, weight_decay) of trainer.py:308 on
+    gcnk_adam_f32: one launch per 8 tensors of a parameter group, the step count
+    on the device (one word shared by all parameters).
+    ``zero_grad_in_step``: the step also zeroes the gradients it read (no
+    zero_grad() fills; gradients must then be kept, zero_grad(set_to_none=False),
+    or not zeroed by the caller at all)."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, zero_grad_in_step=False,
+                 amsgrad=False, maximize=False, foreach=None, fused=None, capturable=None, differentiable=False):
+        if amsgrad or maximize or differentiable:
+            raise ValueError("train.Adam implements amsgrad=False, maximize=False, differentiable=False only")
+        if foreach or fused:
+            raise ValueError("train.Adam is its own single-launch implementation: foreach / fused do not apply")
+        if isinstance(lr, torch.Tensor):
+            raise ValueError("train.Adam takes lr as a number")
+        if not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 <= eps:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        if not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0:
+            raise ValueError(f"Invalid beta parameters: {betas}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay))
+        self.zero_grad_in_step = bool(zero_grad_in_step)
+        self._step_word = None    # int32 [4] on the device: steps taken, arrival counter, padding
+        self._with_grad = None    # ids of the parameters that carried gradients at the first step
+        self._tables = {}         # (group, launch) -> (pointers, AdamTensor array)
+
+    # -- the device step word -------------------------------------------------------------------
+    def _word(self, device):
+        if self._step_word is None:
+            self._step_word = torch.zeros(4, dtype=torch.int32, device=device)
+        elif self._step_word.device != device:
+            raise RuntimeError("train.Adam: all parameters must be on one device (one shared step word)")
+        return self._step_word
+
+    @property
+    def steps(self):
+        """Steps taken (reads the device word: synchronises)."""
+        return 0 if self._step_word is None else int(self._step_word[0].item())
+
+    def _state_of(self, p):
+        st = self.state[p]
+        if "exp_avg" not in st:
+            st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+            st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+        return st
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        work = []
+        for gi, group in enumerate(self.param_groups):
+            ps = [p for p in group["params"] if p.grad is not None]
+            for p in ps:
+                require_device(p, "parameter")
+                g = p.grad
+                if (p.dtype != torch.float32 or g.dtype != torch.float32 or g.layout != torch.strided
+                        or not p.is_contiguous() or not g.is_contiguous()):
+                    raise RuntimeError("train.Adam: parameters and gradients must be contiguous dense fp32 tensors")
+            if ps:
+                work.append((gi, group, ps))
+        ids = tuple(id(p) for _, _, ps in work for p in ps)
+        if self._with_grad is None:
+            self._with_grad = ids
+        elif ids != self._with_grad:
+            raise RuntimeError("train.Adam: the set of parameters that carry gradients changed after the first step "
+                               "(they share one step word)")
+        if not ids:
+            return loss
+        dev = work[0][2][0].device
+        word = self._word(dev)
+        lib = _lib.load()
+        launches = [(gi, group, ps[i:i + _lib.ADAM_MAX_TENSORS])
+                    for gi, group, ps in work for i in range(0, len(ps), _lib.ADAM_MAX_TENSORS)]
+        zero = _lib.ADAM_ZERO_GRAD if self.zero_grad_in_step else 0
+        with torch.cuda.device(dev):
+            stream = _stream(dev)
+            for li, (gi, group, ps) in enumerate(launches):
+                sts = [self._state_of(p) for p in ps]
+                ptrs = tuple(x for p, st in zip(ps, sts)
+                             for x in (p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(),
+                                       st["exp_avg_sq"].data_ptr()))
+                cached = self._tables.get(li)
+                if cached is None or cached[0] != ptrs:   # rebuilt only when a pointer changed
+                    tab = (_lib.AdamTensor * len(ps))()
+                    for k, p in enumerate(ps):
+                        tab[k].p, tab[k].g, tab[k].m, tab[k].v = ptrs[4 * k:4 * k + 4]
+                        tab[k].numel = p.numel()
+                    cached = self._tables[li] = (ptrs, tab)
+                b1, b2 = group["betas"]
+                hold = _lib.ADAM_HOLD_STEP if li + 1 < len(launches) else 0
+                _lib.check(lib.gcnk_adam_f32(cached[1], len(ps), float(group["lr"]), float(b1), float(b2),
+                                             float(group["eps"]), float(group["weight_decay"]), word.data_ptr(),
+                                             zero | hold, stream), "gcnk_adam_f32")
+        return loss
+
+    # -- checkpoints in torch.optim.Adam's keys -------------------------------------------------
+    def state_dict(self):
+        sd = super().state_dict()
+        if sd["state"]:   # (the per-parameter dicts are the optimiser's own: copied, not extended)
+            t = float(self.steps)
+            sd["state"] = {k: dict(st, step=torch.tensor(t, dtype=torch.float32)) for k, st in sd["state"].items()}
+        sd["param_groups"] = [dict(g, amsgrad=False, maximize=False, foreach=None, capturable=False,
+                                   differentiable=False, fused=None) for g in sd["param_groups"]]
+        return sd
+
+    def load_state_dict(self, state_dict):
+        steps = {float(st["step"]) for st in state_dict["state"].values() if "step" in st}
+        if len(steps) > 1:
+            raise ValueError(f"train.Adam: parameters at different steps {sorted(steps)} (one shared step word)")
+        if any(g.get("amsgrad") or g.get("maximize") for g in state_dict["param_groups"]):
+            raise ValueError("train.Adam implements amsgrad=False, maximize=False only")
+        super().load_state_dict(state_dict)
+        keep = set(self.defaults)
+        for g in self.param_groups:
+            for k in [k for k in g if k not in keep and k != "params"]:
+                del g[k]
+        dev = None
+        for p, st in self.state.items():
+            st.pop("step", None)
+            for k in ("exp_avg", "exp_avg_sq"):
+                st[k] = st[k].to(device=p.device, dtype=torch.float32).contiguous()
+            dev = p.device
+        self._tables.clear()
+        if dev is not None:
+            self._word(dev).copy_(torch.tensor([int(steps.pop()) if steps else 0, 0, 0, 0], dtype=torch.int32))

@@ -22,6 +22,8 @@
  *   utils.py:25-109  accuracy / macro_f1 counts              -> gcnk_class_stats (one launch, no per-class syncs)
  *   trainer.py:98-148 edge list -> symmetric adjacency        -> gcnk_edgelist_size / _csr (host, no networkx)
  *   layer.py:185 th.dropout keep-mask draw (CPU generator)    -> gcnk_bernoulli_mt19937 (host, same stream)
+ *   trainer.py:307, 358-361, 383-384 CrossEntropyLoss on logits[idx] -> gcnk_ce_forward_f32 / gcnk_ce_backward_f32
+ *   trainer.py:308, 359, 362 th.optim.Adam step (and zero_grad)   -> gcnk_adam_f32 (one launch per 8 tensors)
  *
  * Conventions
  *   - All pointers are DEVICE pointers unless a parameter says "host".
@@ -599,6 +601,97 @@ int gcnk_sym_normalize(const int32_t* rowptr, const int32_t* colind, const float
  * ------------------------------------------------------------------------- */
 int gcnk_class_stats(const float* logits, int64_t ld, const int64_t* target, const int64_t* idx, int64_t n,
                      int32_t nclass, int32_t* counts, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Mean cross-entropy over a node set (csrc/loss.hip; additions within ABI 13):
+ *   trainer.py:307      criterion = nn.CrossEntropyLoss()
+ *   trainer.py:358-361  loss = criterion(logits[train_lst], target[train_lst]); loss.backward()
+ *   trainer.py:383-384  the validation loss (forward only, lse = NULL)
+ * without materialising logits[idx] and without the sort + scatter ATen's
+ * indexing backward runs: the index set is turned once into row multiplicities,
+ * and both passes are dense over the M rows of logits [M x P] (ld).
+ *
+ *   gcnk_ce_row_counts: counts[r] (zeroed by the call) = how often row r occurs
+ *     in idx[0 .. n), r < M; counts[M] = entries outside [0, M), which are
+ *     skipped, never dereferenced.  Integer atomics: exact.
+ *   gcnk_ce_forward_f32: for every row r with counts[r] > 0 (every row, once,
+ *     when counts is NULL; n is then M)
+ *         lse_r = max_j z_rj + log sum_j exp(z_rj - max_j z_rj)        (fp32)
+ *         l_r   = lse_r - z[r, target[r]]                              (float64)
+ *         *loss = fp32( (sum_r counts[r] * l_r) / n )
+ *     the sum in float64 in a fixed order (a fixed tree over a workgroup's rows,
+ *     the workgroups' partials in index order): bitwise reproducible, no float
+ *     atomics.  lse[r] is stored for the scored rows when lse != NULL (a
+ *     backward needs it); target[r] is read for scored rows only.  A scored row whose target is outside [0, P) makes the
+ *     loss NaN; nothing outside the row is read.  1 <= P <= 1024 (GCNK_EARG
+ *     otherwise); workspace: gcnk_ce_workspace_bytes(M, P) bytes, 8-B aligned.
+ *     Two launches.  M == 0: nothing is launched or written.
+ *   gcnk_ce_backward_f32: the whole dense dlogits [M x P] (ldd) in one launch:
+ *         counts[r] == 0:  +0.0
+ *         otherwise:       g * fp32(counts[r] / n) * (exp(z_rj - lse_r) - [j == target[r]])
+ *     g = *grad_out (a device scalar; 1 when NULL).  Columns P .. ldd - 1 are
+ *     never written.  No zero-fill launch, no host sync.
+ * ------------------------------------------------------------------------- */
+int gcnk_ce_row_counts(const int64_t* idx, int64_t n, int32_t M, int32_t* counts, void* stream);
+int64_t gcnk_ce_workspace_bytes(int32_t M, int32_t P);
+int gcnk_ce_forward_f32(const float* logits, int64_t ld, int32_t M, int32_t P, const int64_t* target,
+                        const int32_t* counts, int64_t n, float* loss, float* lse, void* workspace,
+                        int64_t workspace_bytes, void* stream);
+int gcnk_ce_backward_f32(const float* logits, int64_t ld, int32_t M, int32_t P, const int64_t* target,
+                         const int32_t* counts, int64_t n, const float* lse, const float* grad_out,
+                         float* dlogits, int64_t ldd, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Adam step (csrc/adam.hip; an addition within ABI 13): trainer.py:308
+ * optimizer = th.optim.Adam(...), trainer.py:362 optimizer.step() -- torch's
+ * Adam with amsgrad = False, maximize = False -- for up to
+ * GCNK_ADAM_MAX_TENSORS contiguous fp32 tensors {p, g, m, v, numel} in ONE
+ * launch (the table travels in the kernel's arguments; more tensors take
+ * further calls).  With t = state[0] + 1, per element, in fp32 unless said:
+ *     g' = fma(wd, p, g)                                  wd   = fp32(weight_decay)
+ *     m' = fma(omb1, g' - m, m)                           omb1 = fp32(1 - beta1)
+ *     v' = fma(b2, v, (omb2 * g') * g')                   b2   = fp32(beta2), omb2 = fp32(1 - beta2)
+ *     p' = p - (step * m') / (sqrt(v') / sbc2 + eps)      step = fp32(lr / (1 - beta1^t))
+ *                                                         sbc2 = fp32(sqrt(1 - beta2^t))
+ * i.e. m' = beta1 m + (1 - beta1) g', v' = beta2 v + (1 - beta2) g'^2 and
+ * p' = p - lr / (1 - beta1^t) * m' / (sqrt(v') / sqrt(1 - beta2^t) + eps), with
+ * the operations in the order torch's step takes them (lerp_, mul_ + addcmul_,
+ * sqrt / div / add_, addcdiv_).  1 - beta, beta^t (pow), step and sbc2 are
+ * formed in float64 and rounded once (the last two on the device from the step
+ * word, once per workgroup); sqrt and the divisions are correctly rounded.
+ * The step word: state[0] is the number of steps taken, on the DEVICE, so a
+ * step captured in a hipGraph advances on every replay.  Every workgroup reads
+ * it at entry; the word is advanced only after all workgroups of the launch
+ * have read it, by the last to arrive at the counter state[1] (zero on entry,
+ * left zero on return), so a workgroup that starts late never sees t + 1.
+ * state: int32[2], used by one call at a time.
+ * flags:
+ *   GCNK_ADAM_ZERO_GRAD  also store +0.0 to g after reading it (trainer.py:359
+ *                        optimizer.zero_grad(): a captured step needs no fills)
+ *   GCNK_ADAM_HOLD_STEP  read the step word, do not advance it: for every call
+ *                        of one optimiser step over more than 8 tensors but the last
+ * GCNK_EARG (on the host, before any launch) for a NULL table, buffer or state,
+ * numel < 0, ntensors outside [0, 8], beta outside [0, 1), lr, eps or
+ * weight_decay < 0.  ntensors == 0 succeeds and does nothing.
+ * Work is cut into chunks of GCNK_ADAM_CHUNK elements, one workgroup each:
+ * 16-B accesses where a tensor's four buffers share their offset from a 16-B
+ * boundary (a scalar head of up to 3 elements, a scalar ragged tail), scalar
+ * otherwise.  28 B of traffic per element: an HBM-bound stream, to be judged
+ * against gcnk_stream_copy_f32's rate.
+ * ------------------------------------------------------------------------- */
+#define GCNK_ADAM_MAX_TENSORS 8
+#define GCNK_ADAM_CHUNK 2048
+#define GCNK_ADAM_ZERO_GRAD 1
+#define GCNK_ADAM_HOLD_STEP 2
+typedef struct gcnk_adam_tensor {
+  float* p;        /* parameter */
+  float* g;        /* its gradient */
+  float* m;        /* exp_avg */
+  float* v;        /* exp_avg_sq */
+  int64_t numel;
+} gcnk_adam_tensor;
+int gcnk_adam_f32(const gcnk_adam_tensor* t /* host */, int32_t ntensors, double lr, double beta1, double beta2,
+                  double eps, double weight_decay, int32_t* state, int32_t flags, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Weighted edge-list loader (HOST pointers; no device work): the graph file
