@@ -55,6 +55,22 @@ class AdamTensor(ctypes.Structure):
     """gcnk.h gcnk_adam_tensor"""
     _fields_ = [("p", _vp), ("g", _vp), ("m", _vp), ("v", _vp), ("numel", _i64)]
 
+
+class EpochState(ctypes.Structure):
+    """gcnk.h gcnk_epoch_state (32 bytes on the device)"""
+    _fields_ = [("epoch", _i32), ("stopped", _i32), ("stop_epoch", _i32), ("counter", _i32), ("best", _f64),
+                ("arrivals", _i32), ("reserved", _i32)]
+
+
+# gcnk_epoch_tail_f32's stop reasons (gcnk.h GCNK_EPOCH_STOP_*)
+EPOCH_STOP_PATIENCE, EPOCH_STOP_MAX_EPOCH = 1, 2
+
+
+def epoch_row_words(nclass):
+    """gcnk.h GCNK_EPOCH_ROW_WORDS: train_loss | val_loss | TP | FP | FN | correct"""
+    return 3 * nclass + 3
+
+
 # name -> (restype, argtypes); every symbol include/gcnk.h declares
 SIGNATURES = {
     "gcnk_abi_version": (ctypes.c_int, []),
@@ -179,6 +195,13 @@ SIGNATURES = {
     "gcnk_ce_backward_f32": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
     # tensor table (host, AdamTensor[ntensors]), ntensors, lr, beta1, beta2, eps, weight_decay, state, flags, stream
     "gcnk_adam_f32": (ctypes.c_int, [_vp, _i32, _f64, _f64, _f64, _f64, _f64, _vp, _i32, _vp]),
+    # gcnk_adam_f32's arguments, then gate before stream
+    "gcnk_adam_gated_f32": (ctypes.c_int, [_vp, _i32, _f64, _f64, _f64, _f64, _f64, _vp, _i32, _vp, _vp]),
+    "gcnk_epoch_tail_workspace_bytes": (_i64, [_i32, _i32]),
+    # logits, ld, M, P, target, counts, n, train_loss, state, history, max_epoch, patience, delta, workspace,
+    # workspace_bytes, stream
+    "gcnk_epoch_tail_f32": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _f64,
+                                           _vp, _i64, _vp]),
     "gcnk_edgelist_size": (ctypes.c_int, [ctypes.c_char_p, _vp, _vp]),
     "gcnk_edgelist_csr": (ctypes.c_int, [ctypes.c_char_p, _i64, _i64, _vp, _vp, _vp]),
     "gcnk_csr_to_dense": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp]),

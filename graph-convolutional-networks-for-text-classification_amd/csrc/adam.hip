@@ -47,8 +47,9 @@ __device__ __forceinline__ void adam_elem(const Coef& k, float& p, float g, floa
 
 static_assert(kChunk == 2 * 4 * 256, "a workgroup of 256 threads holds a chunk as two float4 pieces per thread");
 
-__global__ void __launch_bounds__(256) adam_kernel(const AdamArgs a, int32_t* __restrict__ state) {
-  __shared__ float s_step[2];
+__global__ void __launch_bounds__(256) adam_kernel(const AdamArgs a, int32_t* __restrict__ state,
+                                                   const int32_t* __restrict__ gate) {
+  __shared__ float s_step[3];   // the two step factors; the gate word
   const int tid = threadIdx.x;
   const int32_t blk = blockIdx.x;
   // The step word: read at entry by one lane (the load is in flight while the chunk's own loads are
@@ -56,8 +57,14 @@ __global__ void __launch_bounds__(256) adam_kernel(const AdamArgs a, int32_t* __
   // the last of the launch's workgroups to arrive knows every other has read t, and only then stores
   // t + 1 (and leaves the counter zero for the next call): a workgroup that starts late still reads t.
   // Nothing else passes between workgroups.
-  int32_t t = 0;
-  if (tid == 0) t = __hip_atomic_load(state, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  // The gate (gcnk_adam_gated_f32): a word an earlier launch on the stream wrote, so every workgroup of
+  // this launch reads the same value; read by the same lane and broadcast with the step factors.  Closed,
+  // the workgroup returns behind the barrier having stored nothing and counted itself in nowhere.
+  int32_t t = 0, closed = 0;
+  if (tid == 0) {
+    t = __hip_atomic_load(state, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (gate) closed = __hip_atomic_load(gate, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
 
   // (tensor, chunk) of this workgroup: selected without indexing the argument block dynamically
   float *p = a.t[0].p, *g = a.t[0].g, *m = a.t[0].m, *v = a.t[0].v;
@@ -97,8 +104,10 @@ __global__ void __launch_bounds__(256) adam_kernel(const AdamArgs a, int32_t* __
     const double tn = (double)(t + 1);
     s_step[0] = (float)(a.lr / (1.0 - pow(a.beta1, tn)));
     s_step[1] = (float)sqrt(1.0 - pow(a.beta2, tn));
+    s_step[2] = __int_as_float(closed);
   }
   __syncthreads();
+  if (__float_as_int(s_step[2]) != 0) return;
   if (tid == 0 && a.advance) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // t has been read before this workgroup is counted in
     const int32_t arrived = __hip_atomic_fetch_add(state + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -150,21 +159,22 @@ __global__ void __launch_bounds__(256) adam_kernel(const AdamArgs a, int32_t* __
 
 using namespace gcnk;
 
-extern "C" int gcnk_adam_f32(const gcnk_adam_tensor* t, int32_t ntensors, double lr, double beta1, double beta2,
-                             double eps, double weight_decay, int32_t* state, int32_t flags, void* stream) {
+static int adam_launch(const char* who, const gcnk_adam_tensor* t, int32_t ntensors, double lr, double beta1,
+                       double beta2, double eps, double weight_decay, int32_t* state, int32_t flags,
+                       const int32_t* gate, void* stream) {
   if (ntensors < 0 || ntensors > kMaxTensors) {
-    set_error("gcnk_adam_f32: bad argument (ntensors=%d, at most %d per call)", ntensors, kMaxTensors);
+    set_error("%s: bad argument (ntensors=%d, at most %d per call)", who, ntensors, kMaxTensors);
     return GCNK_EARG;
   }
   if (!(lr >= 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0) ||
       !(weight_decay >= 0.0) || (flags & ~(GCNK_ADAM_ZERO_GRAD | GCNK_ADAM_HOLD_STEP))) {
-    set_error("gcnk_adam_f32: bad argument (lr=%g beta1=%g beta2=%g eps=%g weight_decay=%g flags=%d; lr, eps, weight_decay >= 0, "
-              "0 <= beta < 1)", lr, beta1, beta2, eps, weight_decay, flags);
+    set_error("%s: bad argument (lr=%g beta1=%g beta2=%g eps=%g weight_decay=%g flags=%d; lr, eps, weight_decay >= 0, "
+              "0 <= beta < 1)", who, lr, beta1, beta2, eps, weight_decay, flags);
     return GCNK_EARG;
   }
   if (ntensors == 0) return GCNK_OK;
   if (!t || !state) {
-    set_error("gcnk_adam_f32: null tensor table or state");
+    set_error("%s: null tensor table or state", who);
     return GCNK_EARG;
   }
   AdamArgs a = {};
@@ -172,7 +182,7 @@ extern "C" int gcnk_adam_f32(const gcnk_adam_tensor* t, int32_t ntensors, double
   for (int i = 0; i < ntensors; ++i) {
     const gcnk_adam_tensor& x = t[i];
     if (x.numel < 0 || (x.numel > 0 && (!x.p || !x.g || !x.m || !x.v))) {
-      set_error("gcnk_adam_f32: tensor %d: null buffer or numel < 0 (numel=%lld)", i, (long long)x.numel);
+      set_error("%s: tensor %d: null buffer or numel < 0 (numel=%lld)", who, i, (long long)x.numel);
       return GCNK_EARG;
     }
     const uintptr_t off = reinterpret_cast<uintptr_t>(x.p) & 15u;
@@ -184,7 +194,7 @@ extern "C" int gcnk_adam_f32(const gcnk_adam_tensor* t, int32_t ntensors, double
     const int64_t body = same ? (x.numel > a.head[i] ? x.numel - a.head[i] : 0) : x.numel;
     chunks += x.numel > 0 ? (body + kChunk - 1) / kChunk + (body == 0 ? 1 : 0) : 0;
     if (chunks > INT32_MAX) {
-      set_error("gcnk_adam_f32: more than 2^31 chunks in one call");
+      set_error("%s: more than 2^31 chunks in one call", who);
       return GCNK_EARG;
     }
   }
@@ -201,6 +211,18 @@ extern "C" int gcnk_adam_f32(const gcnk_adam_tensor* t, int32_t ntensors, double
   a.advance = (flags & GCNK_ADAM_HOLD_STEP) ? 0 : 1;
   if (chunks == 0 && !a.advance) return GCNK_OK;
   hipLaunchKernelGGL(adam_kernel, dim3((unsigned)(chunks > 0 ? chunks : 1)), dim3(256), 0, (hipStream_t)stream, a,
-                     state);
+                     state, gate);
   return launch_check("adam_kernel");
+}
+
+extern "C" int gcnk_adam_f32(const gcnk_adam_tensor* t, int32_t ntensors, double lr, double beta1, double beta2,
+                             double eps, double weight_decay, int32_t* state, int32_t flags, void* stream) {
+  return adam_launch("gcnk_adam_f32", t, ntensors, lr, beta1, beta2, eps, weight_decay, state, flags, nullptr, stream);
+}
+
+extern "C" int gcnk_adam_gated_f32(const gcnk_adam_tensor* t, int32_t ntensors, double lr, double beta1, double beta2,
+                                   double eps, double weight_decay, int32_t* state, int32_t flags,
+                                   const int32_t* gate, void* stream) {
+  return adam_launch("gcnk_adam_gated_f32", t, ntensors, lr, beta1, beta2, eps, weight_decay, state, flags, gate,
+                     stream);
 }

@@ -14,14 +14,12 @@
 // columns.  Row sums meet in a shuffle tree of fixed shape; the loss is summed in float64:
 // a fixed tree over a workgroup's rows, the workgroups' partials in index order by a second
 // launch, one rounding to fp32.  No float atomics: bitwise reproducible.
-#include "gcnk_common.h"
-
-#include <cmath>
+#include "ce_row.h"
 
 namespace gcnk {
 namespace {
 
-constexpr int kMaxClasses = 1024;   // gcnk_class_stats's limit
+using namespace ce;   // the row arithmetic, shared with epoch.hip
 
 __global__ void __launch_bounds__(256)
 ce_row_counts_kernel(const int64_t* __restrict__ idx, int64_t n, int32_t M, int32_t* __restrict__ counts) {
@@ -31,42 +29,12 @@ ce_row_counts_kernel(const int64_t* __restrict__ idx, int64_t n, int32_t M, int3
   atomicAdd(counts + (r >= 0 && r < M ? r : (int64_t)M), 1);   // out of range: counted in counts[M], never a row
 }
 
-// four consecutive columns c .. c + 3 of row z; columns >= P read as `fill`
-template <bool VEC>
-__device__ __forceinline__ void load4(const float* __restrict__ z, int32_t c, int32_t P, float fill, float (&v)[4]) {
-  if constexpr (VEC) {   // P % 4 == 0, 16-B aligned rows
-    if (c < P) {
-      const float4 t = *reinterpret_cast<const float4*>(z + c);
-      v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-    } else {
-      v[0] = v[1] = v[2] = v[3] = fill;
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = c + j < P ? z[c + j] : fill;
-  }
-}
-
-template <int LPR>
-__device__ __forceinline__ float group_max(float v) {
-#pragma unroll
-  for (int off = LPR / 2; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-  return v;
-}
-template <int LPR>
-__device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-  for (int off = LPR / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 template <int LPR, bool VEC>
 __global__ void __launch_bounds__(256)
 ce_forward_kernel(const float* __restrict__ logits, int64_t ld, int32_t M, int32_t P,
                   const int64_t* __restrict__ target, const int32_t* __restrict__ counts,
                   float* __restrict__ lse_out, double* __restrict__ part) {
   constexpr int RPB = 256 / LPR;   // rows per workgroup
-  constexpr int STEP = 4 * LPR;    // columns per pass
   __shared__ double s_w[RPB];
   const int g = threadIdx.x / LPR, lg = threadIdx.x % LPR;
   const int64_t r = (int64_t)blockIdx.x * RPB + g;
@@ -74,45 +42,19 @@ ce_forward_kernel(const float* __restrict__ logits, int64_t ld, int32_t M, int32
   if (r < M) cnt = counts ? counts[r] : 1;
   const bool scored = cnt > 0;          // uniform over the lane group
   const float* z = logits + (scored ? r : 0) * ld;
-  const float ninf = -INFINITY;
-
-  // every lane takes part in the shuffles; an unscored group computes on `fill` and is dropped
-  float v[4];
-  if (scored) load4<VEC>(z, 4 * lg, P, ninf, v); else v[0] = v[1] = v[2] = v[3] = 0.f;
-  float mx = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
-  if (LPR == 64 && scored)
-    for (int32_t c = 4 * lg + STEP; c < P; c += STEP) {
-      float u[4];
-      load4<VEC>(z, c, P, ninf, u);
-      mx = fmaxf(mx, fmaxf(fmaxf(u[0], u[1]), fmaxf(u[2], u[3])));
-    }
-  mx = group_max<LPR>(mx);
-  float s = (expf(v[0] - mx) + expf(v[1] - mx)) + (expf(v[2] - mx) + expf(v[3] - mx));
-  if (LPR == 64 && scored)
-    for (int32_t c = 4 * lg + STEP; c < P; c += STEP) {
-      float u[4];
-      load4<VEC>(z, c, P, ninf, u);
-      s += (expf(u[0] - mx) + expf(u[1] - mx)) + (expf(u[2] - mx) + expf(u[3] - mx));
-    }
-  s = group_sum<LPR>(s);
+  float v[4], mx, s;
+  row_max_sum<LPR, VEC>(z, lg, P, scored, v, mx, s);
 
   if (lg == 0) {
     double w = 0.0;
     if (scored) {
-      const float lse = mx + logf(s);
-      const int64_t t = target[r];
-      const float zt = t >= 0 && t < P ? z[t] : NAN;   // a target outside [0, P): NaN loss, nothing read
-      w = (double)cnt * ((double)lse - (double)zt);
+      const float lse = row_lse(mx, s);
+      w = row_weighted_loss(z, P, target[r], cnt, lse);
       if (lse_out) lse_out[r] = lse;
     }
     s_w[g] = w;
   }
-  __syncthreads();
-#pragma unroll
-  for (int st = RPB / 2; st > 0; st >>= 1) {   // fixed tree over the workgroup's rows
-    if ((int)threadIdx.x < st) s_w[threadIdx.x] += s_w[threadIdx.x + st];
-    __syncthreads();
-  }
+  block_tree<RPB>(s_w);
   if (threadIdx.x == 0) part[blockIdx.x] = s_w[0];
 }
 
@@ -121,16 +63,10 @@ ce_forward_kernel(const float* __restrict__ logits, int64_t ld, int32_t M, int32
 __global__ void __launch_bounds__(256)
 ce_reduce_kernel(const double* __restrict__ part, int32_t nblk, int64_t n, float* __restrict__ loss) {
   __shared__ double s[256];
-  const int32_t run = (nblk + 255) / 256;
-  const int32_t b0 = threadIdx.x * run, b1 = min(b0 + run, nblk);
-  double acc = 0.0;
-  for (int32_t b = b0; b < b1; ++b) acc += part[b];
-  s[threadIdx.x] = acc;
+  s[threadIdx.x] = partial_run(nblk, [&](int32_t b) { return part[b]; });
   __syncthreads();
   if (threadIdx.x != 0) return;
-  double t = s[0];
-  for (int i = 1; i < 256; ++i) t += s[i];
-  *loss = (float)(t / (double)n);
+  *loss = mean_of_runs(s, n);
 }
 
 template <int LPR, bool VEC>
@@ -173,17 +109,7 @@ ce_backward_kernel(const float* __restrict__ logits, int64_t ld, int32_t M, int3
   }
 }
 
-// lanes per row: the smallest power of two covering ceil(P / 4) float4 pieces, at most 64
-inline int lanes_per_row(int32_t P) {
-  const int pieces = (P + 3) / 4;
-  int l = 1;
-  while (l < pieces && l < 64) l <<= 1;
-  return l;
-}
-inline int32_t ce_blocks(int32_t M, int32_t P) {
-  const int rpb = 256 / lanes_per_row(P);
-  return (int32_t)(((int64_t)M + rpb - 1) / rpb);
-}
+inline int32_t ce_blocks(int32_t M, int32_t P) { return blocks(M, P); }
 
 template <bool VEC>
 void launch_forward(int lpr, dim3 grid, hipStream_t s, const float* logits, int64_t ld, int32_t M, int32_t P,

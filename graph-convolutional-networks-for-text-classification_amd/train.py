@@ -19,9 +19,18 @@ backward takes.
 launch per 8 tensors of a parameter group and its step count on the device, so
 a step captured in a hipGraph advances on every replay.  Checkpoints
 interchange with ``torch.optim.Adam`` (``step`` / ``exp_avg`` / ``exp_avg_sq``).
+
+``fit`` is the loop itself (trainer.py:349-376) at replay speed: the epoch's
+bookkeeping -- validation loss and class counts, the early-stopping decision,
+the history row -- is one launch on the device (``EpochLog``,
+gcnk_epoch_tail_f32), the optimiser step is gated by that launch's stop word
+(gcnk_adam_gated_f32), and one epoch is captured in a hipGraph and replayed;
+the host looks at the stop word once per ``poll_every`` epochs.
 """
+import collections
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _lib, derived
@@ -164,10 +173,15 @@ class Adam(torch.optim.Optimizer):
     on the device (one word shared by all parameters).
     ``zero_grad_in_step``: the step also zeroes the gradients it read (no
     zero_grad() fills; gradients must then be kept, zero_grad(set_to_none=False),
-    or not zeroed by the caller at all)."""
+    or not zeroed by the caller at all).
+    ``gate`` (settable): an int32 device word, written earlier on the stream
+    (``EpochLog.stop_word``); while it is non-zero a step changes nothing at
+    all (gcnk_adam_gated_f32), so steps queued past the stopping epoch are
+    no-ops."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, zero_grad_in_step=False,
-                 amsgrad=False, maximize=False, foreach=None, fused=None, capturable=None, differentiable=False):
+                 amsgrad=False, maximize=False, foreach=None, fused=None, capturable=None, differentiable=False,
+                 gate=None):
         if amsgrad or maximize or differentiable:
             raise ValueError("train.Adam implements amsgrad=False, maximize=False, differentiable=False only")
         if foreach or fused:
@@ -184,6 +198,7 @@ class Adam(torch.optim.Optimizer):
             raise ValueError(f"Invalid weight_decay value: {weight_decay}")
         super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay))
         self.zero_grad_in_step = bool(zero_grad_in_step)
+        self.gate = gate
         self._step_word = None    # int32 [4] on the device: steps taken, arrival counter, padding
         self._with_grad = None    # ids of the parameters that carried gradients at the first step
         self._tables = {}         # (group, launch) -> (pointers, AdamTensor array)
@@ -239,6 +254,10 @@ class Adam(torch.optim.Optimizer):
         launches = [(gi, group, ps[i:i + _lib.ADAM_MAX_TENSORS])
                     for gi, group, ps in work for i in range(0, len(ps), _lib.ADAM_MAX_TENSORS)]
         zero = _lib.ADAM_ZERO_GRAD if self.zero_grad_in_step else 0
+        gate = self.gate
+        if gate is not None and (not isinstance(gate, torch.Tensor) or gate.device != dev or gate.dtype != torch.int32
+                                 or gate.numel() < 1):
+            raise ValueError("train.Adam: gate must be an int32 tensor on the parameters' device")
         with torch.cuda.device(dev):
             stream = _stream(dev)
             for li, (gi, group, ps) in enumerate(launches):
@@ -255,9 +274,12 @@ class Adam(torch.optim.Optimizer):
                     cached = self._tables[li] = (ptrs, tab)
                 b1, b2 = group["betas"]
                 hold = _lib.ADAM_HOLD_STEP if li + 1 < len(launches) else 0
-                _lib.check(lib.gcnk_adam_f32(cached[1], len(ps), float(group["lr"]), float(b1), float(b2),
-                                             float(group["eps"]), float(group["weight_decay"]), word.data_ptr(),
-                                             zero | hold, stream), "gcnk_adam_f32")
+                args = (cached[1], len(ps), float(group["lr"]), float(b1), float(b2), float(group["eps"]),
+                        float(group["weight_decay"]), word.data_ptr(), zero | hold)
+                if gate is None:
+                    _lib.check(lib.gcnk_adam_f32(*args, stream), "gcnk_adam_f32")
+                else:   # every launch of the step, the HOLD_STEP ones included
+                    _lib.check(lib.gcnk_adam_gated_f32(*args, gate.data_ptr(), stream), "gcnk_adam_gated_f32")
         return loss
 
     # -- checkpoints in torch.optim.Adam's keys -------------------------------------------------
@@ -290,3 +312,209 @@ class Adam(torch.optim.Optimizer):
         self._tables.clear()
         if dev is not None:
             self._word(dev).copy_(torch.tensor([int(steps.pop()) if steps else 0, 0, 0, 0], dtype=torch.int32))
+
+
+class EpochLog:
+    """The per-epoch bookkeeping of trainer.py:372-398 on the device: the state of
+    gcnk_epoch_tail_f32 (epoch, early-stopping counter and best score, stop
+    reason), the history buffer (``max_epoch`` rows of train loss | validation
+    loss | TP | FP | FN | correct) and the launch's workspace.  ``record`` is
+    one launch and no host sync; once a stop reason is set, further ``record``
+    calls write nothing."""
+
+    def __init__(self, max_epoch, nclass, device, patience=10, delta=0.0):
+        if max_epoch < 1 or patience < 0 or not 1 <= nclass <= 1024:
+            raise ValueError(f"EpochLog: max_epoch >= 1, patience >= 0, 1 <= nclass <= 1024 "
+                             f"(got {max_epoch}, {patience}, {nclass})")
+        device = torch.device(device)
+        if device.type != "cuda":
+            require_device(torch.empty(0, device=device), "EpochLog's device")
+        self.max_epoch, self.nclass, self.patience, self.delta = int(max_epoch), int(nclass), int(patience), float(delta)
+        self.device = device
+        self._state = torch.zeros(8, dtype=torch.int32, device=device)   # gcnk_epoch_state: all-zero is initial
+        self._history = torch.zeros(self.max_epoch, _lib.epoch_row_words(self.nclass), dtype=torch.int32, device=device)
+        self._ws = None
+        self._n = None   # the validation set's size (the metrics' denominator)
+        self.graph = None   # fit: the captured epoch (the parameters' .grad live in its memory pool)
+
+    @property
+    def stop_word(self):
+        """int32 [1] device view of the state's ``stopped`` word: train.Adam's gate."""
+        return self._state[1:2]
+
+    def record(self, logits, target, val_idx, train_loss=None):
+        """Close an epoch: validation loss and counts of ``logits`` on ``val_idx``,
+        ``train_loss`` (a device scalar) copied in, the early-stopping decision
+        and the history row -- one launch on the current stream."""
+        with torch.no_grad():
+            logits, target, rc = _prepare(logits, target, val_idx)
+            if logits.device != self.device or logits.shape[1] != self.nclass:
+                raise ValueError(f"EpochLog.record: logits [{tuple(logits.shape)}] on {logits.device}, expected "
+                                 f"{self.nclass} classes on {self.device}")
+            M, P = logits.shape
+            n = rc.n if rc is not None else M
+            if self._n is None:
+                self._n = n
+            elif self._n != n:
+                raise ValueError(f"EpochLog.record: the validation set changed size ({self._n} -> {n})")
+            if train_loss is not None:
+                require_device(train_loss, "train_loss")
+                train_loss = train_loss.detach()
+                if train_loss.dtype != torch.float32 or train_loss.numel() != 1:
+                    raise ValueError("EpochLog.record: train_loss must be one fp32 value on the device")
+            lib = _lib.load()
+            nb = lib.gcnk_epoch_tail_workspace_bytes(M, P)
+            if nb < 0:
+                _lib.check(int(nb), "gcnk_epoch_tail_workspace_bytes")
+            if self._ws is None or self._ws.numel() * 8 < nb:
+                self._ws = torch.empty(nb // 8, dtype=torch.float64, device=self.device)
+            with torch.cuda.device(self.device):
+                _lib.check(lib.gcnk_epoch_tail_f32(
+                    logits.data_ptr(), logits.stride(0), M, P, target.data_ptr(),
+                    rc.counts.data_ptr() if rc is not None else None, n,
+                    train_loss.data_ptr() if train_loss is not None else None,
+                    self._state.data_ptr(), self._history.data_ptr(), self.max_epoch, self.patience, self.delta,
+                    self._ws.data_ptr(), self._ws.numel() * 8, _stream(self.device)), "gcnk_epoch_tail_f32")
+
+    def state(self):
+        """The device state as a host _lib.EpochState (one 32-byte copy: synchronises)."""
+        return _lib.EpochState.from_buffer_copy(self._state.cpu().numpy().tobytes())
+
+    def poll(self):
+        """(epochs recorded, stop reason: 0 running, 1 patience, 2 max_epoch) from
+        one small device->host copy."""
+        st = self.state()
+        return st.epoch, st.stopped
+
+    def history(self, num_classes=None):
+        """The list of dicts the reference's loop builds (trainer.py:372-376), one per
+        recorded epoch: epoch, train_loss, val_loss, acc, macro_f1, precision,
+        recall -- the four metrics from the counts by the reference's numpy
+        arithmetic (``num_classes``: utils.py:53-54; by default the model's)."""
+        from . import metrics
+        epochs, _ = self.poll()
+        rows = self._history[:epochs].cpu().numpy()
+        P = self.nclass
+        out = []
+        for e in range(epochs):
+            tl, vl = (float(x) for x in rows[e, :2].view(np.float32))
+            acc, f1, p, r = metrics._from_counts(rows[e, 2:].astype(np.int64), P,
+                                                 P if num_classes is None else num_classes, self._n)
+            out.append({"epoch": e, "train_loss": tl, "val_loss": vl, "acc": acc, "macro_f1": f1, "precision": p,
+                        "recall": r})
+        return out
+
+
+FitResult = collections.namedtuple("FitResult", "history epochs stop_reason optimizer log")
+
+
+def run_epoch(model, features, adj, target, train_idx, val_idx, optimizer, log, criterion=cross_entropy):
+    """One epoch of trainer.py:354-398 with nothing read back: the training step
+    (forward in train mode, loss on ``train_idx``, backward, ``optimizer.step()``),
+    the forward in eval mode under no_grad, and ``log.record`` on ``val_idx``
+    with the step's loss.  Every call is a launch on the current stream, so an
+    epoch can be captured in a hipGraph and replayed (the index tensors must be
+    the same objects from call to call: their row counts are cached by
+    identity).  ``fit`` is this in a loop."""
+    model.train()
+    optimizer.zero_grad()   # to None, as the reference's call does: no fills, and autograd stores, not adds
+    loss = criterion(model(features, adj), target, train_idx)
+    loss.backward()
+    optimizer.step()
+    model.eval()
+    with torch.no_grad():
+        log.record(model(features, adj), target, val_idx, loss)
+
+
+def fit(model, features, adj, target, train_idx, val_idx, *, lr=0.02, max_epoch=200, patience=10, delta=0.0,
+        weight_decay=0, poll_every=None, graph=None):
+    """The reference's training loop (trainer.py:349-376) to early stopping:
+    Adam(lr, weight_decay) on the mean cross-entropy of ``train_idx``, the
+    validation loss and metrics on ``val_idx`` after every epoch,
+    EarlyStopping(patience, delta), at most ``max_epoch`` epochs.  Returns
+    FitResult(history, epochs, stop_reason, optimizer, log): the history the
+    reference prints (``EpochLog.history``), the number of epochs run, why it
+    stopped (1: patience, 2: max_epoch), the train.Adam and the EpochLog.
+
+    Nothing is decided on the host.  An epoch is: the training step (forward,
+    loss, backward, Adam gated by the log's stop word), the forward in eval
+    mode under no_grad, and ``log.record``.  The host queues ``poll_every``
+    epochs and then reads the stop word once; the epochs queued past the
+    stopping one are no-ops on the parameters, the optimiser's moments and step
+    count, the state and the history.
+
+    Graph mode (``graph=True``; the default when the model draws its dropout
+    masks on the device, dropout_rng="device", or has dropout 0): epoch 0 runs
+    eagerly (a real, counted epoch: plans, launch records and row counts are
+    built there), then ONE epoch is captured in a hipGraph -- a single chain on
+    one stream -- and replayed, ``poll_every`` (default 16) replays per look.
+    Eager mode (``graph=False``; forced for dropout_rng="cpu", whose masks are
+    drawn on the host): the same calls per epoch without capture, by default
+    ``poll_every=1``, which leaves torch's CPU generator exactly where the
+    reference's loop leaves it.  graph=True with CPU masks raises ValueError.
+
+    After ``fit`` returns, the parameters, ``exp_avg``, ``exp_avg_sq`` and the
+    optimiser's step count are those of the loop that breaks at the stopping
+    epoch, and the model is in eval mode.  The parameters' ``.grad`` and the
+    model's mask offset ``_rng_base`` (and with CPU masks and poll_every > 1
+    torch's CPU generator) may be those of up to ``poll_every - 1`` gated epochs
+    later: the forward and backward of a queued epoch still run, only their
+    effect on the model is gated."""
+    require_device(features, "features")
+    require_device(adj, "adj")
+    params = list(model.parameters())
+    if not params:
+        raise ValueError("fit: the model has no parameters")
+    require_device(params[0], "the model")
+    dev = params[0].device
+    host_masks = getattr(model, "dropout_rng", "device") == "cpu" and float(getattr(model, "dropout", 0.0)) > 0.0
+    if graph is None:
+        graph = not host_masks
+    elif graph and host_masks:
+        raise ValueError("fit: graph=True needs masks drawn on the device (dropout_rng='device') or dropout 0: "
+                         "dropout_rng='cpu' draws them on the host every step")
+    if poll_every is None:
+        poll_every = 16 if graph else 1
+    if poll_every < 1:
+        raise ValueError(f"fit: poll_every must be >= 1 (got {poll_every})")
+    target = torch.as_tensor(target).to(device=dev, dtype=torch.int64).contiguous()
+    tr = torch.as_tensor(train_idx).to(device=dev, dtype=torch.int64).contiguous()
+    va = torch.as_tensor(val_idx).to(device=dev, dtype=torch.int64).contiguous()
+    gc2 = getattr(model, "gc2", None)
+    nclass = gc2.out_features if hasattr(gc2, "out_features") else int(target.max().item()) + 1
+
+    log = EpochLog(max_epoch, nclass, dev, patience, delta)
+    # the gate is closed by the epoch that stops: every later step is a no-op
+    opt = Adam(params, lr=lr, weight_decay=weight_decay, gate=log.stop_word)
+
+    def epoch():
+        run_epoch(model, features, adj, target, tr, va, opt, log)
+
+    def done():
+        epochs, reason = log.poll()
+        return FitResult(log.history(), epochs, reason, opt, log)
+
+    if not graph:
+        while True:
+            for _ in range(poll_every):
+                epoch()
+            if log.poll()[1]:
+                return done()
+
+    side = torch.cuda.Stream(dev)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(side):
+        epoch()   # epoch 0, eager: builds the plans, the launch records and both sets' row counts
+    torch.cuda.current_stream(dev).wait_stream(side)
+    if log.poll()[1]:   # (max_epoch == 1)
+        return done()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        epoch()
+    log.graph = g
+    # (the capture itself launched nothing: the first replay is epoch 1)
+    while True:
+        for _ in range(poll_every):
+            g.replay()
+        if log.poll()[1]:
+            return done()

@@ -693,6 +693,103 @@ typedef struct gcnk_adam_tensor {
 int gcnk_adam_f32(const gcnk_adam_tensor* t /* host */, int32_t ntensors, double lr, double beta1, double beta2,
                   double eps, double weight_decay, int32_t* state, int32_t flags, void* stream);
 
+/* The same step behind a gate (an addition within ABI 13): `gate` is a device
+ * word written by an EARLIER launch on the same stream (gcnk_epoch_state's
+ * `stopped`), so it is uniform over the launch.  *gate != 0: the launch changes
+ * nothing -- no p, m or v, neither state word, no gradient zeroing (with
+ * GCNK_ADAM_ZERO_GRAD too) -- so optimiser steps queued past the epoch that
+ * stopped training leave the model where the loop that breaks there leaves it.
+ * *gate == 0, or gate == NULL: gcnk_adam_f32, bit for bit (the same kernel).
+ * The gate is read by the lane that reads the step word and reaches the other
+ * lanes with the step factors, behind the same barrier.  Pass the gate to every
+ * launch of one step, the GCNK_ADAM_HOLD_STEP ones included.  Arguments and
+ * GCNK_EARG cases otherwise as gcnk_adam_f32. */
+int gcnk_adam_gated_f32(const gcnk_adam_tensor* t /* host */, int32_t ntensors, double lr, double beta1,
+                        double beta2, double eps, double weight_decay, int32_t* state, int32_t flags,
+                        const int32_t* gate, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * The tail of a training epoch in one launch (csrc/epoch.hip; an addition
+ * within ABI 13): trainer.py:378-398 TopicGCNTrainer.val on the validation set
+ * (the loss of trainer.py:383 and the counts behind accuracy / macro_f1),
+ * trainer.py:372-376 the history row and the stopping decision of
+ * utils.py:216-255 EarlyStopping, all on the DEVICE: a loop built on it never
+ * waits for the GPU to decide, and may queue epochs ahead (a hipGraph of one
+ * epoch, replayed).  It replaces gcnk_class_stats + gcnk_ce_forward_f32 (a
+ * memset and three kernels), their device->host copy and the Python object.
+ *
+ * Inputs: logits [M x P] (ld), int64 `target` indexed by row, `counts` =
+ * gcnk_ce_row_counts of the validation index set (NULL: every row once, n is
+ * then M), n = the set's length, `train_loss` a device float (NULL: NaN is
+ * recorded).  With e = state->epoch, for every row r with counts[r] > 0, in one
+ * dense pass:
+ *     lse_r, l_r     as gcnk_ce_forward_f32 forms them (the same code)
+ *     pred_r         the first maximal logit, a NaN counting as maximal
+ *                    (gcnk_class_stats: th.max semantics)
+ *     pred_r == target[r]:  TP[pred_r] += counts[r], correct += counts[r]
+ *     otherwise:            FP[pred_r] += counts[r], and FN[target[r]] +=
+ *                           counts[r] when target[r] is inside [0, P)
+ * so duplicates in the index set count as often as they occur; target[r] is
+ * read for scored rows only.  The validation loss
+ *     val_loss = fp32( (sum_r counts[r] * l_r) / n )
+ * is summed in float64 with gcnk_ce_forward_f32's partition, tree and order:
+ * it is BITWISE that function's result on the same inputs (NaN for n == 0 or a
+ * scored target outside [0, P)).  The counts are integer atomics into the
+ * history row: exact.  No float atomics, no memset node; no workgroup waits on
+ * another (the workgroup that arrives last at state->arrivals finishes the
+ * epoch), and two launches on equal inputs write bitwise equal rows.
+ *
+ * The last arriver then runs utils.py:238-255 in float64 on
+ * score = -(double)val_loss:
+ *     e == 0:                     best = score
+ *     score < best + delta:       counter += 1; counter >= patience stops
+ *                                 (reason GCNK_EPOCH_STOP_PATIENCE)
+ *     otherwise:                  best = score, counter = 0
+ * with exactly those comparisons (a NaN loss becomes `best`, an equal loss
+ * resets the counter, as in the reference); not stopped and e + 1 == max_epoch
+ * stops with reason GCNK_EPOCH_STOP_MAX_EPOCH.  It writes history row e
+ *     float train_loss | float val_loss | int32 TP[P] | FP[P] | FN[P] | correct
+ * (GCNK_EPOCH_ROW_WORDS(P) = 3 P + 3 four-byte words per row; rows are
+ * consecutive), sets stop_epoch = e on a stop, `stopped` to the reason and
+ * epoch = e + 1.
+ *
+ * state->stopped != 0 at entry: the launch writes NOTHING, no history row and
+ * no state word (the same when state->epoch is outside [0, max_epoch), which
+ * names no row).  `stopped` is the gate of gcnk_adam_gated_f32.
+ *
+ * The caller zeroes the state and the history (max_epoch rows) ONCE, before the
+ * first launch of a run (all-zero is the initial state; the counts of row e are
+ * added into it).  epoch and stopped are read by every workgroup at entry and
+ * written only by the last arriver, after every workgroup has read them (as
+ * gcnk_adam_f32's step word); `arrivals` is zero on entry and left zero.  One
+ * launch at a time per state.  max_epoch, patience and delta are to be the same
+ * in every launch of a run.
+ *
+ * 1 <= P <= 1024; workspace: gcnk_epoch_tail_workspace_bytes(M, P) bytes, 8-B
+ * aligned (the loss partials: written before they are read, never zeroed).
+ * GCNK_EARG (on the host, before any launch) for M < 0, P outside [1, 1024],
+ * ld < P, n < 0, max_epoch < 1, patience < 0, a NaN delta, a NULL state,
+ * history or workspace (or logits / target with M > 0), a state or workspace
+ * not 8-B aligned, or a workspace too small.
+ * ------------------------------------------------------------------------- */
+#define GCNK_EPOCH_STOP_PATIENCE 1
+#define GCNK_EPOCH_STOP_MAX_EPOCH 2
+#define GCNK_EPOCH_ROW_WORDS(P) (3 * (P) + 3)
+typedef struct gcnk_epoch_state {
+  int32_t epoch;       /* epochs recorded: the index of the next history row */
+  int32_t stopped;     /* 0: running; otherwise a GCNK_EPOCH_STOP_* reason -- the gate word */
+  int32_t stop_epoch;  /* index of the epoch that stopped the run (valid when stopped != 0) */
+  int32_t counter;     /* EarlyStopping.counter */
+  double best;         /* EarlyStopping.best_score (set by the first epoch) */
+  int32_t arrivals;    /* the launch's arrival counter: zero between launches */
+  int32_t reserved;
+} gcnk_epoch_state;    /* 32 bytes, 8-B aligned, on the device */
+int64_t gcnk_epoch_tail_workspace_bytes(int32_t M, int32_t P);
+int gcnk_epoch_tail_f32(const float* logits, int64_t ld, int32_t M, int32_t P, const int64_t* target,
+                        const int32_t* counts, int64_t n, const float* train_loss, gcnk_epoch_state* state,
+                        void* history, int32_t max_epoch, int32_t patience, double delta, void* workspace,
+                        int64_t workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------
  * Weighted edge-list loader (HOST pointers; no device work): the graph file
  * build_graph.py:199 writes (nx.write_weighted_edgelist: "u v weight" lines,
