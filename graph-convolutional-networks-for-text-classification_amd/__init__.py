@@ -8,11 +8,11 @@ from .layer import GCN, GraphConvolution
 from .ops import GCNFn, GraphConvFn, Operand, colsum, gemm, spmm
 from .parallel import ColumnShardedSpMM, shard_bounds, sharded_gcn_forward
 from .sparse import CSR, as_csr, from_arrays, from_torch, preprocess_adj
-from .train import Adam, EpochLog, FitResult, IndexedCrossEntropy, cross_entropy, fit, run_epoch
+from .train import Adam, BestKeeper, EpochLog, FitResult, IndexedCrossEntropy, cross_entropy, fit, run_epoch
 
 __all__ = [
     "datasets", "metrics", "parallel", "sparse", "train", "Adam", "IndexedCrossEntropy", "cross_entropy",
-    "EpochLog", "FitResult", "fit", "run_epoch",
+    "EpochLog", "BestKeeper", "FitResult", "fit", "run_epoch",
     "GCN", "GraphConvolution", "GCNFn", "GraphConvFn", "Operand", "CSR",
     "as_csr", "from_arrays", "from_torch", "preprocess_adj", "spmm", "gemm", "colsum",
     "ColumnShardedSpMM", "shard_bounds", "sharded_gcn_forward",

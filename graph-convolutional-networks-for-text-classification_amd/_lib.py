@@ -64,6 +64,18 @@ class EpochState(ctypes.Structure):
 
 # gcnk_epoch_tail_f32's stop reasons (gcnk.h GCNK_EPOCH_STOP_*)
 EPOCH_STOP_PATIENCE, EPOCH_STOP_MAX_EPOCH = 1, 2
+# gcnk_keep_best_f32 (gcnk.h GCNK_KEEP_*)
+KEEP_MAX_TENSORS, KEEP_CHUNK, KEEP_HOLD_STATE = 8, 8192, 1
+
+
+class KeepTensor(ctypes.Structure):
+    """gcnk.h gcnk_keep_tensor"""
+    _fields_ = [("src", _vp), ("dst", _vp), ("numel", _i64)]
+
+
+class KeepState(ctypes.Structure):
+    """gcnk.h gcnk_keep_state (16 bytes on the device)"""
+    _fields_ = [("seen", _i32), ("best", _i32), ("arrivals", _i32), ("copies", _i32)]
 
 
 def epoch_row_words(nclass):
@@ -202,6 +214,8 @@ SIGNATURES = {
     # workspace_bytes, stream
     "gcnk_epoch_tail_f32": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _f64,
                                            _vp, _i64, _vp]),
+    # tensor table (host, KeepTensor[ntensors]), ntensors, epoch_state, state, flags, stream
+    "gcnk_keep_best_f32": (ctypes.c_int, [_vp, _i32, _vp, _vp, _i32, _vp]),
     "gcnk_edgelist_size": (ctypes.c_int, [ctypes.c_char_p, _vp, _vp]),
     "gcnk_edgelist_csr": (ctypes.c_int, [ctypes.c_char_p, _i64, _i64, _vp, _vp, _vp]),
     "gcnk_csr_to_dense": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp]),

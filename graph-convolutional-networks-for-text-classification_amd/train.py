@@ -25,7 +25,10 @@ bookkeeping -- validation loss and class counts, the early-stopping decision,
 the history row -- is one launch on the device (``EpochLog``,
 gcnk_epoch_tail_f32), the optimiser step is gated by that launch's stop word
 (gcnk_adam_gated_f32), and one epoch is captured in a hipGraph and replayed;
-the host looks at the stop word once per ``poll_every`` epochs.
+the host looks at the stop word once per ``poll_every`` epochs.  With
+``restore_best=True`` one more launch per epoch keeps the parameters of the
+best epoch on the device (``BestKeeper``, gcnk_keep_best_f32: the checkpoint
+utils.py:244 / :254 leave commented out) and ``fit`` ends on those.
 """
 import collections
 import ctypes
@@ -336,6 +339,12 @@ class EpochLog:
         self._ws = None
         self._n = None   # the validation set's size (the metrics' denominator)
         self.graph = None   # fit: the captured epoch (the parameters' .grad live in its memory pool)
+        self.keeper = None  # the BestKeeper built on this log (fit(restore_best=True)), if any
+
+    @property
+    def best_epoch(self):
+        """The keeper's ``best_epoch`` (None without a keeper)."""
+        return None if self.keeper is None else self.keeper.best_epoch
 
     @property
     def stop_word(self):
@@ -405,14 +414,84 @@ class EpochLog:
         return out
 
 
+class BestKeeper:
+    """EarlyStopping.save_checkpoint (utils.py:257-262, called -- commented out --
+    at utils.py:244 and :254) on the device: one ``best`` buffer per parameter
+    and the 16-byte state of gcnk_keep_best_f32.  ``keep()``, queued right after
+    ``log.record``, copies the parameters into the buffers if that record
+    improved the validation loss and writes nothing otherwise -- one launch per
+    8 tensors, no host decision, capturable with the epoch.  One ``keep()`` per
+    ``record``.  The buffers are allocated here, before any capture."""
+
+    def __init__(self, params, log):
+        self.params = list(params)
+        for p in self.params:
+            if (not isinstance(p, torch.Tensor) or p.device != log.device or p.dtype != torch.float32
+                    or p.layout != torch.strided or not p.is_contiguous()):
+                raise RuntimeError("train.BestKeeper: parameters must be contiguous dense fp32 tensors on the "
+                                   f"log's device ({log.device})")
+        self.log = log
+        self.best = [torch.zeros_like(p, memory_format=torch.contiguous_format).detach() for p in self.params]
+        self._state = torch.zeros(4, dtype=torch.int32, device=log.device)   # gcnk_keep_state: all-zero is initial
+        self._tables = {}   # launch -> (pointers, KeepTensor array)
+        log.keeper = self
+
+    @torch.no_grad()
+    def keep(self):
+        """The launch (or launches: 8 tensors each, all but the last holding the
+        state) on the current stream."""
+        lib = _lib.load()
+        dev = self.log.device
+        n = _lib.KEEP_MAX_TENSORS
+        launches = [(self.params[i:i + n], self.best[i:i + n]) for i in range(0, len(self.params), n)]
+        with torch.cuda.device(dev):
+            stream = _stream(dev)
+            for li, (ps, bs) in enumerate(launches):
+                ptrs = tuple(x for p, b in zip(ps, bs) for x in (p.data_ptr(), b.data_ptr()))
+                cached = self._tables.get(li)
+                if cached is None or cached[0] != ptrs:   # rebuilt only when a pointer changed
+                    tab = (_lib.KeepTensor * len(ps))()
+                    for k, p in enumerate(ps):
+                        tab[k].src, tab[k].dst = ptrs[2 * k:2 * k + 2]
+                        tab[k].numel = p.numel()
+                    cached = self._tables[li] = (ptrs, tab)
+                hold = _lib.KEEP_HOLD_STATE if li + 1 < len(launches) else 0
+                _lib.check(lib.gcnk_keep_best_f32(cached[1], len(ps), self.log._state.data_ptr(),
+                                                  self._state.data_ptr(), hold, stream), "gcnk_keep_best_f32")
+
+    def state(self):
+        """The device state as a host _lib.KeepState (one 16-byte copy: synchronises)."""
+        return _lib.KeepState.from_buffer_copy(self._state.cpu().numpy().tobytes())
+
+    @property
+    def best_epoch(self):
+        """The 0-based epoch whose parameters the buffers hold; None while nothing
+        is kept (reads the device state: synchronises)."""
+        best = self.state().best
+        return None if best == 0 else best - 1
+
+    @torch.no_grad()
+    def restore(self):
+        """Copy the kept parameters back IN PLACE (data pointers stay valid for
+        launch records and captured graphs); returns ``best_epoch``."""
+        e = self.best_epoch
+        if e is None:
+            raise RuntimeError("train.BestKeeper: nothing was kept (no keep() has followed an improving record)")
+        for p, b in zip(self.params, self.best):
+            p.copy_(b)
+        return e
+
+
 FitResult = collections.namedtuple("FitResult", "history epochs stop_reason optimizer log")
 
 
-def run_epoch(model, features, adj, target, train_idx, val_idx, optimizer, log, criterion=cross_entropy):
+def run_epoch(model, features, adj, target, train_idx, val_idx, optimizer, log, criterion=cross_entropy,
+              keeper=None):
     """One epoch of trainer.py:354-398 with nothing read back: the training step
     (forward in train mode, loss on ``train_idx``, backward, ``optimizer.step()``),
     the forward in eval mode under no_grad, and ``log.record`` on ``val_idx``
-    with the step's loss.  Every call is a launch on the current stream, so an
+    with the step's loss -- then, with a ``keeper`` (BestKeeper), its ``keep()``.
+    Every call is a launch on the current stream, so an
     epoch can be captured in a hipGraph and replayed (the index tensors must be
     the same objects from call to call: their row counts are cached by
     identity).  ``fit`` is this in a loop."""
@@ -424,10 +503,12 @@ def run_epoch(model, features, adj, target, train_idx, val_idx, optimizer, log, 
     model.eval()
     with torch.no_grad():
         log.record(model(features, adj), target, val_idx, loss)
+        if keeper is not None:
+            keeper.keep()
 
 
 def fit(model, features, adj, target, train_idx, val_idx, *, lr=0.02, max_epoch=200, patience=10, delta=0.0,
-        weight_decay=0, poll_every=None, graph=None):
+        weight_decay=0, poll_every=None, graph=None, restore_best=False):
     """The reference's training loop (trainer.py:349-376) to early stopping:
     Adam(lr, weight_decay) on the mean cross-entropy of ``train_idx``, the
     validation loss and metrics on ``val_idx`` after every epoch,
@@ -459,7 +540,19 @@ def fit(model, features, adj, target, train_idx, val_idx, *, lr=0.02, max_epoch=
     model's mask offset ``_rng_base`` (and with CPU masks and poll_every > 1
     torch's CPU generator) may be those of up to ``poll_every - 1`` gated epochs
     later: the forward and backward of a queued epoch still run, only their
-    effect on the model is gated."""
+    effect on the model is gated.
+
+    ``restore_best=True``: what EarlyStopping.save_checkpoint (utils.py:257-262)
+    was written for and the reference leaves commented out (utils.py:244, :254).
+    A BestKeeper is built before epoch 0 and its ``keep()`` follows every
+    ``log.record`` (captured with the epoch in graph mode): one more launch per
+    epoch, still no host decision.  After the stop the parameters of the epoch
+    with the best validation loss (the last one that reset the early-stopping
+    counter) are copied back in place; ``result.log.keeper`` is the keeper and
+    ``result.log.best_epoch`` that epoch.  Only the parameters go back:
+    ``exp_avg``, ``exp_avg_sq`` and the step count stay those of the stopping
+    epoch, and so does the history.  With ``restore_best=False`` nothing is
+    allocated, launched or changed, and ``result.log.keeper`` is None."""
     require_device(features, "features")
     require_device(adj, "adj")
     params = list(model.parameters())
@@ -486,12 +579,15 @@ def fit(model, features, adj, target, train_idx, val_idx, *, lr=0.02, max_epoch=
     log = EpochLog(max_epoch, nclass, dev, patience, delta)
     # the gate is closed by the epoch that stops: every later step is a no-op
     opt = Adam(params, lr=lr, weight_decay=weight_decay, gate=log.stop_word)
+    keeper = BestKeeper(params, log) if restore_best else None   # its buffers exist before any capture
 
     def epoch():
-        run_epoch(model, features, adj, target, tr, va, opt, log)
+        run_epoch(model, features, adj, target, tr, va, opt, log, keeper=keeper)
 
     def done():
         epochs, reason = log.poll()
+        if keeper is not None:
+            keeper.restore()
         return FitResult(log.history(), epochs, reason, opt, log)
 
     if not graph:

@@ -24,6 +24,7 @@
  *   layer.py:185 th.dropout keep-mask draw (CPU generator)    -> gcnk_bernoulli_mt19937 (host, same stream)
  *   trainer.py:307, 358-361, 383-384 CrossEntropyLoss on logits[idx] -> gcnk_ce_forward_f32 / gcnk_ce_backward_f32
  *   trainer.py:308, 359, 362 th.optim.Adam step (and zero_grad)   -> gcnk_adam_f32 (one launch per 8 tensors)
+ *   utils.py:244, 254, 257-262 EarlyStopping.save_checkpoint      -> gcnk_keep_best_f32 (one launch per 8 tensors)
  *
  * Conventions
  *   - All pointers are DEVICE pointers unless a parameter says "host".
@@ -789,6 +790,79 @@ int gcnk_epoch_tail_f32(const float* logits, int64_t ld, int32_t M, int32_t P, c
                         const int32_t* counts, int64_t n, const float* train_loss, gcnk_epoch_state* state,
                         void* history, int32_t max_epoch, int32_t patience, double delta, void* workspace,
                         int64_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Keep the parameters of the best epoch (csrc/keep.hip; an addition within ABI
+ * 13): utils.py:216-262 EarlyStopping.save_checkpoint at the two places where
+ * the validation loss improved, utils.py:244 and utils.py:254 (both calls are
+ * commented out in the reference, which therefore tests the model `patience`
+ * epochs past its best).  ONE launch, queued on the stream right after
+ * gcnk_epoch_tail_f32, copies up to GCNK_KEEP_MAX_TENSORS contiguous fp32
+ * tensors src -> dst (the table travels in the kernel's arguments; more tensors
+ * take further calls) -- but only if the tail that just ran recorded an epoch
+ * that improved.  Nothing is decided on the host: the launch can be captured in
+ * a hipGraph with the epoch and replayed.
+ *
+ * Every workgroup reads epoch_state->epoch, epoch_state->counter and
+ * state->seen at entry (one lane, relaxed agent-scope loads, broadcast through
+ * LDS: gcnk_adam_f32's step-word pattern).  All three were written by EARLIER
+ * launches on the stream, so they are uniform over the launch.
+ *     fresh = epoch > seen          a tail has recorded an epoch since the last look
+ *     copy  = fresh && counter == 0
+ * After a tail that recorded epoch e, counter == 0 holds exactly in the two
+ * branches where the reference would have saved a checkpoint: e == 0, and
+ * !(score < best + delta) -- which covers an equal loss and a NaN loss, as
+ * gcnk_epoch_tail_f32 documents.
+ *   copy:      each workgroup copies its chunk bit for bit (32-bit words: NaN
+ *              payloads, -0.0 and denormals are preserved).
+ *   not copy:  no byte of any dst is written.
+ * Without GCNK_KEEP_HOLD_STATE the last workgroup to arrive at state->arrivals
+ * -- it knows that every other workgroup has read the three words -- stores
+ * seen = epoch and, when copy, best = epoch (1 + the index of the epoch just
+ * kept) and copies += 1; then arrivals = 0.  With GCNK_KEEP_HOLD_STATE the
+ * launch reads and decides the same way, touches no state word and counts in
+ * nowhere: for every call but the last of one keep over more than 8 tensors.
+ *
+ * After a stop the tail writes nothing, so `epoch` stands still and every later
+ * keep launch is a no-op on all bytes.  A patience stop never copies (its
+ * counter is >= 1); a max_epoch stop on an improving last epoch copies in that
+ * epoch's own launch.  ONE keep (all its calls) per tail launch: two tails
+ * between looks would be judged by the second one's `counter` alone.  One keep
+ * at a time per state; the state is zeroed ONCE by the caller (all-zero is
+ * initial).
+ *
+ * Work is cut into chunks of GCNK_KEEP_CHUNK elements, one workgroup (of 1,024
+ * threads) each, found through a prefix table in the kernel's arguments
+ * (gcnk_adam_f32's layout; the chunk is four times that step's, because what a
+ * launch costs beyond its copy is one arrival per workgroup): 16-B accesses
+ * where src and dst share their offset from a 16-B boundary (a scalar head of up
+ * to 3 elements, a scalar ragged tail), all scalar where the offsets disagree.
+ * A chunk's loads are issued after the decision: a launch that does not copy
+ * moves three words per workgroup.  dst is stored nontemporally (it is not read
+ * again before a restore).  No allocation, no sync, no float atomics.
+ *
+ * GCNK_EARG (on the host, before any launch) for ntensors outside [0, 8]; a
+ * NULL table, epoch_state or state; numel < 0; a NULL src or dst with
+ * numel > 0; a src range overlapping its own or another tensor's dst range;
+ * unknown flag bits; a state not 4-B aligned.  ntensors == 0 succeeds and does
+ * nothing.
+ * ------------------------------------------------------------------------- */
+#define GCNK_KEEP_MAX_TENSORS 8
+#define GCNK_KEEP_CHUNK 8192
+#define GCNK_KEEP_HOLD_STATE 1   /* every launch but the last of one keep over more than 8 tensors */
+typedef struct gcnk_keep_tensor {
+  const float* src;    /* the live parameter */
+  float* dst;          /* its best-epoch copy */
+  int64_t numel;
+} gcnk_keep_tensor;
+typedef struct gcnk_keep_state {
+  int32_t seen;        /* gcnk_epoch_state.epoch at the last launch that looked */
+  int32_t best;        /* 1 + index of the epoch whose parameters dst holds; 0: nothing kept yet */
+  int32_t arrivals;    /* the launch's arrival counter: zero between launches */
+  int32_t copies;      /* launches (steps) that copied */
+} gcnk_keep_state;     /* 16 bytes, 4-B aligned, on the device; all-zero is initial */
+int gcnk_keep_best_f32(const gcnk_keep_tensor* t /* host */, int32_t ntensors, const gcnk_epoch_state* epoch_state,
+                       gcnk_keep_state* state, int32_t flags, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Weighted edge-list loader (HOST pointers; no device work): the graph file
