@@ -165,6 +165,8 @@ SIGNATURES = {
         _f32, _u64, _u64, _vp,            # keep_prob, seed, offset, rng_base
         _vp, _i64, _vp, _i64, _vp, _i64,  # W2, ldw2, H, ldh, C2, ldc2
         _vp]),                            # stream
+    # F, Kc, nhub, rec_words, P, ldu, u_aligned16, out6
+    "gcnk_hubfactor_gc1_route": (ctypes.c_int, [_i32, _i32, _i32, _i32, _i32, _i64, _i32, _vp]),
     "gcnk_hubfactor_gc2_f32": (ctypes.c_int, [
         _i32, _i32, _i32, _vp, _i32,      # M, H, P, rec, rec_words
         _vp, _vp, _vp, _vp, _vp, _vp,     # diag, pre, hub_ids (host), hub_rp (host), hub_ci, hub_val
@@ -230,8 +232,10 @@ SIGNATURES = {
     "gcnk_csr_transpose": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
 }
 
-# added within ABI 13 (gc2 from the hub factor, the backward's route report): absent from variants of an older tree
-NEWER_THAN_SOME_VARIANTS = ("gcnk_hubfactor_gc2_f32", "gcnk_factor_diag_f32", "gcnk_gcn_bwd2_route")
+# added within ABI 13 (gc2 from the hub factor, the backward's and the factored gc1's route reports): absent from
+# variants of an older tree
+NEWER_THAN_SOME_VARIANTS = ("gcnk_hubfactor_gc2_f32", "gcnk_factor_diag_f32", "gcnk_gcn_bwd2_route",
+                            "gcnk_hubfactor_gc1_route")
 
 _lock = threading.Lock()
 _lib = None

@@ -412,6 +412,52 @@ extern "C" int64_t gcnk_hubfactor_lds_bytes(int32_t F, int32_t Kc, int32_t nhub,
   return hubfactor_lds_bytes(F, Kc, nhub, rec_words, P);
 }
 
+// What gcnk_hubfactor_gc1_f32 launches for a shape, and whether it launches at
+// all: the one place these rules live.  The entry point launches from this and
+// gcnk_hubfactor_gc1_route reports it.  Returns the first check that fails, in
+// the entry point's order (its own checks on the other operands sit between
+// them): 0 none, 1 sizes, 2 leading dimensions, 3 unsupported shape, 5 LDS.
+struct FactorRoute {
+  int ks, ntq, np, u_lds;
+  int64_t lds_b;       // the operands' LDS bytes (hubfactor_lds_bytes)
+  int64_t lds_launch;  // dynamic LDS of the launch: lds_b, plus U's staged rows when u_lds
+};
+
+static int hubfactor_route(int32_t F, int32_t Kc, int32_t nhub, int32_t rec_words, int32_t P, int64_t ldu,
+                           bool u_aligned16, FactorRoute& rt) {
+  rt = FactorRoute{};
+  if (F <= 0 || Kc <= 0 || nhub <= 0 || P <= 0) return 1;
+  if (ldu < Kc || rec_words < kRecHead || rec_words % 4) return 2;
+  if (F % 4 || F > 256 || Kc > 4 * kMaxKsteps || P > kProjMax) return 3;
+  rt.ks = pick_ks(Kc); rt.ntq = pick_ntq(F); rt.np = pick_np(P);
+  rt.lds_b = hubfactor_lds_bytes(F, Kc, nhub, rec_words, P);
+  if (rt.lds_b > 160 * 1024) return 5;
+  // U's rows through LDS where they fit (R8: 95 + 8.7 KB; the 20ng-shaped 70
+  // topic-weight columns at 152 KB take the direct loads)
+  rt.u_lds = ldu % 4 == 0 && u_aligned16 && rt.lds_b + hubfactor_u_bytes(Kc) <= 160 * 1024;
+  rt.lds_launch = rt.lds_b + (rt.u_lds ? hubfactor_u_bytes(Kc) : 0);
+  return 0;
+}
+
+extern "C" int gcnk_hubfactor_gc1_route(int32_t F, int32_t Kc, int32_t nhub, int32_t rec_words, int32_t P,
+                                        int64_t ldu, int32_t u_aligned16, int64_t* out6) {
+  FactorRoute rt;
+  const int bad = out6 ? hubfactor_route(F, Kc, nhub, rec_words, P, ldu, u_aligned16 != 0, rt) : 1;
+  if (bad == 1 || bad == 2) {
+    set_error("gcnk_hubfactor_gc1_route: null out6, bad sizes or leading dimension (F=%d Kc=%d hubs=%d P=%d)", F, Kc,
+              nhub, P);
+    return GCNK_EARG;
+  }
+  if (bad) {
+    set_error("gcnk_hubfactor_gc1_route: unsupported (F=%d %% 4, F <= 256, Kc=%d <= 128, P=%d <= 32, %lld B of LDS "
+              "<= 160 KiB)", F, Kc, P, (long long)rt.lds_b);
+    return GCNK_EUNSUP;
+  }
+  out6[0] = rt.ks; out6[1] = rt.ntq; out6[2] = rt.np; out6[3] = rt.u_lds; out6[4] = rt.lds_launch;
+  out6[5] = 1;  // workgroups per 32 rows
+  return GCNK_OK;
+}
+
 // The dynamic-LDS limit is raised once per kernel instantiation and device
 // (dyn_lds_attr), then the launch.
 template <int KS, int NTQ, int NP>
@@ -432,17 +478,18 @@ extern "C" int gcnk_hubfactor_gc1_f32(int32_t M, int32_t F, int32_t Kc, int32_t 
                                       float keep_prob, uint64_t seed, uint64_t offset, const uint64_t* rng_base,
                                       const float* W2, int64_t ldw2, float* H, int64_t ldh, float* C2,
                                       int64_t ldc2, void* stream) {
-  if (M <= 0 || F <= 0 || Kc <= 0 || nhub <= 0 || P <= 0 || !U || !W || !S || !rec || !W2 || !C2 || k0 < 0) {
+  FactorRoute rt;
+  const int bad = hubfactor_route(F, Kc, nhub, rec_words, P, ldu, aligned16(U), rt);
+  if (bad == 1 || M <= 0 || !U || !W || !S || !rec || !W2 || !C2 || k0 < 0) {
     set_error("gcnk_hubfactor_gc1_f32: bad sizes or null operand (M=%d F=%d Kc=%d hubs=%d P=%d)", M, F, Kc, nhub, P);
     return GCNK_EARG;
   }
-  if (ldu < Kc || ldw < F || lds < F || ldw2 < P || ldc2 < P || (H && ldh < F) || rec_words < kRecHead ||
-      rec_words % 4) {
+  if (bad == 2 || ldw < F || lds < F || ldw2 < P || ldc2 < P || (H && ldh < F)) {
     set_error("gcnk_hubfactor_gc1_f32: leading dimension too small");
     return GCNK_EARG;
   }
-  if (F % 4 || F > 256 || Kc > 4 * kMaxKsteps || P > kProjMax || ldw != F || lds != F || ldw2 != P ||
-      !aligned16(W) || !aligned16(S) || (H && !aligned16(H)) || (H && ldh % 4) || (bias && !aligned16(bias))) {
+  if (bad == 3 || ldw != F || lds != F || ldw2 != P || !aligned16(W) || !aligned16(S) || (H && !aligned16(H)) ||
+      (H && ldh % 4) || (bias && !aligned16(bias))) {
     set_error("gcnk_hubfactor_gc1_f32: unsupported shape (F=%d %% 4, F <= 256, Kc <= 128, P <= 32, 16-B rows)", F);
     return GCNK_EUNSUP;
   }
@@ -451,17 +498,14 @@ extern "C" int gcnk_hubfactor_gc1_f32(int32_t M, int32_t F, int32_t Kc, int32_t 
     set_error("gcnk_hubfactor_gc1_f32: bad epilogue %d (dropout needs a mask with ldm >= F)", epilogue);
     return GCNK_EARG;
   }
-  const int64_t lds_b = hubfactor_lds_bytes(F, Kc, nhub, rec_words, P);
-  if (lds_b > 160 * 1024) {
+  if (bad == 5) {
     set_error("gcnk_hubfactor_gc1_f32: %lld B of LDS per workgroup > 160 KiB (F=%d Kc=%d hubs=%d)",
-              (long long)lds_b, F, Kc, nhub);
+              (long long)rt.lds_b, F, Kc, nhub);
     return GCNK_EUNSUP;
   }
   FactorArgs a;
   a.M = M; a.F = F; a.Kc = Kc; a.nhub = nhub; a.P = P;
-  // U's rows through LDS where they fit (R8: 95 + 8.7 KB; the 20ng-shaped 70
-  // topic-weight columns at 152 KB take the direct loads)
-  a.u_lds = ldu % 4 == 0 && aligned16(U) && lds_b + hubfactor_u_bytes(Kc) <= 160 * 1024;
+  a.u_lds = rt.u_lds;
   a.U = U; a.ldu = ldu; a.W = W; a.ldw = ldw; a.k0 = k0;
   a.S = S; a.lds = lds; a.rec = rec; a.rec_words = rec_words;
   a.W2 = W2; a.ldw2 = ldw2; a.H = H; a.ldh = ldh; a.C2 = C2; a.ldc2 = ldc2;
@@ -471,8 +515,8 @@ extern "C" int gcnk_hubfactor_gc1_f32(int32_t M, int32_t F, int32_t Kc, int32_t 
   e.code = epilogue; e.stamps = debug_stamps();
   e.ldm = epilogue == GCNK_EPI_BIAS_RELU_HASH ? (ldm > 0 ? ldm : F) : ldm;
   const int64_t nblk = ((int64_t)M + kRB - 1) / kRB;
-  const int ks = pick_ks(Kc), ntq = pick_ntq(F), np = pick_np(P);
-  const int64_t lds_l = lds_b + (a.u_lds ? hubfactor_u_bytes(Kc) : 0);
+  const int ks = rt.ks, ntq = rt.ntq, np = rt.np;
+  const int64_t lds_l = rt.lds_launch;
 #define GCNK_FACTOR_CASE(KS_, NTQ_)                                                   \
   if (ks == KS_ && ntq == NTQ_)                                                       \
     return np == 1 ? launch_factor<KS_, NTQ_, 1>(a, nblk, lds_l, stream)              \

@@ -10,8 +10,10 @@
 // The sum runs in float64 in the row's CSR item order and is rounded to fp32
 // once: the order the host restatement's sparse product uses (scipy csr_matmat
 // accumulates over A's row items in order), and the fp32 x fp32 products are
-// exact in float64, so device U equals the host float64 U bit for bit
-// (tests/test_gpu_parity.py pins it).
+// exact in float64, so device U equals the host float64 U bit for bit.
+// tests/test_factor_build_kernels.py pins every kernel here at its own entry
+// point (hand-made CSRs, bitwise against numpy, sentinels around every output);
+// tests/test_gpu_parity.py pins the whole build to the host restatement.
 //
 // A_H is stored as one record per 32-row block of `perm` (csrc/factor.hip):
 // 33 block-relative item offsets, 3 pad words, 32 row ids (-1 past M), then
@@ -159,7 +161,8 @@ __global__ void __launch_bounds__(64) factor_rec_kernel(const int32_t* __restric
       base += 2 * __popcll(m);
     }
   }
-  if (dropped) atomicAdd(overflow, 1);
+  // one count per block, however many of its items (lanes) were dropped
+  if (__ballot(dropped) != 0 && lane == 0) atomicAdd(overflow, 1);
 }
 
 // ---- structure analysis (gcnk_factor_analyze).  Workspace words:
@@ -173,6 +176,7 @@ __global__ void factor_info_init_kernel(int32_t* __restrict__ info) {
     info[kInfoK0] = INT_MAX;
     info[kInfoK1] = -1;
     info[kInfoXTot] = 0;
+    info[5] = info[6] = info[7] = 0;   // the host's info[8] is copied whole: documented zero
   }
 }
 

@@ -53,9 +53,10 @@
 extern "C" {
 #endif
 
-/* ABI note: 13 also covers gcnk_factor_diag_f32, gcnk_hubfactor_gc2_f32 and the
- * gc2_* fields at the end of gcnk_gcn_fwd (additions only: no existing symbol,
- * field offset or meaning changed, so the number stayed). */
+/* ABI note: 13 also covers gcnk_factor_diag_f32, gcnk_hubfactor_gc2_f32, the
+ * gc2_* fields at the end of gcnk_gcn_fwd and the route reports
+ * gcnk_gcn_bwd2_route / gcnk_hubfactor_gc1_route (additions only: no existing
+ * symbol, field offset or meaning changed, so the number stayed). */
 #define GCNK_ABI_VERSION 13
 
 #define GCNK_OK 0
@@ -321,6 +322,20 @@ int gcnk_hubfactor_gc1_f32(int32_t M, int32_t F, int32_t Kc, int32_t nhub, int32
                            const uint8_t* drop_mask, int64_t ldm, float drop_scale, float keep_prob, uint64_t seed,
                            uint64_t offset, const uint64_t* rng_base, const float* W2, int64_t ldw2, float* H,
                            int64_t ldh, float* C2, int64_t ldc2, void* stream);
+/* Test aid (within ABI 13, an addition only): what gcnk_hubfactor_gc1_f32
+ * launches for these arguments, from the host function the launch itself is
+ * made from (nothing is launched here, no GPU is needed).  u_aligned16: U's
+ * base pointer is 16-B aligned.  out6 =
+ *   0 KS, 1 NTQ, 2 NP   the instantiation hubfactor_gc1_kernel<KS, NTQ, NP>:
+ *                       k-steps of U W[Kc] (13, 18, 25, 32), 16-column tiles
+ *                       of F per wave (2, 3, 4), n-tiles of P (1, 2)
+ *   3 u_lds             U's rows staged in LDS by 16-B DMA (else loaded directly)
+ *   4 dynamic LDS bytes of the launch      5 workgroups per 32 rows (1)
+ * GCNK_EARG / GCNK_EUNSUP where gcnk_hubfactor_gc1_f32 returns them for these
+ * arguments (sizes, ldu < Kc, rec_words; F % 4, F > 256, Kc > 128, P > 32,
+ * more than 160 KiB of LDS). */
+int gcnk_hubfactor_gc1_route(int32_t F, int32_t Kc, int32_t nhub, int32_t rec_words, int32_t P, int64_t ldu,
+                             int32_t u_aligned16, int64_t* out6);
 /* ---------------------------------------------------------------------------
  * gc2's aggregation from the hub factor (csrc/factor_gc2.hip; layer.py:106,110
  * of gc2):  out[r, :P] = sum over row r's items of A-hat, in CSR column order,

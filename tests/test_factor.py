@@ -6,16 +6,20 @@ reference (layer.py:102,106) in float64 on the reference-built R8 graph and on
 synthetic doc-topic graphs, the per-block records hold exactly A-hat's
 hub-column nonzeros, and graphs without the structure are refused."""
 import os
+import sys
 
 import numpy as np
 import pytest
 import scipy.sparse as sp
 import torch
 
-import gcn_amd  # noqa: F401
-from graph_convolutional_networks_for_text_classification_amd import datasets
-from graph_convolutional_networks_for_text_classification_amd.sparse import from_arrays
-from oracle import factor_host as factor
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import factor_cases as fc  # noqa: E402
+
+import gcn_amd  # noqa: E402,F401
+from graph_convolutional_networks_for_text_classification_amd import datasets  # noqa: E402
+from graph_convolutional_networks_for_text_classification_amd.sparse import from_arrays  # noqa: E402
+from oracle import factor_host as factor  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -37,10 +41,15 @@ def _csr(m):
     return from_arrays(m.indptr.astype(np.int32), m.indices.astype(np.int32), m.data.astype(np.float32), m.shape, "cpu")
 
 
-def _check_factor(A, X, F=24, seed=0):
-    """float64: U W1[Kc] + A_H (X[hubs] W1) == A (X W1)."""
+def _check_factor(A, X, F=24, seed=0, dense=False, csr=None):
+    """float64: U W1[Kc] + A_H (X[hubs] W1) == A (X W1).  dense: X goes in as a
+    dense tensor; csr: X's CSR operand as given (explicit zeros kept)."""
     A, X = sp.csr_matrix(A), sp.csr_matrix(X)
-    f = factor.build(_csr(A), _XOp(csr=_csr(X)))
+    if dense:
+        xop = _XOp(dense=torch.from_numpy(np.ascontiguousarray(X.toarray(), dtype=np.float32)))
+    else:
+        xop = _XOp(csr=csr if csr is not None else _csr(X))
+    f = factor.build(_csr(A), xop)
     assert f is not None
     W1 = np.random.default_rng(seed).standard_normal((X.shape[1], F))
     Af, Xf = A.astype(np.float64), X.astype(np.float64)
@@ -130,6 +139,45 @@ def test_factor_dense_features():
     Z = f.U[:, :100].astype(np.float64) @ W1       # rows in the block order
     Zh = A[:, hubs] @ (X[hubs].astype(np.float64) @ W1)
     assert np.abs(Z + Zh[perm] - ref[perm]).max() < 1e-5 * max(1, np.abs(ref).max())
+
+
+def _raw_csr(m):
+    """The CSR operand of a sorted scipy CSR as it is: explicit zeros stay stored."""
+    return from_arrays(m.indptr.astype(np.int32), m.indices.astype(np.int32), m.data.astype(np.float32), m.shape, "cpu")
+
+
+@pytest.mark.parametrize("name,variant", fc.RUNS)
+def test_factor_feature_range_by_hand(name, variant):
+    """Hand-built graphs (tests/factor_cases.py) whose documents' features lie
+    in [k0, k0 + Kc) with k0 > 0, Kc = 1, 65, 128 and 129, or nowhere: the
+    factor's (H, k0, Kc) are exactly those, Kc = 129 is refused, documents
+    without features give (0, 1), explicit zeros stored outside the range do
+    not widen it, and the float64 identity holds for a dense and a CSR X."""
+    c = fc.CONFIGS[name]
+    A = fc.graph()
+    X = fc.features(name, explicit_zeros=variant == "csr_zeros")
+    assert A.shape == (152, 152) and X.shape == (152, c.K)
+    if variant == "csr_zeros":
+        assert (X.data == 0).any()
+        outside = X.indices[X.data == 0]
+        assert ((outside < c.k0) | (outside >= c.k0 + c.kc)).all()
+    if c.expect is None:
+        xop = _XOp(dense=torch.from_numpy(X.toarray())) if variant == "dense" else _XOp(csr=_raw_csr(X))
+        assert factor.build(_csr(A), xop) is None
+        return
+    f = _check_factor(A, X, dense=variant == "dense", csr=None if variant == "dense" else _raw_csr(X))
+    assert (f.H, f.k0, f.Kc) == (fc.NTOPIC,) + c.expect
+    assert f.hubs.tolist() == [150, 151] and f.nblk == 5 and f.M % 32 != 0
+    assert f.U.shape == (152, (f.Kc + 3) // 4 * 4) and not f.U[:, f.Kc:].any()
+
+
+def test_factor_wide_graph_by_hand():
+    """The 600 + 26 graph of the forward test that the factored kernel refuses
+    for LDS: it factors, with 26 hubs and the full Kc = 128 at k0 = 1."""
+    A = fc.wide_graph()
+    X = fc.features("k0_1_kc128", fc.WIDE_NDOC, fc.WIDE_NTOPIC)
+    f = _check_factor(A, X, dense=True)
+    assert (f.H, f.k0, f.Kc) == (fc.WIDE_NTOPIC, 1, 128)
 
 
 def test_factor_refuses_unstructured_graph():

@@ -11,17 +11,22 @@ bit-exact):
     row whose golden top-2 gap exceeds twice the measured max logit error
     (the rows below it are counted and bounded).
 """
+import ctypes
 import os
+import sys
 
 import numpy as np
 import pytest
 import torch
 
-import gcn_amd  # noqa: F401
-from graph_convolutional_networks_for_text_classification_amd import (
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import factor_cases as fc  # noqa: E402
+
+import gcn_amd  # noqa: E402,F401
+from graph_convolutional_networks_for_text_classification_amd import (  # noqa: E402
     GCN, _lib, colsum, datasets, from_arrays, gemm, spmm)
-from graph_convolutional_networks_for_text_classification_amd.sparse import from_torch
-from oracle import csr_ref, gcn_ref
+from graph_convolutional_networks_for_text_classification_amd.sparse import from_torch  # noqa: E402
+from oracle import csr_ref, gcn_ref  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -1361,6 +1366,92 @@ def test_factored_forward_hub_rows_first_ragged(mode):
         _grads_close(ga[k], gb[k], k)
 
 
+def _by_hand_operands(name, variant, wide=False):
+    """(A-hat as a CSR, X as a dense tensor or a CSR) of tests/factor_cases.py on the device.  The CSRs are
+    built from the arrays as they are: explicit zeros stay stored."""
+    A = fc.wide_graph() if wide else fc.graph()
+    nd, nt = (fc.WIDE_NDOC, fc.WIDE_NTOPIC) if wide else (fc.NDOC, fc.NTOPIC)
+    X = fc.features(name, nd, nt, explicit_zeros=variant == "csr_zeros")
+    a = from_arrays(A.indptr, A.indices, A.data, A.shape, DEV)
+    if variant == "dense":
+        return a, torch.from_numpy(X.toarray()).to(DEV)
+    return a, from_arrays(X.indptr, X.indices, X.data, X.shape, DEV)
+
+
+def _factored_against_spmm(A, X, K, F, P, mode, want_kind):
+    """GCN(K, F, P) on (X, A) with ops.FACTOR_GC1 True against False (ops.DENSE_AX off: a dense X would
+    otherwise take the narrow-feature gc1): logits within 1e-5 max(1, max|logits|), the four gradients
+    within _grads_close; the True run's forward record is of kind want_kind."""
+    from graph_convolutional_networks_for_text_classification_amd import ops, record
+    outs = {}
+    for fac in (True, False):
+        saved, saved_ax = ops.FACTOR_GC1, ops.DENSE_AX
+        ops.FACTOR_GC1, ops.DENSE_AX = fac, False
+        try:
+            torch.manual_seed(5)
+            m = GCN(nfeat=K, nhid=F, nclass=P, dropout=0.5, dropout_rng="device").to(DEV)
+            m.train(mode != "eval")
+            lg = m(X, A)
+            lg.square().sum().backward()
+            outs[fac] = (lg.detach().cpu().numpy(), {k: p.grad.cpu().numpy() for k, p in m.named_parameters()})
+            if fac:
+                rec, _ = record.get(A, ops.Operand(X), F, P, DEV, train=True)
+                assert rec.kind in want_kind, record.KIND_NAMES[rec.kind]
+        finally:
+            ops.FACTOR_GC1, ops.DENSE_AX = saved, saved_ax
+    (la, ga), (lb, gb) = outs[True], outs[False]
+    assert np.isfinite(la).all()
+    scale = max(1.0, float(np.abs(lb).max()))
+    err = float(np.abs(la - lb).max())
+    print(f"logits max |factored - spmm| {err:.3e} (bound {1e-5 * scale:.3e})")
+    assert err <= 1e-5 * scale, err
+    assert len(ga) == 4
+    for k in ga:
+        _grads_close(ga[k], gb[k], k)
+
+
+@pytest.mark.parametrize("mode", ["eval", "train_hash"])
+@pytest.mark.parametrize("name,variant", [r for r in fc.RUNS if r[0] in fc.ACCEPTED])
+def test_factored_forward_feature_range_by_hand(name, variant, mode):
+    """The factored forward and its backward on the hand-built graphs of
+    tests/factor_cases.py -- the documents' features in [k0, k0 + Kc) with
+    k0 = 37, 3 and 1 (W1's rows from k0; the dense X's light rows from a base 4
+    bytes off a 16-byte boundary), Kc = 1, 65 and 128, and documents with no
+    feature -- against the SpMM path (ops.FACTOR_GC1 = False), at a hidden width
+    the factored kernel accepts: the record of the factored run is FACTORED."""
+    from graph_convolutional_networks_for_text_classification_amd import factor, ops, record
+    c = fc.CONFIGS[name]
+    A, X = _by_hand_operands(name, variant)
+    xop = ops.Operand(X)
+    assert (xop.csr is None) == (variant == "dense")
+    f = factor.get(A, xop)
+    assert f is not None and (f.H, f.k0, f.Kc) == (fc.NTOPIC,) + c.expect
+    out6 = (ctypes.c_int64 * 6)()
+    assert _lib.load().gcnk_hubfactor_gc1_route(c.F, f.Kc, f.H, f.rec_words, c.P, f.U.stride(0),
+                                                int(f.U.data_ptr() % 16 == 0), out6) == _lib.OK
+    _factored_against_spmm(A, X, c.K, c.F, c.P, mode, (record.FACTORED,))
+
+
+@pytest.mark.parametrize("mode", ["eval", "train_hash"])
+def test_factored_forward_refused_for_lds_takes_the_spmm_path(mode):
+    """Kc = 128 at F = 256 with 26 hubs: the operands factor, the factored
+    kernel's block would take more than 160 KiB of LDS (the route report and
+    gcnk_hubfactor_lds_bytes agree), and the forward takes an SpMM kind without
+    a word -- same logits and gradients as with the factor turned off."""
+    from graph_convolutional_networks_for_text_classification_amd import factor, ops, record
+    c = fc.CONFIGS["k0_1_kc128"]
+    F, P = 256, 8
+    A, X = _by_hand_operands("k0_1_kc128", "dense", wide=True)
+    f = factor.get(A, ops.Operand(X))
+    assert f is not None and (f.H, f.k0, f.Kc) == (fc.WIDE_NTOPIC, 1, 128)
+    out6 = (ctypes.c_int64 * 6)()
+    lib = _lib.load()
+    assert lib.gcnk_hubfactor_gc1_route(F, f.Kc, f.H, f.rec_words, P, f.U.stride(0), 1, out6) == _lib.EUNSUP
+    assert lib.gcnk_hubfactor_lds_bytes(F, f.Kc, f.H, f.rec_words, P) > 160 * 1024
+    assert lib.gcnk_hubfactor_gc1_route(64, f.Kc, f.H, f.rec_words, P, f.U.stride(0), 1, out6) == _lib.OK
+    _factored_against_spmm(A, X, c.K, F, P, mode, (record.SPMM_PROJ, record.SPMM_GEMM))
+
+
 # ------------------------------------------------------------------------------ narrow-feature gc1 (A-hat X cached)
 
 def _gensim_r8_x(r8):
@@ -1758,7 +1849,8 @@ def test_captured_per_op_graph_keeps_its_plans_after_an_in_place_change(inplace_
 
 # ------------------------------------------------------------------------------ device factor build
 
-@pytest.mark.parametrize("case", ["r8", "doc_topic_tt", "hubs_first_dense", "20ng"])
+@pytest.mark.parametrize("case", ["r8", "doc_topic_tt", "hubs_first_dense", "20ng"] +
+                         [f"hand-{n}-{v}" for n, v in fc.RUNS] + ["hand-k0_1_kc128-wide"])
 def test_device_factor_build_is_bitwise_the_host_build(r8, case):
     """factor.build (csrc/factor_build.hip: U as fixed-order float64 sums over
     each row's CSR items, the A_H block records by ballot compaction) against
@@ -1766,10 +1858,26 @@ def test_device_factor_build_is_bitwise_the_host_build(r8, case):
     k0, Kc, row order), U bit for bit after the one fp32 rounding, the records
     word for word and X's hub rows -- on R8, a doc-topic graph with
     topic-topic edges, a renumbered graph with the hubs first, a ragged M and
-    dense X, and the 20ng-shaped graph (70 hubs, BASELINE config 3)."""
+    dense X, and the 20ng-shaped graph (70 hubs, BASELINE config 3); and on the
+    hand-built graphs of tests/factor_cases.py (k0 > 0, Kc = 1, 65, 128, no
+    document features, explicit zeros outside the range, each with a dense and
+    a CSR X; Kc = 129 refused by both builds)."""
     from graph_convolutional_networks_for_text_classification_amd import factor, ops
     from graph_convolutional_networks_for_text_classification_amd.sparse import as_csr
     from oracle import factor_host
+    if case.startswith("hand-"):
+        _, name, variant = case.split("-")
+        a, X = _by_hand_operands(name, "dense" if variant == "wide" else variant, wide=variant == "wide")
+        xop = ops.Operand(X)
+        assert (xop.csr is None) == (variant in ("dense", "wide"))
+        expect = fc.CONFIGS[name].expect
+        if expect is None:
+            assert factor.build(a, xop) is None and factor_host.build(a, xop) is None
+            return
+        _device_build_equals_host_build(a, xop, X if xop.csr is None else None)
+        h = factor_host.build(a, xop)
+        assert (h.H, h.k0, h.Kc) == (fc.WIDE_NTOPIC if variant == "wide" else fc.NTOPIC,) + expect
+        return
     if case == "r8":
         A, X = r8["adj"], r8["features"]
     elif case == "doc_topic_tt":
@@ -1790,6 +1898,12 @@ def test_device_factor_build_is_bitwise_the_host_build(r8, case):
     a = as_csr(A.to(DEV))
     xop = ops.Operand(X.to(DEV))
     Xd = X.to_dense() if X.is_sparse else X      # (a dense-enough sparse X becomes a dense operand)
+    _device_build_equals_host_build(a, xop, Xd)
+
+
+def _device_build_equals_host_build(a, xop, Xd):
+    from graph_convolutional_networks_for_text_classification_amd import factor
+    from oracle import factor_host
     d = factor.build(a, xop)
     torch.cuda.synchronize()
     h = factor_host.build(a, xop)
@@ -1806,4 +1920,4 @@ def test_device_factor_build_is_bitwise_the_host_build(r8, case):
         assert np.array_equal(d.x_hub.colind.cpu().numpy(), h.x_hub_colind)
         assert np.array_equal(d.x_hub.val.cpu().numpy().view(np.int32), h.x_hub_val.view(np.int32))
     else:
-        assert torch.equal(d.x_hub_dense.cpu(), Xd[torch.from_numpy(h.hubs)])
+        assert torch.equal(d.x_hub_dense.cpu(), Xd.cpu()[torch.from_numpy(h.hubs)])

@@ -13,78 +13,37 @@ tail word would give a NaN or miss the float64 result.  F = 200, 52 and 36
 also take the three ways the kernel deals its MFMA n-tiles over the waves (all
 slots real or one short; some waves with no real tile).
 
-Operands are made by hand (block record layout of csrc/factor.hip: 33 item
+Operands are made by hand (tests/hubfactor_cases.py operands(), shared with
+tests/test_hubfactor_routes.py; block record layout of csrc/factor.hip: 33 item
 offsets, 3 pad words, 32 output row ids with -1 past M, then int2 {hub, value}
 items; rec_words the common stride, a multiple of 4), so the expected values
 come from the same arrays in float64 numpy and no row is left out.
 """
 import ctypes
+import os
+import sys
 
 import numpy as np
 import pytest
 import torch
 
-import gcn_amd  # noqa: F401
-from graph_convolutional_networks_for_text_classification_amd import _lib
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import hubfactor_cases as hc  # noqa: E402
+
+import gcn_amd  # noqa: E402,F401
+from graph_convolutional_networks_for_text_classification_amd import _lib  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
-M = 70                       # three 32-row blocks, the last with 6 real rows
-ROWS, REC_ROW, REC_HEAD = 32, 36, 68
-COUNTS = [0, 1, 2, 3, 4, 5, 7, 8, 9, 16, 17, 0]   # ..., 17, 0, 0, 1, ... down a block
-LONG_POS, LONG_ITEMS = 32 + 13, 200               # the long row: middle block, followed by an empty row
+M, K0 = hc.M, hc.K0          # three 32-row blocks, the last with 6 real rows
 GUARD = 8                    # sentinel rows before and after the outputs
 SENTINEL = -12345.0
-NAN_BITS = np.int32(0x7FC00000)
-K0 = 3
 
 
 def _operands(nhub, Kc, F, P):
-    rng = np.random.default_rng(1000 * nhub + 10 * Kc + F + P)
-    perm = rng.permutation(M)                      # position in block order -> output row
-    assert not np.array_equal(perm, np.arange(M))
-    nblk = (M + ROWS - 1) // ROWS
-    counts = np.array([COUNTS[(p % ROWS) % len(COUNTS)] for p in range(nblk * ROWS)])
-    counts[M:] = 0                                 # rows past M hold nothing
-    counts[LONG_POS] = LONG_ITEMS
-    counts[LONG_POS + 1] = 0                       # an empty row right after the long one
-    counts[2 * ROWS - 1] = 0                       # and one as that block's last row
-    hubs = [rng.integers(0, nhub, c) for c in counts]             # repeated hubs allowed
-    vals = [rng.uniform(-1.0, 1.0, c).astype(np.float32) for c in counts]
-    per_block = counts.reshape(nblk, ROWS).sum(1)
-    rec_words = (REC_HEAD + 2 * int(per_block.max()) + 3) // 4 * 4 + 4   # every record keeps a tail
-    rec = np.full((nblk, rec_words), NAN_BITS, np.int32)
-    for b in range(nblk):
-        off = np.concatenate([[0], np.cumsum(counts[b * ROWS:(b + 1) * ROWS])])
-        rec[b, :ROWS + 1] = off
-        rec[b, ROWS + 1:REC_ROW] = 0
-        ids = np.full(ROWS, -1, np.int64)
-        real = min(ROWS, M - b * ROWS)
-        ids[:real] = perm[b * ROWS:b * ROWS + real]
-        rec[b, REC_ROW:REC_HEAD] = ids
-        h = np.concatenate(hubs[b * ROWS:(b + 1) * ROWS]).astype(np.int32)
-        v = np.concatenate(vals[b * ROWS:(b + 1) * ROWS]).astype(np.float32)
-        rec[b, REC_HEAD:REC_HEAD + 2 * len(h):2] = h
-        rec[b, REC_HEAD + 1:REC_HEAD + 2 * len(h):2] = v.view(np.int32)
     # U's leading dimension: a multiple of 4 (rows staged in LDS) or odd (fragments loaded directly)
-    ldu = Kc + 2 if nhub == 7 else Kc + 1
-    U = np.zeros((M, ldu), np.float32)
-    U[:, :Kc] = rng.standard_normal((M, Kc)) * 0.3
-    U[:, Kc:] = np.nan                             # columns past Kc are not the kernel's to read into Z
-    W1 = rng.standard_normal((K0 + Kc + 5, F)).astype(np.float32)
-    S = rng.standard_normal((nhub, F)).astype(np.float32)
-    b1 = rng.standard_normal(F).astype(np.float32)
-    W2 = rng.standard_normal((F, P)).astype(np.float32)
-    # float64 from the same arrays, rows in output order
-    Z = np.zeros((M, F))
-    UW = U[:, :Kc].astype(np.float64) @ W1[K0:K0 + Kc].astype(np.float64)
-    for pos in range(M):
-        z = UW[pos].copy()
-        for hcol, val in zip(hubs[pos], vals[pos]):
-            z += np.float64(val) * S[hcol].astype(np.float64)
-        Z[perm[pos]] = z
-    return dict(rec=rec, rec_words=rec_words, ldu=ldu, U=U, W1=W1, S=S, b1=b1, W2=W2, Z=Z)
+    return hc.operands(nhub, Kc, F, P, Kc + 2 if nhub == 7 else Kc + 1)
 
 
 @pytest.mark.parametrize("P", [8, 20])
