@@ -78,6 +78,29 @@ class KeepState(ctypes.Structure):
     _fields_ = [("seen", _i32), ("best", _i32), ("arrivals", _i32), ("copies", _i32)]
 
 
+class LaunchTables:
+    """The host tensor tables of a multi-tensor entry point (gcnk_adam_f32,
+    gcnk_keep_best_f32): rows of the ctypes ``struct`` (a tensor's pointers,
+    then ``numel``), at most ``per_call`` of them a launch."""
+
+    def __init__(self, struct, per_call):
+        self.struct, self.per_call, self._cache = struct, per_call, {}   # launch -> (pointers, struct array)
+        self.clear = self._cache.clear
+
+    def launches(self, ptrs, numels, first=0, last=True):
+        """[(table, rows, hold)] for the tensors with pointer tuples ``ptrs``, the
+        launches numbered from ``first``; a table is rebuilt only when one of
+        its pointers changed.  ``hold`` (the entry point's HOLD flag is due): on
+        every launch but the last, and on that too unless ``last``."""
+        out = []
+        for i in range(0, len(ptrs), self.per_call):
+            key, li = tuple(ptrs[i:i + self.per_call]), first + len(out)
+            if self._cache.get(li, (None,))[0] != key:
+                self._cache[li] = (key, (self.struct * len(key))(*[(*p, n) for p, n in zip(key, numels[i:])]))
+            out.append((self._cache[li][1], len(key), not last or i + self.per_call < len(ptrs)))
+        return out
+
+
 def epoch_row_words(nclass):
     """gcnk.h GCNK_EPOCH_ROW_WORDS: train_loss | val_loss | TP | FP | FN | correct"""
     return 3 * nclass + 3
@@ -273,6 +296,12 @@ def load():
             raise RuntimeError(f"libgcnk ABI version {v} != expected {ABI_VERSION}")
         _lib = lib
         return lib
+
+
+def stream(device):
+    """The current stream of ``device`` as the ``void* stream`` every launch takes."""
+    import torch
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 def check(rc, what):

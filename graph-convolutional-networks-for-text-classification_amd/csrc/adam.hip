@@ -7,12 +7,9 @@
 // is one pass: read p, g, m, v, write p, m, v (28 B per element, the compulsory traffic).
 // The contract -- the arithmetic, its roundings, the step word -- is in include/gcnk.h.
 //
-// Work is cut into chunks of GCNK_ADAM_CHUNK elements; a prefix table in the kernel's
-// arguments maps a workgroup to (tensor, chunk).  A tensor whose four buffers sit at the
-// same offset from a 16-B boundary has a scalar head of up to 3 elements in its chunk 0
-// and 16-B accesses from there on (a chunk's ragged tail is scalar again); a tensor whose
-// buffers disagree is all scalar.
+// Work is cut into chunks of GCNK_ADAM_CHUNK elements by tensor_chunks.h's table.
 #include "gcnk_common.h"
+#include "tensor_chunks.h"
 
 #include <cmath>
 
@@ -24,8 +21,7 @@ constexpr int kMaxTensors = GCNK_ADAM_MAX_TENSORS;
 
 struct AdamArgs {
   gcnk_adam_tensor t[kMaxTensors];
-  int32_t first[kMaxTensors + 1];   // first[i]: the first workgroup of tensor i; first[nt ..] = all chunks
-  int32_t head[kMaxTensors];        // scalar elements in front of the 16-B aligned body; -1: all scalar
+  chunks::Table<kMaxTensors> tab;
   double lr, beta1, beta2;
   float omb1, b2, omb2, eps, wd;   // fp32( beta2 ), fp32( 1 - beta ) formed in float64
   int32_t zero_grad, advance;
@@ -53,10 +49,8 @@ __global__ void __launch_bounds__(256) adam_kernel(const AdamArgs a, int32_t* __
   const int tid = threadIdx.x;
   const int32_t blk = blockIdx.x;
   // The step word: read at entry by one lane (the load is in flight while the chunk's own loads are
-  // issued).  After the barrier below that lane -- its load of t complete -- counts this workgroup in;
-  // the last of the launch's workgroups to arrive knows every other has read t, and only then stores
-  // t + 1 (and leaves the counter zero for the next call): a workgroup that starts late still reads t.
-  // Nothing else passes between workgroups.
+  // issued).  After the barrier below that lane counts this workgroup in, and the last to arrive stores
+  // t + 1 (arrive_last, gcnk_common.h).  Nothing else passes between workgroups.
   // The gate (gcnk_adam_gated_f32): a word an earlier launch on the stream wrote, so every workgroup of
   // this launch reads the same value; read by the same lane and broadcast with the step factors.  Closed,
   // the workgroup returns behind the barrier having stored nothing and counted itself in nowhere.
@@ -66,35 +60,31 @@ __global__ void __launch_bounds__(256) adam_kernel(const AdamArgs a, int32_t* __
     if (gate) closed = __hip_atomic_load(gate, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 
-  // (tensor, chunk) of this workgroup: selected without indexing the argument block dynamically
+  // this workgroup's tensor, selected here (tensor_chunks.h: a shared helper doing it cost scratch, or keep's time)
   float *p = a.t[0].p, *g = a.t[0].g, *m = a.t[0].m, *v = a.t[0].v;
   int64_t numel = a.t[0].numel;
-  int32_t first = 0, head = a.head[0];
+  int32_t first = 0, head = a.tab.head[0];
 #pragma unroll
   for (int i = 1; i < kMaxTensors; ++i)
-    if (blk >= a.first[i]) {
+    if (blk >= a.tab.first[i]) {
       p = a.t[i].p; g = a.t[i].g; m = a.t[i].m; v = a.t[i].v;
       numel = a.t[i].numel;
-      first = a.first[i];
-      head = a.head[i];
+      first = a.tab.first[i];
+      head = a.tab.head[i];
     }
-  const bool work = blk < a.first[kMaxTensors];   // (a launch of empty tensors only advances the step)
-  const int32_t chunk = blk - first;
+  // (without work, a launch of empty tensors only, the step still advances)
+  const chunks::Span<kChunk> s(blk - first, head, blk < a.tab.first[kMaxTensors], numel);
 
   // the 16-B aligned body of the chunk, loaded before the step factors are known
-  const int64_t e0 = (int64_t)(head < 0 ? 0 : head) + (int64_t)chunk * kChunk;   // 16-B aligned in all four buffers
-  const int64_t e1 = min(e0 + (int64_t)kChunk, numel);
-  const int32_t len = work && e1 > e0 ? (int32_t)(e1 - e0) : 0;
-  const int32_t n4 = head < 0 ? 0 : len / 4;
-  float4* p4 = reinterpret_cast<float4*>(p + e0);
-  float4* g4 = reinterpret_cast<float4*>(g + e0);
-  float4* m4 = reinterpret_cast<float4*>(m + e0);
-  float4* v4 = reinterpret_cast<float4*>(v + e0);
+  float4* p4 = reinterpret_cast<float4*>(p + s.e0);
+  float4* g4 = reinterpret_cast<float4*>(g + s.e0);
+  float4* m4 = reinterpret_cast<float4*>(m + s.e0);
+  float4* v4 = reinterpret_cast<float4*>(v + s.e0);
   float4 pe[2], ge[2], me[2], ve[2];
 #pragma unroll
   for (int it = 0; it < 2; ++it) {
     const int32_t i = tid + 256 * it;
-    if (i < n4) {
+    if (i < s.n4) {
       pe[it] = p4[i]; ge[it] = g4[i]; me[it] = m4[i]; ve[it] = v4[i];
     }
   }
@@ -108,31 +98,28 @@ __global__ void __launch_bounds__(256) adam_kernel(const AdamArgs a, int32_t* __
   }
   __syncthreads();
   if (__float_as_int(s_step[2]) != 0) return;
-  if (tid == 0 && a.advance) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // t has been read before this workgroup is counted in
-    const int32_t arrived = __hip_atomic_fetch_add(state + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (arrived == (int32_t)gridDim.x - 1) {
-      __hip_atomic_store(state + 1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(state, t + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+  if (tid == 0 && a.advance && arrive_last(state + 1)) {
+    __hip_atomic_store(state + 1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(state, t + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
-  if (!work) return;
+  if (!s.work) return;
   const Coef k = {a.omb1, a.b2, a.omb2, a.eps, a.wd, s_step[0], s_step[1]};
 
-  if (head < 0) {   // buffers at different offsets from a 16-B boundary: scalar
-    for (int64_t e = e0 + tid; e < e1; e += 256) {
-      float ps = p[e], ms = m[e], vs = v[e];
-      const float gs = g[e];
-      adam_elem(k, ps, gs, ms, vs);
-      p[e] = ps; m[e] = ms; v[e] = vs;
-      if (a.zero_grad) g[e] = 0.f;
-    }
+  auto scalar = [&](int64_t e) {
+    float ps = p[e], ms = m[e], vs = v[e];
+    const float gs = g[e];
+    adam_elem(k, ps, gs, ms, vs);
+    p[e] = ps; m[e] = ms; v[e] = vs;
+    if (a.zero_grad) g[e] = 0.f;
+  };
+  if (s.head < 0) {   // buffers at different offsets from a 16-B boundary: scalar
+    for (int64_t e = s.e0 + tid; e < s.e1; e += 256) scalar(e);
     return;
   }
 #pragma unroll
   for (int it = 0; it < 2; ++it) {
     const int32_t i = tid + 256 * it;
-    if (i < n4) {
+    if (i < s.n4) {
       adam_elem(k, pe[it].x, ge[it].x, me[it].x, ve[it].x);
       adam_elem(k, pe[it].y, ge[it].y, me[it].y, ve[it].y);
       adam_elem(k, pe[it].z, ge[it].z, me[it].z, ve[it].z);
@@ -141,17 +128,8 @@ __global__ void __launch_bounds__(256) adam_kernel(const AdamArgs a, int32_t* __
       if (a.zero_grad) g4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
   }
-  // the scalar head in front of chunk 0's aligned body, and the chunk's ragged tail
-  int64_t e = -1;
-  if (chunk == 0 && tid < head && tid < numel) e = tid;
-  else if (tid >= 32 && tid - 32 < len - 4 * n4) e = e0 + 4 * (int64_t)n4 + (tid - 32);
-  if (e >= 0) {
-    float ps = p[e], ms = m[e], vs = v[e];
-    const float gs = g[e];
-    adam_elem(k, ps, gs, ms, vs);
-    p[e] = ps; m[e] = ms; v[e] = vs;
-    if (a.zero_grad) g[e] = 0.f;
-  }
+  const int64_t e = s.edge(tid);
+  if (e >= 0) scalar(e);
 }
 
 }  // namespace
@@ -178,27 +156,19 @@ static int adam_launch(const char* who, const gcnk_adam_tensor* t, int32_t ntens
     return GCNK_EARG;
   }
   AdamArgs a = {};
-  int64_t chunks = 0;
+  int64_t nchunks = 0;
   for (int i = 0; i < ntensors; ++i) {
     const gcnk_adam_tensor& x = t[i];
     if (x.numel < 0 || (x.numel > 0 && (!x.p || !x.g || !x.m || !x.v))) {
       set_error("%s: tensor %d: null buffer or numel < 0 (numel=%lld)", who, i, (long long)x.numel);
       return GCNK_EARG;
     }
-    const uintptr_t off = reinterpret_cast<uintptr_t>(x.p) & 15u;
-    const bool same = (reinterpret_cast<uintptr_t>(x.g) & 15u) == off && (reinterpret_cast<uintptr_t>(x.m) & 15u) == off &&
-                      (reinterpret_cast<uintptr_t>(x.v) & 15u) == off && off % 4 == 0;
     a.t[i] = x;
-    a.first[i] = (int32_t)chunks;
-    a.head[i] = same ? (int32_t)(((16 - off) & 15u) / 4) : -1;
-    const int64_t body = same ? (x.numel > a.head[i] ? x.numel - a.head[i] : 0) : x.numel;
-    chunks += x.numel > 0 ? (body + kChunk - 1) / kChunk + (body == 0 ? 1 : 0) : 0;
-    if (chunks > INT32_MAX) {
+    if (!chunks::append<kChunk>(a.tab, i, x.numel, chunks::head_of({x.p, x.g, x.m, x.v}), nchunks)) {
       set_error("%s: more than 2^31 chunks in one call", who);
       return GCNK_EARG;
     }
   }
-  for (int i = ntensors; i <= kMaxTensors; ++i) a.first[i] = (int32_t)chunks;
   a.lr = lr;
   a.beta1 = beta1;
   a.beta2 = beta2;
@@ -209,8 +179,8 @@ static int adam_launch(const char* who, const gcnk_adam_tensor* t, int32_t ntens
   a.wd = (float)weight_decay;
   a.zero_grad = (flags & GCNK_ADAM_ZERO_GRAD) ? 1 : 0;
   a.advance = (flags & GCNK_ADAM_HOLD_STEP) ? 0 : 1;
-  if (chunks == 0 && !a.advance) return GCNK_OK;
-  hipLaunchKernelGGL(adam_kernel, dim3((unsigned)(chunks > 0 ? chunks : 1)), dim3(256), 0, (hipStream_t)stream, a,
+  if (nchunks == 0 && !a.advance) return GCNK_OK;
+  hipLaunchKernelGGL(adam_kernel, dim3((unsigned)(nchunks > 0 ? nchunks : 1)), dim3(256), 0, (hipStream_t)stream, a,
                      state, gate);
   return launch_check("adam_kernel");
 }

@@ -14,14 +14,11 @@
 // set, a launch writes nothing: epochs queued past the stop are no-ops, and `stopped` is
 // the gate gcnk_adam_gated_f32 reads.
 //
-// Between workgroups there is one hand-off and no wait: a workgroup's partial is stored
-// agent-coherently by one lane, which drains its stores (s_waitcnt vmcnt(0)) and then adds
-// to the agent-scope arrival counter in the state; the workgroup whose add returned
-// gridDim.x - 1 is the last, and reads the partials with agent-coherent loads behind a
-// workgroup barrier that lane has joined (spmm.hip's hand-off of partial slots).  The
-// state's epoch and stopped words are read by every workgroup at entry and written only by
-// the last arriver, after every workgroup's read has completed (the same drain), as
-// adam_kernel treats its step word.
+// Between workgroups there is one hand-off and no wait (arrive_last, gcnk_common.h): a
+// workgroup's partial is stored agent-coherently by the lane that then counts it in; the
+// last to arrive reads the partials with agent-coherent loads behind a workgroup barrier
+// that lane has joined.  The state's epoch and stopped words are read by every workgroup at
+// entry, by that same lane, and written only by the last arriver.
 #include "ce_row.h"
 
 namespace gcnk {
@@ -114,10 +111,7 @@ epoch_tail_kernel(const float* __restrict__ logits, int64_t ld, int32_t M, int32
   }
   if (tid == 0) {
     __hip_atomic_store(part + blockIdx.x, s_w[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    // the partial stored and the state words read before this workgroup is counted in
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const int32_t arrived = __hip_atomic_fetch_add(&state->arrivals, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    s_word[2] = arrived == (int32_t)gridDim.x - 1;
+    s_word[2] = arrive_last(&state->arrivals);
   }
   __syncthreads();
   int32_t* row = history + (int64_t)e * (3 * (int64_t)P + 3);

@@ -47,6 +47,21 @@ inline hipError_t dyn_lds_attr(std::atomic<uint64_t>& done, const void* fn, int 
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// The hand-off of a launch whose workgroups all read (or store) something that only the last
+// of them may then overwrite (or read): called by the ONE lane of a workgroup that issued
+// those loads / stores, it counts the workgroup in on `counter` (zero at entry) and returns
+// whether it arrived last.  The drain comes first: the relaxed agent-scope add orders nothing
+// by itself, and s_waitcnt vmcnt(0) holds it back until that lane's vector-memory loads have
+// returned and its stores are acknowledged.  So the workgroup whose add returns gridDim.x - 1
+// knows every other has read its words -- a workgroup that starts late still reads the old
+// ones -- and that every partial stored agent-coherently before the call can be read with
+// agent-coherent loads.  No workgroup waits.  The last arriver resets the counter with its
+// own stores.  (spmm.hip's wave-level hand-off of partial slots is a different structure.)
+__device__ __forceinline__ bool arrive_last(int32_t* counter) {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  return __hip_atomic_fetch_add(counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (int32_t)gridDim.x - 1;
+}
+
 // ----------------------------------------------------------------------------
 // Epilogue parameters for SpMM (row-complete elements).
 struct Epi {

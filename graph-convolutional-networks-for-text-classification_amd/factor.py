@@ -139,15 +139,13 @@ def build(adj, xop):
     (csrc/factor_build.hip: fixed-order float64 sums, bitwise the host
     restatement oracle/factor_host.py).  No torch kernel runs here: their
     first-use module loads were ~120 ms of the first forward (round 5)."""
-    import ctypes
-
     from . import _lib
     M, K = adj.shape
     if M != K or xop.shape[0] != M:
         return None
     dev = adj.device
     lib = _lib.load()
-    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    stream = _lib.stream(dev)
     nnz = adj.nnz
     hmin = max(64, 8 * ((nnz + M - 1) // M))
     x = xop.csr

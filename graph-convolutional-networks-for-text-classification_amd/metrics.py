@@ -8,8 +8,6 @@ counts come from one gcnk_class_stats launch and one device->host copy
 instead of 3 * nclass + 1 ``.item()`` syncs.  ``evaluate`` returns all four
 from a single launch (what TopicGCNTrainer.val computes, trainer.py:378-398).
 """
-import ctypes
-
 import numpy as np
 import torch
 
@@ -34,7 +32,7 @@ def class_stats(pred, targ, idx=None, out=None):
     with torch.cuda.device(pred.device):
         _lib.check(lib.gcnk_class_stats(pred.data_ptr(), pred.stride(0), targ.data_ptr(),
                                         idx.data_ptr() if idx is not None else None, n, nclass, counts.data_ptr(),
-                                        ctypes.c_void_p(torch.cuda.current_stream(pred.device).cuda_stream)),
+                                        _lib.stream(pred.device)),
                    "gcnk_class_stats")
     return counts
 

@@ -21,8 +21,7 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else _NULL
 
 
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+_stream = _lib.stream
 
 
 def _dense_f32(t, what):

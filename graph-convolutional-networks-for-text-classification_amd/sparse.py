@@ -26,10 +26,6 @@ from .derived import Cache, stamp
 _INT32_MAX = 2**31 - 1
 
 
-def _stream_ptr(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
 def require_device(t, what):
     if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
         dev = getattr(t, "device", type(t))
@@ -182,7 +178,7 @@ class CSR:
         lib = _lib.load()
         M, K = self.shape
         with torch.cuda.device(self.device):
-            s = _stream_ptr(self.device)
+            s = _lib.stream(self.device)
             nbytes = lib.gcnk_spmm_plan_bytes(self.rowptr.data_ptr(), self.colind.data_ptr(), M, K, self.nnz,
                                               ipc, groups, dense_threshold, s)
             if nbytes < 0:
@@ -221,7 +217,7 @@ def transpose(a):
     with torch.cuda.device(dev):
         _lib.check(lib.gcnk_csr_transpose(a.rowptr.data_ptr(), a.colind.data_ptr(), a.val.data_ptr(), M, K, a.nnz,
                                           rp_t.data_ptr(), ci_t.data_ptr(), v_t.data_ptr(), ws.data_ptr(), wsb,
-                                          _stream_ptr(dev)), "gcnk_csr_transpose")
+                                          _lib.stream(dev)), "gcnk_csr_transpose")
     return CSR(rp_t, ci_t, v_t, (K, M))
 
 
@@ -267,7 +263,7 @@ def from_torch(t):
     with torch.cuda.device(dev):
         _lib.check(lib.gcnk_coo_to_csr(rows.data_ptr(), cols.data_ptr(), vals.data_ptr(), nnz_in, M, K,
                                        rowptr.data_ptr(), colind.data_ptr(), val.data_ptr(), ws.data_ptr(), wsb,
-                                       _stream_ptr(dev)), "gcnk_coo_to_csr")
+                                       _lib.stream(dev)), "gcnk_coo_to_csr")
     nnz = int(rowptr[M])   # one-time setup sync
     if nnz < 0:
         raise RuntimeError(f"sparse COO operand has an index outside its shape {tuple(t.shape)}")
@@ -313,7 +309,7 @@ def preprocess_adj(adj):
     with torch.cuda.device(dev):
         _lib.check(lib.gcnk_sym_normalize(a.rowptr.data_ptr(), a.colind.data_ptr(), a.val.data_ptr(), n, a.nnz,
                                           rp.data_ptr(), ci.data_ptr(), v.data_ptr(), ws.data_ptr(), wsb,
-                                          _stream_ptr(dev)), "gcnk_sym_normalize")
+                                          _lib.stream(dev)), "gcnk_sym_normalize")
     nnz = int(rp[n])   # one-time setup sync
     return CSR(rp, ci[:nnz], v[:nnz], (n, n))
 

@@ -31,7 +31,6 @@ best epoch on the device (``BestKeeper``, gcnk_keep_best_f32: the checkpoint
 utils.py:244 / :254 leave commented out) and ``fit`` ends on those.
 """
 import collections
-import ctypes
 
 import numpy as np
 import torch
@@ -40,8 +39,14 @@ from . import _lib, derived
 from .sparse import require_device
 
 
-def _stream(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+def _workspace(query, what, device, M, P, ws=None):
+    """(float64 workspace, its bytes) for the size ``query(M, P)``; ``ws`` is reused when large enough."""
+    nb = query(M, P)
+    if nb < 0:
+        _lib.check(int(nb), what)
+    if ws is None or ws.numel() * 8 < nb:
+        ws = torch.empty(max(1, nb // 8), dtype=torch.float64, device=device)
+    return ws, nb
 
 
 class RowCounts:
@@ -57,13 +62,18 @@ class RowCounts:
 _COUNTS = derived.Cache(capacity=16)
 
 
+def _counts_n(rc, M):
+    """(counts pointer, n) of a RowCounts; of every one of M rows once for None."""
+    return (rc.counts.data_ptr(), rc.n) if rc is not None else (None, M)
+
+
 def _build_counts(idx, M, T, device):
     i = idx.to(device=device, dtype=torch.int64).contiguous().view(-1)
     # counted over the T <= M rows that have a label: the rows past them stay 0 (never scored, so their
     # missing labels are never read), and counts[T] collects the entries outside [0, T)
     counts = torch.zeros(M + 1, dtype=torch.int32, device=device)
     with torch.cuda.device(device):
-        _lib.check(_lib.load().gcnk_ce_row_counts(i.data_ptr(), i.numel(), T, counts.data_ptr(), _stream(device)),
+        _lib.check(_lib.load().gcnk_ce_row_counts(i.data_ptr(), i.numel(), T, counts.data_ptr(), _lib.stream(device)),
                    "gcnk_ce_row_counts")
     bad = int(counts[T].item())   # the one-time synchronising check, like a plan build
     if bad:
@@ -95,15 +105,11 @@ def _forward(logits, target, rc, want_lse, loss=None):
     if M == 0:
         return loss.fill_(float("nan")), None
     lse = torch.empty(M, dtype=torch.float32, device=dev) if want_lse else None
-    nb = lib.gcnk_ce_workspace_bytes(M, P)
-    if nb < 0:
-        _lib.check(int(nb), "gcnk_ce_workspace_bytes")
-    ws = torch.empty(max(1, nb // 8), dtype=torch.float64, device=dev)
+    ws, nb = _workspace(lib.gcnk_ce_workspace_bytes, "gcnk_ce_workspace_bytes", dev, M, P)
     with torch.cuda.device(dev):
         _lib.check(lib.gcnk_ce_forward_f32(
-            logits.data_ptr(), logits.stride(0), M, P, target.data_ptr(),
-            rc.counts.data_ptr() if rc is not None else None, rc.n if rc is not None else M,
-            loss.data_ptr(), lse.data_ptr() if lse is not None else None, ws.data_ptr(), nb, _stream(dev)),
+            logits.data_ptr(), logits.stride(0), M, P, target.data_ptr(), *_counts_n(rc, M),
+            loss.data_ptr(), lse.data_ptr() if lse is not None else None, ws.data_ptr(), nb, _lib.stream(dev)),
             "gcnk_ce_forward_f32")
     return loss, lse
 
@@ -129,9 +135,8 @@ class _CrossEntropyFn(torch.autograd.Function):
         g = grad_out.to(device=dev, dtype=torch.float32).contiguous()
         with torch.cuda.device(dev):
             _lib.check(_lib.load().gcnk_ce_backward_f32(
-                logits.data_ptr(), logits.stride(0), M, P, target.data_ptr(),
-                rc.counts.data_ptr() if rc is not None else None, rc.n if rc is not None else M,
-                lse.data_ptr(), g.data_ptr(), dlogits.data_ptr(), P, _stream(dev)),
+                logits.data_ptr(), logits.stride(0), M, P, target.data_ptr(), *_counts_n(rc, M),
+                lse.data_ptr(), g.data_ptr(), dlogits.data_ptr(), P, _lib.stream(dev)),
                 "gcnk_ce_backward_f32")
         return dlogits, None, None, None
 
@@ -204,7 +209,7 @@ class Adam(torch.optim.Optimizer):
         self.gate = gate
         self._step_word = None    # int32 [4] on the device: steps taken, arrival counter, padding
         self._with_grad = None    # ids of the parameters that carried gradients at the first step
-        self._tables = {}         # (group, launch) -> (pointers, AdamTensor array)
+        self._tables = _lib.LaunchTables(_lib.AdamTensor, _lib.ADAM_MAX_TENSORS)
 
     # -- the device step word -------------------------------------------------------------------
     def _word(self, device):
@@ -254,35 +259,26 @@ class Adam(torch.optim.Optimizer):
         dev = work[0][2][0].device
         word = self._word(dev)
         lib = _lib.load()
-        launches = [(gi, group, ps[i:i + _lib.ADAM_MAX_TENSORS])
-                    for gi, group, ps in work for i in range(0, len(ps), _lib.ADAM_MAX_TENSORS)]
         zero = _lib.ADAM_ZERO_GRAD if self.zero_grad_in_step else 0
         gate = self.gate
         if gate is not None and (not isinstance(gate, torch.Tensor) or gate.device != dev or gate.dtype != torch.int32
                                  or gate.numel() < 1):
             raise ValueError("train.Adam: gate must be an int32 tensor on the parameters' device")
         with torch.cuda.device(dev):
-            stream = _stream(dev)
-            for li, (gi, group, ps) in enumerate(launches):
-                sts = [self._state_of(p) for p in ps]
-                ptrs = tuple(x for p, st in zip(ps, sts)
-                             for x in (p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(),
-                                       st["exp_avg_sq"].data_ptr()))
-                cached = self._tables.get(li)
-                if cached is None or cached[0] != ptrs:   # rebuilt only when a pointer changed
-                    tab = (_lib.AdamTensor * len(ps))()
-                    for k, p in enumerate(ps):
-                        tab[k].p, tab[k].g, tab[k].m, tab[k].v = ptrs[4 * k:4 * k + 4]
-                        tab[k].numel = p.numel()
-                    cached = self._tables[li] = (ptrs, tab)
+            stream = _lib.stream(dev)
+            li = 0
+            for wi, (gi, group, ps) in enumerate(work):   # a launch holds tensors of one group: its coefficients
+                ptrs = [(p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr())
+                        for p, st in ((p, self._state_of(p)) for p in ps)]
                 b1, b2 = group["betas"]
-                hold = _lib.ADAM_HOLD_STEP if li + 1 < len(launches) else 0
-                args = (cached[1], len(ps), float(group["lr"]), float(b1), float(b2), float(group["eps"]),
-                        float(group["weight_decay"]), word.data_ptr(), zero | hold)
-                if gate is None:
-                    _lib.check(lib.gcnk_adam_f32(*args, stream), "gcnk_adam_f32")
-                else:   # every launch of the step, the HOLD_STEP ones included
-                    _lib.check(lib.gcnk_adam_gated_f32(*args, gate.data_ptr(), stream), "gcnk_adam_gated_f32")
+                coef = (float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]))
+                for tab, n, hold in self._tables.launches(ptrs, [p.numel() for p in ps], li, wi + 1 == len(work)):
+                    args = (tab, n, *coef, word.data_ptr(), zero | (_lib.ADAM_HOLD_STEP if hold else 0))
+                    if gate is None:
+                        _lib.check(lib.gcnk_adam_f32(*args, stream), "gcnk_adam_f32")
+                    else:   # every launch of the step, the HOLD_STEP ones included
+                        _lib.check(lib.gcnk_adam_gated_f32(*args, gate.data_ptr(), stream), "gcnk_adam_gated_f32")
+                    li += 1
         return loss
 
     # -- checkpoints in torch.optim.Adam's keys -------------------------------------------------
@@ -361,7 +357,7 @@ class EpochLog:
                 raise ValueError(f"EpochLog.record: logits [{tuple(logits.shape)}] on {logits.device}, expected "
                                  f"{self.nclass} classes on {self.device}")
             M, P = logits.shape
-            n = rc.n if rc is not None else M
+            counts, n = _counts_n(rc, M)
             if self._n is None:
                 self._n = n
             elif self._n != n:
@@ -372,18 +368,14 @@ class EpochLog:
                 if train_loss.dtype != torch.float32 or train_loss.numel() != 1:
                     raise ValueError("EpochLog.record: train_loss must be one fp32 value on the device")
             lib = _lib.load()
-            nb = lib.gcnk_epoch_tail_workspace_bytes(M, P)
-            if nb < 0:
-                _lib.check(int(nb), "gcnk_epoch_tail_workspace_bytes")
-            if self._ws is None or self._ws.numel() * 8 < nb:
-                self._ws = torch.empty(nb // 8, dtype=torch.float64, device=self.device)
+            self._ws, nb = _workspace(lib.gcnk_epoch_tail_workspace_bytes, "gcnk_epoch_tail_workspace_bytes",
+                                      self.device, M, P, self._ws)
             with torch.cuda.device(self.device):
                 _lib.check(lib.gcnk_epoch_tail_f32(
-                    logits.data_ptr(), logits.stride(0), M, P, target.data_ptr(),
-                    rc.counts.data_ptr() if rc is not None else None, n,
+                    logits.data_ptr(), logits.stride(0), M, P, target.data_ptr(), counts, n,
                     train_loss.data_ptr() if train_loss is not None else None,
                     self._state.data_ptr(), self._history.data_ptr(), self.max_epoch, self.patience, self.delta,
-                    self._ws.data_ptr(), self._ws.numel() * 8, _stream(self.device)), "gcnk_epoch_tail_f32")
+                    self._ws.data_ptr(), nb, _lib.stream(self.device)), "gcnk_epoch_tail_f32")
 
     def state(self):
         """The device state as a host _lib.EpochState (one 32-byte copy: synchronises)."""
@@ -433,7 +425,7 @@ class BestKeeper:
         self.log = log
         self.best = [torch.zeros_like(p, memory_format=torch.contiguous_format).detach() for p in self.params]
         self._state = torch.zeros(4, dtype=torch.int32, device=log.device)   # gcnk_keep_state: all-zero is initial
-        self._tables = {}   # launch -> (pointers, KeepTensor array)
+        self._tables = _lib.LaunchTables(_lib.KeepTensor, _lib.KEEP_MAX_TENSORS)
         log.keeper = self
 
     @torch.no_grad()
@@ -442,22 +434,12 @@ class BestKeeper:
         state) on the current stream."""
         lib = _lib.load()
         dev = self.log.device
-        n = _lib.KEEP_MAX_TENSORS
-        launches = [(self.params[i:i + n], self.best[i:i + n]) for i in range(0, len(self.params), n)]
+        ptrs = [(p.data_ptr(), b.data_ptr()) for p, b in zip(self.params, self.best)]
         with torch.cuda.device(dev):
-            stream = _stream(dev)
-            for li, (ps, bs) in enumerate(launches):
-                ptrs = tuple(x for p, b in zip(ps, bs) for x in (p.data_ptr(), b.data_ptr()))
-                cached = self._tables.get(li)
-                if cached is None or cached[0] != ptrs:   # rebuilt only when a pointer changed
-                    tab = (_lib.KeepTensor * len(ps))()
-                    for k, p in enumerate(ps):
-                        tab[k].src, tab[k].dst = ptrs[2 * k:2 * k + 2]
-                        tab[k].numel = p.numel()
-                    cached = self._tables[li] = (ptrs, tab)
-                hold = _lib.KEEP_HOLD_STATE if li + 1 < len(launches) else 0
-                _lib.check(lib.gcnk_keep_best_f32(cached[1], len(ps), self.log._state.data_ptr(),
-                                                  self._state.data_ptr(), hold, stream), "gcnk_keep_best_f32")
+            stream = _lib.stream(dev)
+            for tab, n, hold in self._tables.launches(ptrs, [p.numel() for p in self.params]):
+                _lib.check(lib.gcnk_keep_best_f32(tab, n, self.log._state.data_ptr(), self._state.data_ptr(),
+                                                  _lib.KEEP_HOLD_STATE if hold else 0, stream), "gcnk_keep_best_f32")
 
     def state(self):
         """The device state as a host _lib.KeepState (one 16-byte copy: synchronises)."""
@@ -590,13 +572,15 @@ def fit(model, features, adj, target, train_idx, val_idx, *, lr=0.02, max_epoch=
             keeper.restore()
         return FitResult(log.history(), epochs, reason, opt, log)
 
-    if not graph:
+    def run(one):   # the host queues poll_every epochs, then looks at the stop word once
         while True:
             for _ in range(poll_every):
-                epoch()
+                one()
             if log.poll()[1]:
                 return done()
 
+    if not graph:
+        return run(epoch)
     side = torch.cuda.Stream(dev)
     side.wait_stream(torch.cuda.current_stream(dev))
     with torch.cuda.stream(side):
@@ -608,9 +592,4 @@ def fit(model, features, adj, target, train_idx, val_idx, *, lr=0.02, max_epoch=
     with torch.cuda.graph(g):
         epoch()
     log.graph = g
-    # (the capture itself launched nothing: the first replay is epoch 1)
-    while True:
-        for _ in range(poll_every):
-            g.replay()
-        if log.poll()[1]:
-            return done()
+    return run(g.replay)   # (the capture itself launched nothing: the first replay is epoch 1)

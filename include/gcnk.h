@@ -677,9 +677,9 @@ int gcnk_ce_backward_f32(const float* logits, int64_t ld, int32_t M, int32_t P, 
  * word, once per workgroup); sqrt and the divisions are correctly rounded.
  * The step word: state[0] is the number of steps taken, on the DEVICE, so a
  * step captured in a hipGraph advances on every replay.  Every workgroup reads
- * it at entry; the word is advanced only after all workgroups of the launch
- * have read it, by the last to arrive at the counter state[1] (zero on entry,
- * left zero on return), so a workgroup that starts late never sees t + 1.
+ * it at entry; it is advanced by the last workgroup to arrive at the counter
+ * state[1] (zero on entry, left zero on return), after all have read it: THE
+ * ARRIVAL HAND-OFF, explained once at arrive_last in csrc/gcnk_common.h.
  * state: int32[2], used by one call at a time.
  * flags:
  *   GCNK_ADAM_ZERO_GRAD  also store +0.0 to g after reading it (trainer.py:359
@@ -689,11 +689,11 @@ int gcnk_ce_backward_f32(const float* logits, int64_t ld, int32_t M, int32_t P, 
  * GCNK_EARG (on the host, before any launch) for a NULL table, buffer or state,
  * numel < 0, ntensors outside [0, 8], beta outside [0, 1), lr, eps or
  * weight_decay < 0.  ntensors == 0 succeeds and does nothing.
- * Work is cut into chunks of GCNK_ADAM_CHUNK elements, one workgroup each:
- * 16-B accesses where a tensor's four buffers share their offset from a 16-B
- * boundary (a scalar head of up to 3 elements, a scalar ragged tail), scalar
- * otherwise.  28 B of traffic per element: an HBM-bound stream, to be judged
- * against gcnk_stream_copy_f32's rate.
+ * Work is cut into chunks of GCNK_ADAM_CHUNK elements, one workgroup each (THE
+ * CHUNK TABLE, csrc/tensor_chunks.h): 16-B accesses where a tensor's buffers
+ * share their offset from a 16-B boundary (a scalar head of up to 3 elements,
+ * a scalar ragged tail), scalar otherwise.  28 B of traffic per element: an
+ * HBM-bound stream, to be judged against gcnk_stream_copy_f32's rate.
  * ------------------------------------------------------------------------- */
 #define GCNK_ADAM_MAX_TENSORS 8
 #define GCNK_ADAM_CHUNK 2048
@@ -776,9 +776,9 @@ int gcnk_adam_gated_f32(const gcnk_adam_tensor* t /* host */, int32_t ntensors, 
  * The caller zeroes the state and the history (max_epoch rows) ONCE, before the
  * first launch of a run (all-zero is the initial state; the counts of row e are
  * added into it).  epoch and stopped are read by every workgroup at entry and
- * written only by the last arriver, after every workgroup has read them (as
- * gcnk_adam_f32's step word); `arrivals` is zero on entry and left zero.  One
- * launch at a time per state.  max_epoch, patience and delta are to be the same
+ * written only by the last arriver (gcnk_adam_f32's arrival hand-off, which
+ * here also hands over the partials); `arrivals` is zero on entry and left
+ * zero.  One launch at a time per state.  max_epoch, patience and delta are to be the same
  * in every launch of a run.
  *
  * 1 <= P <= 1024; workspace: gcnk_epoch_tail_workspace_bytes(M, P) bytes, 8-B
@@ -832,9 +832,9 @@ int gcnk_epoch_tail_f32(const float* logits, int64_t ld, int32_t M, int32_t P, c
  *              payloads, -0.0 and denormals are preserved).
  *   not copy:  no byte of any dst is written.
  * Without GCNK_KEEP_HOLD_STATE the last workgroup to arrive at state->arrivals
- * -- it knows that every other workgroup has read the three words -- stores
- * seen = epoch and, when copy, best = epoch (1 + the index of the epoch just
- * kept) and copies += 1; then arrivals = 0.  With GCNK_KEEP_HOLD_STATE the
+ * (gcnk_adam_f32's arrival hand-off) stores seen = epoch and, when copy,
+ * best = epoch (1 + the index of the epoch just kept) and copies += 1; then
+ * arrivals = 0.  With GCNK_KEEP_HOLD_STATE the
  * launch reads and decides the same way, touches no state word and counts in
  * nowhere: for every call but the last of one keep over more than 8 tensors.
  *
@@ -847,12 +847,9 @@ int gcnk_epoch_tail_f32(const float* logits, int64_t ld, int32_t M, int32_t P, c
  * initial).
  *
  * Work is cut into chunks of GCNK_KEEP_CHUNK elements, one workgroup (of 1,024
- * threads) each, found through a prefix table in the kernel's arguments
- * (gcnk_adam_f32's layout; the chunk is four times that step's, because what a
- * launch costs beyond its copy is one arrival per workgroup): 16-B accesses
- * where src and dst share their offset from a 16-B boundary (a scalar head of up
- * to 3 elements, a scalar ragged tail), all scalar where the offsets disagree.
- * A chunk's loads are issued after the decision: a launch that does not copy
+ * threads) each, by gcnk_adam_f32's chunk table (the chunk is four times that
+ * step's, because what a launch costs beyond its copy is one arrival per
+ * workgroup).  A chunk's loads are issued after the decision: a launch that does not copy
  * moves three words per workgroup.  dst is stored nontemporally (it is not read
  * again before a restore).  No allocation, no sync, no float atomics.
  *
