@@ -106,6 +106,10 @@ def epoch_row_words(nclass):
     return 3 * nclass + 3
 
 
+# the nine epilogue arguments of the entry points that end in the SpMM's fused epilogue:
+# bias, epilogue, drop_mask, ldm, drop_scale, keep_prob, seed, offset, rng_base
+_EPI_ARGS = [_vp, _i32, _vp, _i64, _f32, _f32, _u64, _u64, _vp]
+
 # name -> (restype, argtypes); every symbol include/gcnk.h declares
 SIGNATURES = {
     "gcnk_abi_version": (ctypes.c_int, []),
@@ -126,9 +130,7 @@ SIGNATURES = {
         _vp, _vp,                 # plan (device), plan header (host, 16 words)
         _vp, _i64, _i32,          # B, ldb, F
         _vp, _i64,                # C, ldc
-        _vp, _i32,                # bias, epilogue
-        _vp, _i64, _f32,          # drop_mask, ldm, drop_scale
-        _f32, _u64, _u64, _vp,    # keep_prob, seed, offset, rng_base
+        *_EPI_ARGS,
         _vp, _i64,                # workspace, workspace_bytes
         _vp, _i64,                # counters, counter_bytes
         _i32, _vp,                # lanes_hint, stream
@@ -137,9 +139,7 @@ SIGNATURES = {
         _vp, _vp,                 # plan (device), plan header (host, 16 words)
         _vp, _i64, _i32,          # B, ldb, F
         _vp, _i64,                # C, ldc
-        _vp, _i32,                # bias, epilogue
-        _vp, _i64, _f32,          # drop_mask, ldm, drop_scale
-        _f32, _u64, _u64, _vp,    # keep_prob, seed, offset, rng_base
+        *_EPI_ARGS,
         _vp, _i64,                # workspace, workspace_bytes
         _vp, _i64,                # counters, counter_bytes
         _i32, _i32, _vp,          # lanes_hint, part, stream
@@ -148,9 +148,7 @@ SIGNATURES = {
         _vp, _vp,                 # plan, plan header
         _vp, _i64, _i32,          # B, ldb, F
         _vp, _i64,                # C (nullable), ldc
-        _vp, _i32,                # bias, epilogue
-        _vp, _i64, _f32,          # drop_mask, ldm, drop_scale
-        _f32, _u64, _u64, _vp,    # keep_prob, seed, offset, rng_base
+        *_EPI_ARGS,
         _vp, _i64, _i32, _vp, _i64,  # W, ldw, P, C2, ldc2
         _vp, _i64,                # workspace, workspace_bytes
         _vp, _i64,                # counters, counter_bytes
@@ -183,9 +181,7 @@ SIGNATURES = {
         _i32, _i32, _i32, _i32, _i32,     # M, F, Kc, nhub, P
         _vp, _i64, _vp, _i64, _i32,       # U, ldu, W, ldw, k0
         _vp, _i64, _vp, _i32,             # S, lds, rec, rec_words
-        _vp, _i32,                        # bias, epilogue
-        _vp, _i64, _f32,                  # drop_mask, ldm, drop_scale
-        _f32, _u64, _u64, _vp,            # keep_prob, seed, offset, rng_base
+        *_EPI_ARGS,
         _vp, _i64, _vp, _i64, _vp, _i64,  # W2, ldw2, H, ldh, C2, ldc2
         _vp]),                            # stream
     # F, Kc, nhub, rec_words, P, ldu, u_aligned16, out6
@@ -200,9 +196,7 @@ SIGNATURES = {
     "gcnk_dense_gc1_f32": (ctypes.c_int, [
         _i32, _i32, _i32, _i32,           # M, K, F, P
         _vp, _i64, _vp, _i64,             # AX, ldax, W1, ldw1
-        _vp, _i32,                        # bias, epilogue
-        _vp, _i64, _f32,                  # drop_mask, ldm, drop_scale
-        _f32, _u64, _u64, _vp,            # keep_prob, seed, offset, rng_base
+        *_EPI_ARGS,
         _vp, _i64, _vp, _i64, _vp, _i64,  # W2, ldw2, H, ldh, C2, ldc2
         _vp]),                            # stream
     "gcnk_aggregate_f32": (ctypes.c_int, [_vp, _vp, _vp, _i32, _vp, _i64, _i32, _vp, _i64, _i32, _vp]),

@@ -30,7 +30,6 @@
 namespace gcnk {
 namespace {
 
-typedef float f32x4v __attribute__((ext_vector_type(4)));
 constexpr int kBwdBlock = 256;
 constexpr int kBwdCols = 256;      // columns per workgroup slice
 constexpr int kBwdRowsMax = 256;   // rows per workgroup (LDS staging of gS2 / G)
@@ -53,8 +52,7 @@ struct VecIO<4> {
   }
   // streaming store (gZ1: written once, read by the next launch)
   static __device__ __forceinline__ void store_nt(float* p, const float (&v)[4]) {
-    typedef float f4a __attribute__((ext_vector_type(4), aligned(16)));
-    __builtin_nontemporal_store(f4a{v[0], v[1], v[2], v[3]}, reinterpret_cast<f4a*>(p));
+    store16_nt(p, f32x4{v[0], v[1], v[2], v[3]});
   }
 };
 template <>
@@ -67,15 +65,15 @@ struct VecIO<2> {
     *reinterpret_cast<float2*>(p) = make_float2(v[0], v[1]);
   }
   static __device__ __forceinline__ void store_nt(float* p, const float (&v)[2]) {
-    __builtin_nontemporal_store(v[0], p);
-    __builtin_nontemporal_store(v[1], p + 1);
+    store4_nt(p, v[0]);
+    store4_nt(p + 1, v[1]);
   }
 };
 template <>
 struct VecIO<1> {
   static __device__ __forceinline__ void load(const float* p, float (&v)[1]) { v[0] = *p; }
   static __device__ __forceinline__ void store(float* p, const float (&v)[1]) { *p = v[0]; }
-  static __device__ __forceinline__ void store_nt(float* p, const float (&v)[1]) { __builtin_nontemporal_store(v[0], p); }
+  static __device__ __forceinline__ void store_nt(float* p, const float (&v)[1]) { store4_nt(p, v[0]); }
 };
 
 struct Bwd2Args {
@@ -244,28 +242,28 @@ __global__ void __launch_bounds__(kBwdBlock) gcn_bwd2_kernel(Bwd2Args a) {
   // element: the phase measured ~3.7 us at R8, profiles/r05_bwd2_stamps_v2.log.)
   if (bwd2_vec_reduce(a, VEC, PM)) {
     constexpr int KE4 = KE / 4;   // VEC (PM + 1) / 4 float4 per thread (PM % 4 == 0)
-    f32x4v* mine = reinterpret_cast<f32x4v*>(s_red) + tid * KE4;
+    f32x4* mine = reinterpret_cast<f32x4*>(s_red) + tid * KE4;
 #pragma unroll
     for (int v = 0; v < VEC; ++v)
 #pragma unroll
-      for (int p = 0; p < PM; p += 4) mine[(v * PM + p) / 4] = f32x4v{gw[v][p], gw[v][p + 1], gw[v][p + 2], gw[v][p + 3]};
+      for (int p = 0; p < PM; p += 4) mine[(v * PM + p) / 4] = f32x4{gw[v][p], gw[v][p + 1], gw[v][p + 2], gw[v][p + 3]};
 #pragma unroll
     for (int v = 0; v < VEC; v += 4) {
-      f32x4v g4;
+      f32x4 g4;
 #pragma unroll
       for (int i = 0; i < 4; ++i) g4[i] = v + i < VEC ? gb[v + i] : 0.f;
       mine[(VEC * PM + v) / 4] = g4;
     }
     __syncthreads();
-    const f32x4v* red = reinterpret_cast<const f32x4v*>(s_red);
+    const f32x4* red = reinterpret_cast<const f32x4*>(s_red);
     for (int e = tid; e < CT * KE4; e += kBwdBlock) {
       const int u = e / KE4, k4 = e - u * KE4;
-      f32x4v sum = red[u * KE4 + k4];
+      f32x4 sum = red[u * KE4 + k4];
       for (int l = 1; l < RL; ++l) sum += red[(l * CT + u) * KE4 + k4];
       const int64_t c0 = (int64_t)(cu0 + u) * VEC;
       if (c0 >= a.N) continue;
       if (k4 < VEC * PM / 4) {   // gW2 rows c0 .. c0 + VEC - 1: VEC PM contiguous floats
-        *reinterpret_cast<f32x4v*>(prow + c0 * a.P + 4 * k4) = sum;
+        *reinterpret_cast<f32x4*>(prow + c0 * a.P + 4 * k4) = sum;
       } else {                   // gb1 [c0 .. c0 + VEC): VEC floats
 #pragma unroll
         for (int i = 0; i < 4; ++i)

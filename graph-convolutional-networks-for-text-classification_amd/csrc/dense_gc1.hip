@@ -39,8 +39,6 @@
 namespace gcnk {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kWaves = 4;        // one per SIMD
 constexpr int kThreads = 64 * kWaves;
 constexpr int kHP = 64 + 4;      // wave-private H1 tile row stride (floats): 16 x (64 + 4)
@@ -62,8 +60,6 @@ struct DenseArgs {
 // A-tile row stride: >= 4 KS and = 4 (mod 64), so lane (row c, quadrant q)
 // reading k = 4 s + q hits bank 4 c + q: conflict-free
 constexpr int a_stride(int ks) { return 64 * ((4 * ks - 4 + 63) / 64) + 4; }
-
-typedef unsigned int u32x3 __attribute__((ext_vector_type(3)));
 
 __device__ __forceinline__ float mask_bits(float v, int m) { return __int_as_float(__float_as_int(v) & m); }
 
@@ -105,12 +101,10 @@ dense_gc1_kernel(DenseArgs a) {
   stamp(a.epi, 0);
   float* hw = s_h[w];
   // the A tile [16 x 4 KS] (zero past K and M): thread element e -> row e / (4 KS),
-  // k e % (4 KS) -- consecutive threads, consecutive k: coalesced
-  // The A tile through a buffer resource over the tile's rows (rows past M,
-  // and every row of a tile past the last, read 0): thread element i has a
-  // fixed offset inside the tile, and an element past K or past the tile gets
-  // an offset past any tile's resource, so it reads 0 too -- one load
-  // instruction per element, no compares or selects in the tile loop.
+  // k e % (4 KS) -- consecutive threads, consecutive k: coalesced.  Read through
+  // a buffer resource over the tile's rows (device_mem.h): thread element i has a
+  // fixed offset inside the tile, past any tile's resource for an element past K
+  // or past the tile -- no compares or selects in the tile loop.
   int voff[kAPer];
 #pragma unroll
   for (int i = 0; i < kAPer; ++i) {
@@ -120,10 +114,9 @@ dense_gc1_kernel(DenseArgs a) {
   auto load_a = [&](int tile, float (&av)[kAPer]) {
     const int64_t row0 = (int64_t)tile * 16;
     const int rows = row0 < a.M ? (int)min<int64_t>(16, a.M - row0) : 0;
-    const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(a.A + (rows ? row0 : 0) * a.lda), (short)0, rows * (int)a.lda * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ra = buffer_rsrc(a.A + (rows ? row0 : 0) * a.lda, rows * (int)a.lda * 4);
 #pragma unroll
-    for (int i = 0; i < kAPer; ++i) av[i] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(ra, voff[i], 0, 0));
+    for (int i = 0; i < kAPer; ++i) av[i] = buf_load_f32(ra, voff[i]);
   };
   auto put_a = [&](int buf, const float (&av)[kAPer]) {
 #pragma unroll
@@ -132,21 +125,17 @@ dense_gc1_kernel(DenseArgs a) {
       if (e < 16 * 4 * KS) s_A[buf][(e / (4 * KS)) * KP + e % (4 * KS)] = av[i];
     }
   };
-  //      Every operand is read through a buffer resource sized to it, so a
-  //      row past K (W1), F (W2) or a missing b1 reads 0 with no compare, and
-  //      columns are clamped into [0, F): what a lane computes for a column
-  //      past F is finite and is multiplied by W2's zero rows (and never
-  //      stored).  The prologue's instruction count is its time (4 cycles an
-  //      instruction, next to the other workgroup's MFMAs): a clamped,
-  //      compared and masked load costs ~12 instructions, a buffer load with
-  //      a scalar offset 1-2.
-  const __amdgpu_buffer_rsrc_t rw1 =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.W), (short)0, K * (int)a.ldw * 4, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rw2 =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.W2), (short)0, F * (int)a.ldw2 * 4, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rb1 =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.epi.bias ? a.epi.bias : a.W), (short)0,
-                                        a.epi.bias ? F * 4 : 0, 0x00020000);
+  //      Every operand through a buffer resource sized to it: a row past K
+  //      (W1), F (W2) or a missing b1 reads 0, and columns are clamped into
+  //      [0, F): what a lane computes for a column past F is finite and is
+  //      multiplied by W2's zero rows (and never stored).  The prologue's
+  //      instruction count is its time (4 cycles each, next to the other
+  //      workgroup's MFMAs): a clamped, compared and masked load costs ~12
+  //      instructions, a buffer load with a scalar offset 1-2.
+  const __amdgpu_buffer_rsrc_t rw1 = buffer_rsrc(a.W, K * (int)a.ldw * 4);
+  const __amdgpu_buffer_rsrc_t rw2 = buffer_rsrc(a.W2, F * (int)a.ldw2 * 4);
+  // (no b1: the zero-byte resource, over W1 as before -- a null base there compiles to other kernel text)
+  const __amdgpu_buffer_rsrc_t rb1 = buffer_rsrc_if(a.epi.bias != nullptr, a.epi.bias ? a.epi.bias : a.W, F * 4);
   //      1. every load issued (the first A tile last) ...
   float wf[KS][NI];
   // NI = 3: a lane whose three columns cross F reads the row's last three and
@@ -159,10 +148,10 @@ dense_gc1_kernel(DenseArgs a) {
     for (int s = 0; s < KS; ++s) {
       const int so = 16 * s * (int)a.ldw;
       if constexpr (NI == 4) {
-        const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rw1, vo + so, 0, 0));
+        const f32x4 v = buf_load_f32x4(rw1, vo + so);
         wf[s][0] = v[0]; wf[s][1] = v[1]; wf[s][2] = v[2]; wf[s][3] = v[3];
       } else {
-        const u32x3 v = __builtin_amdgcn_raw_buffer_load_b96(rw1, vo + so, 0, 0);
+        const u32x3 v = buf_load_u32x3(rw1, vo + so);
         wf[s][0] = __uint_as_float(v.x); wf[s][1] = __uint_as_float(v.y); wf[s][2] = __uint_as_float(v.z);
       }
     }
@@ -175,7 +164,7 @@ dense_gc1_kernel(DenseArgs a) {
 #pragma unroll
     for (int i = 0; i < kTPer; ++i) {
       const int e = tid + kThreads * i, k = e >> 4, ct = kTail0 + (e & 15);
-      tv[i] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rw1, (k * (int)a.ldw + (ct < F ? ct : 0)) * 4, 0, 0));
+      tv[i] = buf_load_f32(rw1, (k * (int)a.ldw + (ct < F ? ct : 0)) * 4);
     }
   }
   float w2f[JS][NPM];
@@ -186,20 +175,20 @@ dense_gc1_kernel(DenseArgs a) {
     for (int p = 0; p < NPM; ++p) {   // (columns of P past P: their S2 columns are never stored)
       const int col = js < JS ? base + 4 * js + q : kTail0 + 4 * (js - JS) + q, pc = 16 * p + c;
       float& dst = js < JS ? w2f[js < JS ? js : 0][p] : w2t[js < JS ? 0 : js - JS][p];
-      dst = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rw2, (col * (int)a.ldw2 + pc) * 4, 0, 0));
+      dst = buf_load_f32(rw2, (col * (int)a.ldw2 + pc) * 4);
     }
   float bv[NI], btl = 0.f;
 #pragma unroll
   for (int t = 0; t < NI; ++t)
-    bv[t] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rb1, (cl + t) * 4, 0, 0));
+    bv[t] = buf_load_f32(rb1, (cl + t) * 4);
   if constexpr (kTail)
-    btl = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rb1, (kTail0 + c < F ? kTail0 + c : F) * 4, 0, 0));
+    btl = buf_load_f32(rb1, (kTail0 + c < F ? kTail0 + c : F) * 4);
   float av0[kAPer];
   load_a(blockIdx.x, av0);
   float pv[PV ? PV : 1];
 #pragma unroll
   for (int i = 0; i < PV; ++i)   // W2[tid][16 NPM + i] (rows past F read 0)
-    pv[i] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rw2, (tid * (int)a.ldw2 + 16 * NPM + i) * 4, 0, 0));
+    pv[i] = buf_load_f32(rw2, (tid * (int)a.ldw2 + 16 * NPM + i) * 4);
   //      2. ... then the NI = 3 shift (skipped, uniformly, once F >= 192) and
   //      the values pinned (left alone, the compiler re-derived them inside
   //      the tile loop)
@@ -296,14 +285,14 @@ dense_gc1_kernel(DenseArgs a) {
       const int64_t row = row0 + 4 * q + r;
       if constexpr (NI == 4) {
         const f32x4 h4 = {h[0], h[1], h[2], h[3]};
-        if (a.H && row < a.M && col0 < F) __builtin_nontemporal_store(h4, reinterpret_cast<f32x4*>(a.H + row * a.ldh + col0));
+        if (a.H && row < a.M && col0 < F) store16_nt(a.H + row * a.ldh + col0, h4);
         *reinterpret_cast<f32x4*>(&hw[(4 * q + r) * kHP + 4 * c]) = h4;
       } else {
         if (a.H) {
 #pragma unroll
           for (int t = 0; t < NI; ++t)
-            if (row < a.M && col0 + t < F) __builtin_nontemporal_store(h[t], a.H + row * a.ldh + col0 + t);
-          if (mine && row < a.M && kTail0 + c < F) __builtin_nontemporal_store(ht, a.H + row * a.ldh + kTail0 + c);
+            if (row < a.M && col0 + t < F) store4_nt(a.H + row * a.ldh + col0 + t, h[t]);
+          if (mine && row < a.M && kTail0 + c < F) store4_nt(a.H + row * a.ldh + kTail0 + c, ht);
         }
 #pragma unroll
         for (int t = 0; t < NI; ++t) hw[(4 * q + r) * kHP + NI * c + t] = h[t];
@@ -483,24 +472,6 @@ int launch(const DenseArgs& a, hipStream_t s) {
   return launch_ks<32>(a, grid, s);
 }
 
-// the epilogue fields of the entry point
-Epi make_epi(const float* bias, int32_t epilogue, const uint8_t* mask, int64_t ldm, int32_t F, float scale, float keep,
-             uint64_t seed, uint64_t offset, const uint64_t* rng_base) {
-  Epi e;
-  e.bias = bias;
-  e.mask = mask;
-  e.ldm = epilogue == GCNK_EPI_BIAS_RELU_HASH ? (ldm > 0 ? ldm : F) : ldm;
-  e.scale = scale;
-  e.keep_prob = keep;
-  e.seed_lo = (uint32_t)seed;
-  e.seed_hi = (uint32_t)(seed >> 32);
-  e.offset = offset;
-  e.rng_base = rng_base;
-  e.code = epilogue;
-  e.stamps = debug_stamps();
-  return e;
-}
-
 }  // namespace
 }  // namespace gcnk
 
@@ -518,25 +489,21 @@ extern "C" int gcnk_dense_gc1_f32(int32_t M, int32_t K, int32_t F, int32_t P, co
   }
   if (K > 128 || F > 256 || F % 4 || P > kMaxP || ldw1 % 4 || !aligned16(W1) ||
       (int64_t)K * ldw1 * 4 >= INT32_MAX || (int64_t)F * ldw2 * 4 >= INT32_MAX ||   // (32-bit buffer offsets;
-      (int64_t)16 * ldax * 4 >= 0x7ff00000 ||                                        //  A's tile sentinel past them)
+      (int64_t)16 * ldax * 4 >= kBufOob ||                                             //  A's tile sentinel past them)
       (bias && !aligned16(bias)) || (H && (ldh % 4 || !aligned16(H)))) {
     set_error("gcnk_dense_gc1_f32: unsupported shape (K=%d <= 128, F=%d <= 256 and %% 4, P=%d <= 32, "
               "16-B aligned W1 / b1 / H1 rows)", K, F, P);
     return GCNK_EUNSUP;
   }
-  if (epilogue != GCNK_EPI_BIAS_RELU && epilogue != GCNK_EPI_BIAS_RELU_DROP && epilogue != GCNK_EPI_BIAS_RELU_HASH) {
-    set_error("gcnk_dense_gc1_f32: epilogue %d is not a gc1 epilogue (bias + ReLU [+ dropout])", epilogue);
-    return GCNK_EARG;
-  }
-  if (epilogue == GCNK_EPI_BIAS_RELU_DROP && (!drop_mask || ldm < F)) {
-    set_error("gcnk_dense_gc1_f32: dropout epilogue needs a mask with ldm >= F");
-    return GCNK_EARG;
-  }
+  constexpr int32_t kGc1Codes =   // bias + ReLU [+ dropout]
+      1 << GCNK_EPI_BIAS_RELU | 1 << GCNK_EPI_BIAS_RELU_DROP | 1 << GCNK_EPI_BIAS_RELU_HASH;
   DenseArgs a{};
+  const int rc = make_epi("gcnk_dense_gc1_f32", bias, epilogue, drop_mask, ldm, drop_scale, keep_prob, seed, offset,
+                          rng_base, F, kGc1Codes, &a.epi);
+  if (rc) return rc;
   a.M = M; a.K = K; a.F = F; a.P = P;
   a.A = AX; a.lda = ldax; a.W = W1; a.ldw = ldw1; a.W2 = W2; a.ldw2 = ldw2;
   a.H = H; a.ldh = ldh; a.C2 = C2; a.ldc2 = ldc2;
-  a.epi = make_epi(bias, epilogue, drop_mask, ldm, F, drop_scale, keep_prob, seed, offset, rng_base);
   a.ntiles = (M + 15) / 16;
   return launch(a, reinterpret_cast<hipStream_t>(stream));
 }

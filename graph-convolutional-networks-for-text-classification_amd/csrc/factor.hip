@@ -38,8 +38,6 @@
 namespace gcnk {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kRB = 32;         // rows per workgroup
 constexpr int kThreads = 512;   // 8 waves: 2 row strips x 4 column quarters
 constexpr int kMaxKsteps = 32;  // Kc <= 128
@@ -154,16 +152,15 @@ hubfactor_gc1_kernel(FactorArgs a) {
   constexpr int kq = Fp / 16;  // k-steps per quarter
   float bw[NP][kq];
   {
-    const __amdgpu_buffer_rsrc_t rw =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.W2), (short)0, F * a.P * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rw = buffer_rsrc(a.W2, F * a.P * 4);
     const int kstep = 16 * a.P;   // bytes between the lane's consecutive k (4 rows of P floats)
 #pragma unroll
     for (int t = 0; t < NP; ++t) {
       const int col = 16 * t + (lane & 15);
-      int off = col < a.P ? ((4 * quarter * kq + (lane >> 4)) * a.P + col) * 4 : 0x7ff00000;
+      int off = col < a.P ? ((4 * quarter * kq + (lane >> 4)) * a.P + col) * 4 : (int)kBufOob;
 #pragma unroll
       for (int j = 0; j < kq; ++j, off += kstep)
-        bw[t][j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rw, off, 0, 0));
+        bw[t][j] = buf_load_f32(rw, off);
     }
   }
   float af[KS];
@@ -293,10 +290,7 @@ hubfactor_gc1_kernel(FactorArgs a) {
     }
     if (row >= 0) {
       auto put = [&](int q, const float4& h) __attribute__((always_inline)) {
-        if (a.H) {  // H1 for the backward: streaming store (no dirty L2 lines at the kernel's end)
-          typedef float f4a __attribute__((ext_vector_type(4), aligned(16)));
-          __builtin_nontemporal_store(f4a{h.x, h.y, h.z, h.w}, reinterpret_cast<f4a*>(a.H + row * a.ldh + 4 * q));
-        }
+        if (a.H) store16_nt(a.H + row * a.ldh + 4 * q, h);  // H1 for the backward
         *reinterpret_cast<float4*>(s_Z + r * Fz + 4 * q) = h;
       };
       // eval / no-dropout: one uniform branch around all the elements (tested
@@ -493,27 +487,20 @@ extern "C" int gcnk_hubfactor_gc1_f32(int32_t M, int32_t F, int32_t Kc, int32_t 
     set_error("gcnk_hubfactor_gc1_f32: unsupported shape (F=%d %% 4, F <= 256, Kc <= 128, P <= 32, 16-B rows)", F);
     return GCNK_EUNSUP;
   }
-  if (epilogue < GCNK_EPI_NONE || epilogue > GCNK_EPI_BIAS_RELU_HASH ||
-      (epilogue == GCNK_EPI_BIAS_RELU_DROP && (!drop_mask || ldm < F))) {
-    set_error("gcnk_hubfactor_gc1_f32: bad epilogue %d (dropout needs a mask with ldm >= F)", epilogue);
-    return GCNK_EARG;
-  }
+  FactorArgs a;
+  const int rc = make_epi("gcnk_hubfactor_gc1_f32", bias, epilogue, drop_mask, ldm, drop_scale, keep_prob, seed, offset,
+                          rng_base, F, kEpiAllCodes, &a.epi);
+  if (rc) return rc;
   if (bad == 5) {
     set_error("gcnk_hubfactor_gc1_f32: %lld B of LDS per workgroup > 160 KiB (F=%d Kc=%d hubs=%d)",
               (long long)rt.lds_b, F, Kc, nhub);
     return GCNK_EUNSUP;
   }
-  FactorArgs a;
   a.M = M; a.F = F; a.Kc = Kc; a.nhub = nhub; a.P = P;
   a.u_lds = rt.u_lds;
   a.U = U; a.ldu = ldu; a.W = W; a.ldw = ldw; a.k0 = k0;
   a.S = S; a.lds = lds; a.rec = rec; a.rec_words = rec_words;
   a.W2 = W2; a.ldw2 = ldw2; a.H = H; a.ldh = ldh; a.C2 = C2; a.ldc2 = ldc2;
-  Epi& e = a.epi;
-  e.bias = bias; e.mask = drop_mask; e.scale = drop_scale; e.keep_prob = keep_prob;
-  e.seed_lo = (uint32_t)seed; e.seed_hi = (uint32_t)(seed >> 32); e.offset = offset; e.rng_base = rng_base;
-  e.code = epilogue; e.stamps = debug_stamps();
-  e.ldm = epilogue == GCNK_EPI_BIAS_RELU_HASH ? (ldm > 0 ? ldm : F) : ldm;
   const int64_t nblk = ((int64_t)M + kRB - 1) / kRB;
   const int ks = rt.ks, ntq = rt.ntq, np = rt.np;
   const int64_t lds_l = rt.lds_launch;

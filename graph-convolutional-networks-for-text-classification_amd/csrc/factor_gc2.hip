@@ -33,8 +33,6 @@
 namespace gcnk {
 namespace {
 
-typedef float f32v4 __attribute__((ext_vector_type(4)));
-
 constexpr int kThreads = 256;
 constexpr int kRB = 32;                    // rows per block record (csrc/factor.hip)
 constexpr int kRecRow = 36, kRecHead = 68;
@@ -43,8 +41,6 @@ constexpr int kHubU = 16;                  // items (and gathers) in flight per 
 constexpr int kDocU = 8;                   // items of a document row read from LDS per batch
 constexpr int kCollect = 16;               // collector groups of the hub rows' fixed-order combine
 constexpr int kPartSlots = 384;            // combine slots: 16 * ceil(G / 16) * P4 <= 336, zero past the real ones
-constexpr uint32_t kOob = 0x7ff00000u;     // a byte offset past every resource (sizes are checked below it)
-constexpr int kBufDword3 = 0x00020000;     // raw buffer resource word 3 (gfx9)
 
 struct Gc2Args {
   int32_t M, H, P, rec_words;
@@ -65,16 +61,7 @@ struct Gc2Args {
   int32_t hub_rp[kMaxHubs + 1];
 };
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* base, uint32_t bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, (int)bytes, kBufDword3);
-}
-__device__ __forceinline__ f32v4 load4(__amdgpu_buffer_rsrc_t r, uint32_t off) {
-  return __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0);
-}
-__device__ __forceinline__ uint32_t load1(__amdgpu_buffer_rsrc_t r, uint32_t off) {
-  return __builtin_amdgcn_raw_buffer_load_b32(r, (int)off, 0, 0);
-}
-__device__ __forceinline__ void fma4(f32v4& acc, float a, const f32v4& b) {
+__device__ __forceinline__ void fma4(f32x4& acc, float a, const f32x4& b) {
   acc.x = fmaf(a, b.x, acc.x);
   acc.y = fmaf(a, b.y, acc.y);
   acc.z = fmaf(a, b.z, acc.z);
@@ -98,17 +85,17 @@ __device__ __forceinline__ void stamp2(const Gc2Args& a, int k) {
 // AND on the value: a select per product element made the chain ~36 instructions
 // a term, 1.4 us of a lone wave's issue.)
 template <int P4>
-__device__ __forceinline__ void doc_chain(f32v4& acc, const int2* s_items, const float* s_hub, int zero_off, int c,
+__device__ __forceinline__ void doc_chain(f32x4& acc, const int2* s_items, const float* s_hub, int zero_off, int c,
                                           int jb, int je) {
   constexpr int P = 4 * P4;
   for (int j0 = jb; j0 < je; j0 += kDocU) {
     int2 it[kDocU];
-    f32v4 hv[kDocU];
+    f32x4 hv[kDocU];
 #pragma unroll
     for (int u = 0; u < kDocU; ++u) it[u] = s_items[min(j0 + u, je - 1)];
 #pragma unroll
     for (int u = 0; u < kDocU; ++u)
-      hv[u] = *reinterpret_cast<const f32v4*>(s_hub + (j0 + u < je ? it[u].x * P : zero_off) + 4 * c);
+      hv[u] = *reinterpret_cast<const f32x4*>(s_hub + (j0 + u < je ? it[u].x * P : zero_off) + 4 * c);
 #pragma unroll
     for (int u = 0; u < kDocU; ++u) fma4(acc, __int_as_float(it[u].y & (j0 + u < je ? -1 : 0)), hv[u]);
   }
@@ -123,14 +110,14 @@ __global__ void __launch_bounds__(kThreads) factored_spmm_row_kernel(Gc2Args a) 
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int c = tid % P4;
   stamp2(a, 0);
-  const __amdgpu_buffer_rsrc_t r_s2 = rsrc(a.S2, a.s2_bytes);
-  const __amdgpu_buffer_rsrc_t r_out = rsrc(a.out, a.out_bytes);
+  const __amdgpu_buffer_rsrc_t r_s2 = buffer_rsrc(a.S2, a.s2_bytes);
+  const __amdgpu_buffer_rsrc_t r_out = buffer_rsrc(a.out, a.out_bytes);
   // a hub row's range and id, read with the other arguments in the entry block
   // (behind the branch they were a scalar round trip of their own; a document
   // workgroup reads hub 127's words and drops them)
   const int hsel = min((int)blockIdx.x, kMaxHubs - 1);
   const int32_t hub_b = a.hub_rp[hsel], hub_e = a.hub_rp[hsel + 1], hub_row = a.hub_id[hsel];
-  const f32v4 bv = load4(rsrc(a.b2, a.b2_bytes), 16u * c);   // (no b2: an empty resource, reads 0)
+  const f32x4 bv = buf_load_f32x4(buffer_rsrc(a.b2, a.b2_bytes), 16u * c);   // (no b2: an empty resource, reads 0)
   asm volatile("" ::"s"(hub_b), "s"(hub_e), "s"(hub_row));   // (pinned here: the compiler sank them behind the branch)
 
   if ((int)blockIdx.x < a.H) {
@@ -140,25 +127,25 @@ __global__ void __launch_bounds__(kThreads) factored_spmm_row_kernel(Gc2Args a) 
     const int32_t row = hub_row;
     const int g = tid / P4;
     const bool live = g < G;                // (P = 12, 20, 28: the last threads hold no group)
-    const __amdgpu_buffer_rsrc_t r_ci = rsrc(a.hub_ci + b, 4u * (uint32_t)n);
-    const __amdgpu_buffer_rsrc_t r_v = rsrc(a.hub_val + b, 4u * (uint32_t)n);
-    f32v4 acc = {0.f, 0.f, 0.f, 0.f};
+    const __amdgpu_buffer_rsrc_t r_ci = buffer_rsrc(a.hub_ci + b, 4u * (uint32_t)n);
+    const __amdgpu_buffer_rsrc_t r_v = buffer_rsrc(a.hub_val + b, 4u * (uint32_t)n);
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     for (int32_t k0 = 0; k0 < n; k0 += G * kHubU) {
       uint32_t col[kHubU];
       float val[kHubU];
-      f32v4 s[kHubU];
+      f32x4 s[kHubU];
 #pragma unroll
       for (int j = 0; j < kHubU; ++j) {     // round 1: past the row's end (or a dead thread) reads 0
-        const uint32_t off = live ? 4u * (uint32_t)(k0 + g + G * j) : kOob;
-        col[j] = load1(r_ci, off);
-        val[j] = __uint_as_float(load1(r_v, off));
+        const uint32_t off = live ? 4u * (uint32_t)(k0 + g + G * j) : kBufOob;
+        col[j] = buf_load_u32(r_ci, off);
+        val[j] = buf_load_f32(r_v, off);
       }
       stamp2(a, 1);
 #pragma unroll
       for (int j = 0; j < kHubU; ++j) {     // round 2: their S2 rows; no item, no load (0)
         // (a mask OR-ed in, not a select of the offset: the select became a branch around each load)
-        const uint32_t dead = live && k0 + g + G * j < n ? 0u : kOob;
-        s[j] = load4(r_s2, (col[j] * a.ld4 + 16u * c) | dead);
+        const uint32_t dead = live && k0 + g + G * j < n ? 0u : kBufOob;
+        s[j] = buf_load_f32x4(r_s2, (col[j] * a.ld4 + 16u * c) | dead);
       }
       // (every gather issued before the first fma: the scheduler otherwise pulled
       // the fmas up between them to save registers, a wait for all but one load
@@ -169,18 +156,18 @@ __global__ void __launch_bounds__(kThreads) factored_spmm_row_kernel(Gc2Args a) 
     }
     // the lane groups meet: slot = thread; collector q sums groups q, q + 16, ...
     // in order, then lane c of group 0 sums the collectors in order
-    f32v4* s_part = reinterpret_cast<f32v4*>(smem);
-    f32v4* s_coll = s_part + kPartSlots;
-    const f32v4 zero = {0.f, 0.f, 0.f, 0.f};
+    f32x4* s_part = reinterpret_cast<f32x4*>(smem);
+    f32x4* s_coll = s_part + kPartSlots;
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     s_part[tid] = live ? acc : zero;
     if (tid < kPartSlots - kThreads) s_part[kThreads + tid] = zero;
     __syncthreads();
     constexpr int NJ = (G + kCollect - 1) / kCollect;
     if (tid < kCollect * P4) {
-      f32v4 p[NJ];
+      f32x4 p[NJ];
 #pragma unroll
       for (int j = 0; j < NJ; ++j) p[j] = s_part[(g + kCollect * j) * P4 + c];
-      f32v4 t = p[0];
+      f32x4 t = p[0];
 #pragma unroll
       for (int j = 1; j < NJ; ++j) t += p[j];
       s_coll[tid] = t;
@@ -188,14 +175,14 @@ __global__ void __launch_bounds__(kThreads) factored_spmm_row_kernel(Gc2Args a) 
     __syncthreads();
     stamp2(a, 2);
     if (tid < P4) {
-      f32v4 p[kCollect];
+      f32x4 p[kCollect];
 #pragma unroll
       for (int q = 0; q < kCollect; ++q) p[q] = s_coll[q * P4 + c];
-      f32v4 t = p[0];
+      f32x4 t = p[0];
 #pragma unroll
       for (int q = 1; q < kCollect; ++q) t += p[q];
       t += bv;
-      __builtin_amdgcn_raw_buffer_store_b128(t, r_out, (int)((uint32_t)row * a.ldo4 + 16u * c), 0, 0);
+      buf_store_f32x4(t, r_out, (uint32_t)row * a.ldo4 + 16u * c);
     }
     stamp2(a, 3);
     return;
@@ -217,10 +204,11 @@ __global__ void __launch_bounds__(kThreads) factored_spmm_row_kernel(Gc2Args a) 
     for (int e0 = wv * 64; e0 < rw4; e0 += kThreads)
       if (e0 + lane < rw4) lds_dma16(rec + 4 * (e0 + lane), s_rec + 4 * e0);
   }
-  const uint32_t pos4 = rowt ? 4u * (uint32_t)(blk * kRB + i) : kOob;
-  const float dg = __uint_as_float(load1(rsrc(a.diag, a.pos_bytes), pos4));
-  const int32_t pre = (int32_t)load1(rsrc(a.pre, a.pos_bytes), pos4);
-  const int32_t rid = (int32_t)load1(rsrc(rec, 4u * (uint32_t)a.rec_words), rowt ? 4u * (uint32_t)(kRecRow + i) : kOob);
+  const uint32_t pos4 = rowt ? 4u * (uint32_t)(blk * kRB + i) : kBufOob;
+  const float dg = buf_load_f32(buffer_rsrc(a.diag, a.pos_bytes), pos4);
+  const int32_t pre = (int32_t)buf_load_u32(buffer_rsrc(a.pre, a.pos_bytes), pos4);
+  const int32_t rid =
+      (int32_t)buf_load_u32(buffer_rsrc(rec, 4u * (uint32_t)a.rec_words), rowt ? 4u * (uint32_t)(kRecRow + i) : kBufOob);
   constexpr int NQ = (kMaxHubs * P4 + kThreads - 1) / kThreads;   // pieces of S2[hubs] per thread
   const int nh4 = a.H * P4;
   int32_t hid[NQ];
@@ -238,8 +226,8 @@ __global__ void __launch_bounds__(kThreads) factored_spmm_row_kernel(Gc2Args a) 
     if (tid + kThreads * q < nh4)
       lds_dma16(a.S2 + (int64_t)hid[q] * (a.ld4 / 4) + 4 * ((tid + kThreads * q) % P4),
                 s_hub + 4 * (kThreads * q + 64 * wv));
-  if (tid < P4) *reinterpret_cast<f32v4*>(s_hub + a.H * P + 4 * tid) = f32v4{0.f, 0.f, 0.f, 0.f};   // the zero row
-  const f32v4 own = load4(r_s2, ((uint32_t)rid * a.ld4 + 16u * c) | (doc && dg != 0.f ? 0u : kOob));
+  if (tid < P4) *reinterpret_cast<f32x4*>(s_hub + a.H * P + 4 * tid) = f32x4{0.f, 0.f, 0.f, 0.f};   // the zero row
+  const f32x4 own = buf_load_f32x4(r_s2, ((uint32_t)rid * a.ld4 + 16u * c) | (doc && dg != 0.f ? 0u : kBufOob));
   __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): this wave's DMA and loads have landed
   __syncthreads();
   stamp2(a, 1);
@@ -250,13 +238,13 @@ __global__ void __launch_bounds__(kThreads) factored_spmm_row_kernel(Gc2Args a) 
   const int32_t off0 = s_rec[i], off1 = s_rec[i + 1];
   const int2* s_items = reinterpret_cast<const int2*>(s_rec + kRecHead);
   const int jb = doc ? off0 : 0, je = doc ? off1 : 0, jm = doc ? min(off0 + pre, off1) : 0;
-  f32v4 acc = {0.f, 0.f, 0.f, 0.f};
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   doc_chain<P4>(acc, s_items, s_hub, a.H * P, c, jb, jm);
   fma4(acc, dg, own);
   doc_chain<P4>(acc, s_items, s_hub, a.H * P, c, jm, je);
   stamp2(a, 2);
   acc += bv;
-  __builtin_amdgcn_raw_buffer_store_b128(acc, r_out, (int)(doc ? (uint32_t)rid * a.ldo4 + 16u * c : kOob), 0, 0);
+  buf_store_f32x4(acc, r_out, doc ? (uint32_t)rid * a.ldo4 + 16u * c : kBufOob);
   stamp2(a, 3);
 }
 
@@ -288,8 +276,8 @@ extern "C" int gcnk_hubfactor_gc2_f32(int32_t M, int32_t H, int32_t P, const int
   const int64_t lds_doc = 4 * ((int64_t)rec_words + ((int64_t)H + 1) * P);   // record | S2[hubs] | a zero row
   const int64_t lds_hub = 16 * (int64_t)(kPartSlots + kCollect * 8);
   if (P % 4 || P > 32 || H > kMaxHubs || lds2 % 4 || ldo % 4 || !aligned16(S2) || !aligned16(out) ||
-      !aligned16(rec) || (b2 && !aligned16(b2)) || s2_bytes > (int64_t)kOob || out_bytes > (int64_t)kOob ||
-      nblk * rec_words * 4 > (int64_t)kOob || lds_doc > 64 * 1024) {
+      !aligned16(rec) || (b2 && !aligned16(b2)) || s2_bytes > (int64_t)kBufOob || out_bytes > (int64_t)kBufOob ||
+      nblk * rec_words * 4 > (int64_t)kBufOob || lds_doc > 64 * 1024) {
     set_error("gcnk_hubfactor_gc2_f32: unsupported shape (P=%d %% 4, P <= 32, hubs=%d <= 128, 16-B rows, "
               "operands below 2 GiB, %lld B of LDS <= 64 KiB)", P, H, (long long)lds_doc);
     return GCNK_EUNSUP;

@@ -9,6 +9,7 @@
 #include <atomic>
 
 #include "../../include/gcnk.h"
+#include "device_mem.h"
 
 namespace gcnk {
 
@@ -76,6 +77,27 @@ struct Epi {
   int32_t code;
   unsigned long long* stamps;  // debug timeline (gcnk_debug_set_stamps), normally null
 };
+
+// The Epi of an entry point `who` from its nine ABI arguments (gcnk.h), or GCNK_EARG:
+// `epilogue` must be one of `allowed_codes` (bit c set: code c is accepted), and
+// GCNK_EPI_BIAS_RELU_DROP needs a mask whose rows hold F elements.  The hash
+// epilogue indexes its stream by row * ldm + col; ldm <= 0 there means F.
+constexpr int32_t kEpiAllCodes = (2 << GCNK_EPI_BIAS_RELU_HASH) - 1;
+inline int make_epi(const char* who, const float* bias, int32_t epilogue, const uint8_t* drop_mask, int64_t ldm,
+                    float drop_scale, float keep_prob, uint64_t seed, uint64_t offset, const uint64_t* rng_base,
+                    int32_t F, int32_t allowed_codes, Epi* out) {
+  if (epilogue < GCNK_EPI_NONE || epilogue > GCNK_EPI_BIAS_RELU_HASH || !((allowed_codes >> epilogue) & 1)) {
+    set_error("%s: epilogue %d is not one this entry point takes", who, epilogue);
+    return GCNK_EARG;
+  }
+  if (epilogue == GCNK_EPI_BIAS_RELU_DROP && (!drop_mask || ldm < F)) {
+    set_error("%s: dropout epilogue needs a mask with ldm >= F", who);
+    return GCNK_EARG;
+  }
+  *out = Epi{bias, drop_mask, epilogue == GCNK_EPI_BIAS_RELU_HASH && ldm <= 0 ? F : ldm, drop_scale, keep_prob,
+             (uint32_t)seed, (uint32_t)(seed >> 32), offset, rng_base, epilogue, debug_stamps()};   // (Epi's field order)
+  return GCNK_OK;
+}
 
 // Debug timeline: 4 x s_memrealtime (100 MHz) per workgroup, written by thread 0.
 // Compiled in only with -DGCNK_STAMPS (scripts/stamps.py): the runtime branch
@@ -146,11 +168,8 @@ struct Vec<4> {
   static __device__ __forceinline__ T zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
   static __device__ __forceinline__ T load(const float* p) { return *reinterpret_cast<const float4*>(p); }
   static __device__ __forceinline__ void store(float* p, const T& v) { *reinterpret_cast<float4*>(p) = v; }
-  // one 16-B store instruction whatever the surrounding control flow
-  static __device__ __forceinline__ void store_aligned(float* p, const T& v) {
-    typedef float f4a __attribute__((ext_vector_type(4), aligned(16)));
-    *reinterpret_cast<f4a*>(__builtin_assume_aligned(p, 16)) = f4a{v.x, v.y, v.z, v.w};
-  }
+  static __device__ __forceinline__ void store_aligned(float* p, const T& v) { store16(p, v); }
+  static __device__ __forceinline__ void store_nt(float* p, const T& v) { store16_nt(p, v); }
   static __device__ __forceinline__ void fma(T& acc, float a, const T& b) {
     acc.x = fmaf(a, b.x, acc.x);
     acc.y = fmaf(a, b.y, acc.y);
@@ -199,6 +218,7 @@ struct Vec<1> {
   static __device__ __forceinline__ T load(const float* p) { return *p; }
   static __device__ __forceinline__ void store(float* p, const T& v) { *p = v; }
   static __device__ __forceinline__ void store_aligned(float* p, const T& v) { *p = v; }
+  static __device__ __forceinline__ void store_nt(float* p, const T& v) { store4_nt(p, v); }
   static __device__ __forceinline__ void fma(T& acc, float a, const T& b) { acc = fmaf(a, b, acc); }
   static __device__ __forceinline__ void add(T& acc, const T& b) { acc += b; }
   static __device__ __forceinline__ T epi(const Epi& e, const T& a, const T& b, int64_t row, int64_t col) {

@@ -19,8 +19,6 @@
 namespace gcnk {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 struct GemmEpi {
   const float* bias;
   const float* R;
@@ -45,9 +43,8 @@ __device__ __forceinline__ float gemm_epi(const GemmEpi& e, float acc, int64_t m
 }
 
 constexpr int BK = 16;
-// An operand of the tiled kernel is read through a buffer resource while its span in bytes stays below this
-// (32-bit offsets); the kernel's use_buf and the host's tiled_ptr_fetch (the route's flag) both test against it.
-constexpr int64_t kBufSpanLimit = 0x7ff00000;
+// An operand of the tiled kernel is read through a buffer resource while its span in bytes stays below kBufOob;
+// the kernel's use_buf and the host's tiled_ptr_fetch (the route's flag) both test against it.
 
 template <int WM, int WN, int FM, int FN, bool TA, bool TB>
 __global__ void __launch_bounds__(256)
@@ -79,17 +76,13 @@ gemm_f32_mfma_kernel(int32_t M, int32_t N, int32_t K, int32_t kchunk, const floa
   // flight while tile t is multiplied out of LDS
   constexpr int PA = (BM * BK + 255) / 256, PB = (BN * BK + 255) / 256;
   float ra[PA], rb[PB];
-  // A and B through buffer resources when both fit 32-bit offsets: an element
-  // outside the tile's rows or past this K chunk gets an offset past the
-  // resource and reads 0 -- no branch per load (guarded, each of the tile's
-  // loads compiled into a branch with its own vmcnt(0): the double buffer's
-  // next tile arrived one load at a time)
+  // A and B through buffer resources (device_mem.h) when both fit 32-bit offsets: an element outside the
+  // tile's rows or past this K chunk reads 0 with no branch per load (guarded, each load compiled into a
+  // branch with its own vmcnt(0): the double buffer's next tile arrived one load at a time)
   const int64_t a_bytes = (TA ? (int64_t)K : (int64_t)M) * lda * 4, b_bytes = (TB ? (int64_t)N : (int64_t)K) * ldb * 4;
-  const bool use_buf = a_bytes < kBufSpanLimit && b_bytes < kBufSpanLimit;   // (uniform)
-  const __amdgpu_buffer_rsrc_t rsa =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(A), (short)0, use_buf ? (int)a_bytes : 0, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsb =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(B), (short)0, use_buf ? (int)b_bytes : 0, 0x00020000);
+  const bool use_buf = a_bytes < kBufOob && b_bytes < kBufOob;   // (uniform)
+  const __amdgpu_buffer_rsrc_t rsa = buffer_rsrc_if(use_buf, A, (uint32_t)a_bytes);
+  const __amdgpu_buffer_rsrc_t rsb = buffer_rsrc_if(use_buf, B, (uint32_t)b_bytes);
   auto fetch_buf = [&](int32_t k0) {
 #pragma unroll
     for (int p = 0; p < PA; ++p) {
@@ -99,8 +92,7 @@ gemm_f32_mfma_kernel(int32_t M, int32_t N, int32_t K, int32_t kchunk, const floa
       else { k = e / BM; m = e % BM; }
       const int gm = (int)m0 + m, gk = k0 + k;
       const bool ok = e < BM * BK && gm < M && gk < ke;
-      ra[p] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
-          rsa, ok ? (TA ? (gk * (int)lda + gm) * 4 : (gm * (int)lda + gk) * 4) : 0x7ffffff0, 0, 0));
+      ra[p] = buf_load_f32(rsa, ok ? (TA ? (gk * (int)lda + gm) * 4 : (gm * (int)lda + gk) * 4) : 0x7ffffff0);
     }
 #pragma unroll
     for (int p = 0; p < PB; ++p) {
@@ -110,8 +102,7 @@ gemm_f32_mfma_kernel(int32_t M, int32_t N, int32_t K, int32_t kchunk, const floa
       else { n = e / BK; k = e % BK; }
       const int gn = (int)n0 + n, gk = k0 + k;
       const bool ok = e < BN * BK && gn < N && gk < ke;
-      rb[p] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
-          rsb, ok ? (TB ? (gn * (int)ldb + gk) * 4 : (gk * (int)ldb + gn) * 4) : 0x7ffffff0, 0, 0));
+      rb[p] = buf_load_f32(rsb, ok ? (TB ? (gn * (int)ldb + gk) * 4 : (gk * (int)ldb + gn) * 4) : 0x7ffffff0);
     }
   };
   auto fetch_ptr = [&](int32_t k0) {
@@ -414,24 +405,18 @@ gemm_smallm_wk_kernel(int32_t M, int32_t N, int32_t K, const float* __restrict__
   const int r = lane & 15, q = lane >> 4;
   const int64_t kb0 = ((int64_t)blockIdx.x * kW + w) * KBW;   // this wave's first 16-deep k block
   const int64_t n0 = (int64_t)blockIdx.y * 16 * NTG;
-  // A and B through buffer resources sized to them (the dispatch keeps both
-  // under 2 GB): rows of A past M and rows of B past K read 0 with no compare
-  // or 64-bit address per load (that prologue was ~300 instructions a wave,
-  // issued at 4 cycles each before the last load left); a column of B past N
-  // only feeds an output column that is never stored.  A's components past K
-  // are still zeroed: its row padding is not ours, and 0 x a NaN pad is NaN.
-  const __amdgpu_buffer_rsrc_t ra =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(A), (short)0, M * (int)lda * 4, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rb =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(B), (short)0, K * (int)ldb * 4, 0x00020000);
+  // A and B through buffer resources sized to them (the dispatch keeps both under 2 GB): rows of A past M and
+  // of B past K read 0 with no compare or 64-bit address per load (that prologue was ~300 instructions a wave,
+  // 4 cycles each, before the last load left); a column of B past N only feeds an output column that is never
+  // stored.  A's components past K are still zeroed: its row padding is not ours, and 0 x a NaN pad is NaN.
+  const __amdgpu_buffer_rsrc_t ra = buffer_rsrc(A, M * (int)lda * 4), rb = buffer_rsrc(B, K * (int)ldb * 4);
   f32x4 a4[NMA][KBW];
 #pragma unroll
   for (int t = 0; t < NM; ++t)
 #pragma unroll
     for (int c = 0; c < KBW; ++c) {
       const int row = 16 * t + r, k = 16 * ((int)kb0 + c) + 4 * q;
-      a4[t][c] = __builtin_bit_cast(
-          f32x4, __builtin_amdgcn_raw_buffer_load_b128(ra, (row * (int)lda + (k < K ? k : 0)) * 4, 0, 0));
+      a4[t][c] = buf_load_f32x4(ra, (row * (int)lda + (k < K ? k : 0)) * 4);
     }
   f32x4 r4[kWkRem][KBW];   // VREM: rows 16 NM + i, i < M % 16 (a row past M lies past the resource: 0)
   if (VREM) {
@@ -440,8 +425,7 @@ gemm_smallm_wk_kernel(int32_t M, int32_t N, int32_t K, const float* __restrict__
 #pragma unroll
       for (int c = 0; c < KBW; ++c) {
         const int k = 16 * ((int)kb0 + c) + 4 * q;
-        r4[i][c] = __builtin_bit_cast(
-            f32x4, __builtin_amdgcn_raw_buffer_load_b128(ra, ((16 * NM + i) * (int)lda + (k < K ? k : 0)) * 4, 0, 0));
+        r4[i][c] = buf_load_f32x4(ra, ((16 * NM + i) * (int)lda + (k < K ? k : 0)) * 4);
       }
   }
   float b[KBW][4][NTG];
@@ -452,7 +436,7 @@ gemm_smallm_wk_kernel(int32_t M, int32_t N, int32_t K, const float* __restrict__
 #pragma unroll
       for (int u = 0; u < NTG; ++u) {
         const int k = 16 * ((int)kb0 + c) + 4 * q + j, n = (int)n0 + 16 * u + r;
-        b[c][j][u] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rb, (k * (int)ldb + n) * 4, 0, 0));
+        b[c][j][u] = buf_load_f32(rb, (k * (int)ldb + n) * 4);
       }
   // A's components past K zeroed by bit masks once every load is issued (as a
   // select, each A load compiled into a branch with its own vmcnt(0): eight
@@ -609,17 +593,14 @@ gemm_slab_reduce4_buf_kernel(int32_t M, int32_t N, int32_t S, int32_t per, const
   const uint32_t total4 = (uint32_t)(M * N) / 4, stride = total4 * 16;   // float4 per slab, bytes per slab
   const uint32_t o = blockIdx.x * kRedItems + i;
   const uint32_t s0 = g * per, s1 = min((uint32_t)S, s0 + per);
-  const __amdgpu_buffer_rsrc_t rs =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(slab), (short)0, (int)(S * stride), 0x00020000);
-  constexpr uint32_t kPast = 0x7ff00000;   // past any resource the host admits
+  const __amdgpu_buffer_rsrc_t rs = buffer_rsrc(slab, S * stride);
   const bool ook = o < total4;
   uint32_t off = s0 * stride + o * 16;
   f32x4 v[B];
   auto fetch = [&](uint32_t s) __attribute__((always_inline)) {
 #pragma unroll
     for (int j = 0; j < B; ++j)
-      v[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                                           rs, (int)(ook && s + j < s1 ? off + j * stride : kPast), 0, 0));
+      v[j] = buf_load_f32x4(rs, ook && s + j < s1 ? off + j * stride : kBufOob);
   };
   f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
   fetch(s0);
@@ -653,10 +634,10 @@ gemm_slab_reduce4_buf_kernel(int32_t M, int32_t N, int32_t S, int32_t per, const
 }
 
 // Whether the slab sum may take gemm_slab_reduce4_buf_kernel: every offset it
-// forms ((s0 + per + B) slabs at most, s0 + per <= S + 15) below kBufSpanLimit,
+// forms ((s0 + per + B) slabs at most, s0 + per <= S + 15) below kBufOob,
 // 16-B rows of C for the one store.
 inline bool slab_reduce_buf(int32_t M, int32_t N, int32_t S, const float* slab, const float* C, int64_t ldc) {
-  return ((int64_t)S + 2 * kRedGroups) * M * N * 4 < kBufSpanLimit && ldc % 4 == 0 && aligned16(C) && aligned16(slab);
+  return ((int64_t)S + 2 * kRedGroups) * M * N * 4 < kBufOob && ldc % 4 == 0 && aligned16(C) && aligned16(slab);
 }
 
 // Sum split-K slabs in slab order, then apply the epilogue.
@@ -787,7 +768,7 @@ inline int64_t smallm_slabs(int32_t K) { return ((int64_t)K + 8 * 16 * GCNK_WK_K
 // operand spans more than the 32-bit offsets of a buffer resource
 inline bool tiled_ptr_fetch(bool ta, bool tb, int32_t M, int32_t N, int32_t K, int64_t lda, int64_t ldb) {
   const int64_t a_bytes = (ta ? (int64_t)K : (int64_t)M) * lda * 4, b_bytes = (tb ? (int64_t)N : (int64_t)K) * ldb * 4;
-  return !(a_bytes < kBufSpanLimit && b_bytes < kBufSpanLimit);
+  return !(a_bytes < kBufOob && b_bytes < kBufOob);
 }
 
 inline GemmRoute gemm_route(bool ta, bool tb, int32_t M, int32_t N, int32_t K, int64_t lda, int64_t ldb, bool a16,

@@ -39,10 +39,6 @@ struct KeepArgs {
   int32_t hold;                     // GCNK_KEEP_HOLD_STATE
 };
 
-typedef uint32_t u4a __attribute__((ext_vector_type(4), aligned(16)));
-
-__device__ __forceinline__ void store16(u4a* p, const u4a& v) { __builtin_nontemporal_store(v, p); }
-
 static_assert(kChunk == kPieces * 4 * kThreads && kPieces >= 1, "a workgroup holds a chunk as whole 16-B pieces per thread");
 
 __global__ void __launch_bounds__(kThreads) keep_kernel(const KeepArgs a, const gcnk_epoch_state* __restrict__ es,
@@ -73,8 +69,8 @@ __global__ void __launch_bounds__(kThreads) keep_kernel(const KeepArgs a, const 
     }
   // (without work, a launch of empty tensors only, the state is still updated)
   const chunks::Span<kChunk> s(blk - first, head, blk < a.tab.first[kMaxTensors], numel);
-  const u4a* s4 = reinterpret_cast<const u4a*>(src + s.e0);
-  u4a* d4 = reinterpret_cast<u4a*>(dst + s.e0);
+  const u32x4a* s4 = reinterpret_cast<const u32x4a*>(src + s.e0);
+  u32x4a* d4 = reinterpret_cast<u32x4a*>(dst + s.e0);
 
   if (tid == 0) { s_word[0] = epoch; s_word[1] = counter; s_word[2] = seen; }
   __syncthreads();
@@ -94,13 +90,13 @@ __global__ void __launch_bounds__(kThreads) keep_kernel(const KeepArgs a, const 
     for (int64_t e = s.e0 + tid; e < s.e1; e += kThreads) dst[e] = src[e];
     return;
   }
-  u4a v[kPieces];   // every load of the chunk in flight before its first store
+  u32x4a v[kPieces];   // every load of the chunk in flight before its first store
 #pragma unroll
   for (int it = 0; it < kPieces; ++it)
     if (tid + kThreads * it < s.n4) v[it] = s4[tid + kThreads * it];
 #pragma unroll
   for (int it = 0; it < kPieces; ++it)
-    if (tid + kThreads * it < s.n4) store16(d4 + tid + kThreads * it, v[it]);
+    if (tid + kThreads * it < s.n4) store16_nt(d4 + tid + kThreads * it, v[it]);
   const int64_t e = s.edge(tid);
   if (e >= 0) dst[e] = src[e];
 }

@@ -73,30 +73,27 @@ constexpr int kHeavyU = GCNK_HEAVY_U;
 constexpr int kRowU = GCNK_ROW_U;
 
 
-// Coherent (sc1) raw-buffer accesses from a wave-uniform base (see RowPlan).
-typedef float f32v4 __attribute__((ext_vector_type(4)));
-constexpr int kBufSc1 = 16;               // cache-policy aux bit sc1 (gfx94x/gfx950)
-constexpr int kBufDword3 = 0x00020000;    // raw buffer resource word 3 (gfx9)
+// Coherent (sc1) raw-buffer accesses from a wave-uniform base (see RowPlan).  The
+// resource bounds nothing (the largest num_records): the host checks the offsets.
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t row_rsrc(const float* base_uniform) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base_uniform), (short)0, 0x7fffffff, kBufDword3);
+  return buffer_rsrc(base_uniform, 0x7fffffff);
 }
 __device__ __forceinline__ void store_coherent_v(const float* base_uniform, int64_t off, const float4& v) {
-  const f32v4 x = {v.x, v.y, v.z, v.w};
-  __builtin_amdgcn_raw_buffer_store_b128(x, row_rsrc(base_uniform), (int)(off * 4), 0, kBufSc1);
+  buf_store_f32x4<kBufSc1>(f32x4{v.x, v.y, v.z, v.w}, row_rsrc(base_uniform), (uint32_t)(off * 4));
 }
 __device__ __forceinline__ void store_coherent_v(const float* base_uniform, int64_t off, const float& v) {
-  __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), row_rsrc(base_uniform), (int)(off * 4), 0, kBufSc1);
+  buf_store_f32<kBufSc1>(v, row_rsrc(base_uniform), (uint32_t)(off * 4));
 }
 template <typename T>
 __device__ __forceinline__ T load_coherent_v(const float* base_uniform, int64_t off);
 template <>
 __device__ __forceinline__ float4 load_coherent_v<float4>(const float* base_uniform, int64_t off) {
-  const f32v4 x = __builtin_amdgcn_raw_buffer_load_b128(row_rsrc(base_uniform), (int)(off * 4), 0, kBufSc1);
+  const f32x4 x = buf_load_f32x4<kBufSc1>(row_rsrc(base_uniform), (uint32_t)(off * 4));
   return make_float4(x.x, x.y, x.z, x.w);
 }
 template <>
 __device__ __forceinline__ float load_coherent_v<float>(const float* base_uniform, int64_t off) {
-  return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(row_rsrc(base_uniform), (int)(off * 4), 0, kBufSc1));
+  return buf_load_f32<kBufSc1>(row_rsrc(base_uniform), (uint32_t)(off * 4));
 }
 __device__ __forceinline__ const float* uniform_ptr(const float* p) {
   const uint64_t u = reinterpret_cast<uint64_t>(p);
@@ -383,6 +380,32 @@ __device__ __forceinline__ void gather_rows(const int2* __restrict__ items, int3
   }
 }
 
+// One batch of a wave-broadcast gather: acc += val * B[col, ..] over items
+// j0 .. min(j0 + U, cnt) - 1 of the wave (lane l holds item l in `mine`; j0 and
+// cnt wave-uniform), each broadcast with v_readlane, the U gathers all issued
+// before the first FMA.
+template <int VEC, int U, bool O32>
+__device__ __forceinline__ void gather_batch(const int2& mine, int32_t j0, int32_t cnt, const float* __restrict__ B,
+                                             int64_t ldb, uint32_t ldb4, int64_t colc, uint32_t col4,
+                                             typename Vec<VEC>::T& acc) {
+  using V = Vec<VEC>;
+  typename V::T g[U];
+  float a[U];
+#pragma unroll
+  for (int j = 0; j < U; ++j) {
+    g[j] = V::zero();
+    a[j] = 0.f;
+    if (j0 + j < cnt) {
+      const int32_t c = __builtin_amdgcn_readlane(mine.x, j0 + j);
+      a[j] = __int_as_float(__builtin_amdgcn_readlane(mine.y, j0 + j));
+      g[j] = load_row<VEC, O32>(B, ldb, ldb4, c, colc, col4);
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < U; ++j)
+    if (j0 + j < cnt) V::fma(acc, a[j], g[j]);
+}
+
 // Whole-wavefront groups (LPR == 64; b, e, q wave-uniform): the same sum, but
 // the items come in with ONE vector load per 64 of them (lane l holds item
 // b + q + S*l) and are broadcast with v_readlane, so a batch of U gathers
@@ -392,8 +415,6 @@ template <int VEC, int U, int S, bool O32>
 __device__ __forceinline__ void gather_rows_wave(const int2* __restrict__ items, int32_t b, int32_t e, int q,
                                                  const float* __restrict__ B, int64_t ldb, int64_t colv, bool colok,
                                                  typename Vec<VEC>::T& acc) {
-  using V = Vec<VEC>;
-  using T = typename V::T;
   const int lane = threadIdx.x & 63;
   const uint32_t ldb4 = (uint32_t)ldb * 4u, col4 = colok ? (uint32_t)colv * 4u : 0u;
   const int64_t colc = colok ? colv : 0;  // idle lanes read inside the row (no branch around the load)
@@ -407,23 +428,7 @@ __device__ __forceinline__ void gather_rows_wave(const int2* __restrict__ items,
     // batch of U gathers ran one at a time (ISA of round 3's kernel)
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) expcnt(7) lgkmcnt(15)
     const int32_t cnt = min(64, (e - base + S - 1) / S);  // wave-uniform
-    for (int32_t j0 = 0; j0 < cnt; j0 += U) {
-      T g[U];
-      float a[U];
-#pragma unroll
-      for (int j = 0; j < U; ++j) {
-        g[j] = V::zero();
-        a[j] = 0.f;
-        if (j0 + j < cnt) {
-          const int32_t c = __builtin_amdgcn_readlane(mine.x, j0 + j);
-          a[j] = __int_as_float(__builtin_amdgcn_readlane(mine.y, j0 + j));
-          g[j] = load_row<VEC, O32>(B, ldb, ldb4, c, colc, col4);
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < U; ++j)
-        if (j0 + j < cnt) V::fma(acc, a[j], g[j]);
-    }
+    for (int32_t j0 = 0; j0 < cnt; j0 += U) gather_batch<VEC, U, O32>(mine, j0, cnt, B, ldb, ldb4, colc, col4, acc);
   }
 }
 
@@ -434,8 +439,6 @@ template <int VEC, int U, int S, bool O32>
 __device__ __forceinline__ void gather_rows_wave_direct(const int2* __restrict__ hi, int32_t segp, int q,
                                                         const float* __restrict__ B, int64_t ldb, int64_t colv,
                                                         bool colok, typename Vec<VEC>::T& acc) {
-  using V = Vec<VEC>;
-  using T = typename V::T;
   const int lane = threadIdx.x & 63;
   const uint32_t ldb4 = (uint32_t)ldb * 4u, col4 = colok ? (uint32_t)colv * 4u : 0u;
   const int64_t colc = colok ? colv : 0;
@@ -445,23 +448,7 @@ __device__ __forceinline__ void gather_rows_wave_direct(const int2* __restrict__
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the item words (and the unit word) have landed
     // the segment's items are packed at the front: the valid lanes are a prefix
     const int32_t cnt = __builtin_popcountll(__ballot(mine.x >= 0));  // wave-uniform
-    for (int32_t j0 = 0; j0 < cnt; j0 += U) {
-      T g[U];
-      float a[U];
-#pragma unroll
-      for (int j = 0; j < U; ++j) {
-        g[j] = V::zero();
-        a[j] = 0.f;
-        if (j0 + j < cnt) {
-          const int32_t c = __builtin_amdgcn_readlane(mine.x, j0 + j);
-          a[j] = __int_as_float(__builtin_amdgcn_readlane(mine.y, j0 + j));
-          g[j] = load_row<VEC, O32>(B, ldb, ldb4, c, colc, col4);
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < U; ++j)
-        if (j0 + j < cnt) V::fma(acc, a[j], g[j]);
-    }
+    for (int32_t j0 = 0; j0 < cnt; j0 += U) gather_batch<VEC, U, O32>(mine, j0, cnt, B, ldb, ldb4, colc, col4, acc);
     if (cnt < 64) break;
   }
 }
@@ -478,12 +465,6 @@ __device__ __forceinline__ void wave_group_sum(T& acc) {
   }
 }
 
-__device__ __forceinline__ void store_nt(float* p, const float4& v) {
-  typedef float f4a __attribute__((ext_vector_type(4), aligned(16)));
-  __builtin_nontemporal_store(f4a{v.x, v.y, v.z, v.w}, reinterpret_cast<f4a*>(p));
-}
-__device__ __forceinline__ void store_nt(float* p, const float& v) { __builtin_nontemporal_store(v, p); }
-
 // Epilogue + store (+ fused projection) of one finished row by lane group
 // q == 0 of the calling lanes.
 template <int LPR, int VEC, int NP>
@@ -495,7 +476,7 @@ __device__ __forceinline__ void finish_row(const typename Vec<VEC>::T& acc, int3
   using T = typename V::T;
   const T h = colok ? V::epi(epi, acc, bv, r, colv) : V::zero();
   // nontemporal: no dirty output lines left in the XCD L2s for the end-of-kernel write-back
-  if (colok && store_main) store_nt(C + (int64_t)r * ldc + colv, h);
+  if (colok && store_main) V::store_nt(C + (int64_t)r * ldc + colv, h);
   proj.apply(pa, &h, r, lg);
 }
 
@@ -763,7 +744,6 @@ __global__ void __launch_bounds__(256) spmm_heavy_top_kernel(const int4* __restr
 // contiguous).  acc[nt] += A(16x4) * B(4x16) over 16 k-steps.
 //   A operand lane l: A[row l&15][k l>>4];  B operand: B[k l>>4][col l&15];
 //   C/D reg j: row (l>>4)*4 + j, col l&15   (gfx950 16x16x4 f32 maps).
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 template <bool VEC4, int NT, bool DIAG>
 __device__ __forceinline__ void tile_body(int32_t bx, const int4* __restrict__ tdesc, const int32_t* __restrict__ tcols,
@@ -1353,14 +1333,10 @@ static int spmm_impl(const void* plan, const int32_t* hdr, const float* B, int64
               (long long)ldc, F);
     return GCNK_EARG;
   }
-  if (epilogue < GCNK_EPI_NONE || epilogue > GCNK_EPI_BIAS_RELU_HASH) {
-    set_error("gcnk_spmm_csr_f32: unknown epilogue %d", epilogue);
-    return GCNK_EARG;
-  }
-  if (epilogue == GCNK_EPI_BIAS_RELU_DROP && (!drop_mask || ldm < F)) {
-    set_error("gcnk_spmm_csr_f32: dropout epilogue needs a mask with ldm >= F");
-    return GCNK_EARG;
-  }
+  Epi e;
+  const int erc = make_epi(proj ? "gcnk_spmm_proj_f32" : "gcnk_spmm_csr_f32", bias, epilogue, drop_mask, ldm, drop_scale,
+                           keep_prob, seed, offset, rng_base, F, kEpiAllCodes, &e);
+  if (erc) return erc;
   const int lpr = choose_lpr(F, lanes_hint);
   if (hdr[kHdrGroups] != 64 / lpr) {
     set_error("gcnk_spmm_csr_f32: plan built for %d lane groups per wavefront, this F/lanes uses %d (gcnk_spmm_groups)",
@@ -1379,18 +1355,6 @@ static int spmm_impl(const void* plan, const int32_t* hdr, const float* B, int64
               (long long)counter_bytes);
     return GCNK_EARG;
   }
-  Epi e;
-  e.bias = bias;
-  e.mask = drop_mask;
-  e.ldm = epilogue == GCNK_EPI_BIAS_RELU_HASH ? (ldm > 0 ? ldm : F) : ldm;
-  e.scale = drop_scale;
-  e.keep_prob = keep_prob;
-  e.seed_lo = (uint32_t)seed;
-  e.seed_hi = (uint32_t)(seed >> 32);
-  e.offset = offset;
-  e.rng_base = rng_base;
-  e.code = epilogue;
-  e.stamps = g_stamps;
   const bool vec4 = (F % 4 == 0) && (ldb % 4 == 0) && (ldc % 4 == 0) && aligned16(B) && (!C || aligned16(C)) &&
                     (!workspace || aligned16(workspace)) && (!bias || aligned16(bias));
   hipStream_t s = (hipStream_t)stream;

@@ -12,10 +12,8 @@ namespace {
 
 __global__ void __launch_bounds__(256) stream_copy_kernel(const float4* __restrict__ src, float4* __restrict__ dst,
                                                           int64_t n4) {
-  typedef float f4a __attribute__((ext_vector_type(4), aligned(16)));
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
-    const float4 v = src[i];
-    __builtin_nontemporal_store(f4a{v.x, v.y, v.z, v.w}, reinterpret_cast<f4a*>(dst + i));
+    store16_nt(reinterpret_cast<float*>(dst + i), src[i]);
   }
 }
 
