@@ -191,6 +191,15 @@ SIGNATURES = {
         _vp, _vp, _vp, _vp, _vp, _vp,     # diag, pre, hub_ids (host), hub_rp (host), hub_ci, hub_val
         _vp, _i64, _vp, _vp, _i64,        # S2, lds2, b2, out, ldo
         _vp]),                            # stream
+    "gcnk_score_docs_f32": (ctypes.c_int, [
+        _i32, _i32, _i32, _i32, _i32, _i32,   # B, F, Kc, H, P, k0
+        _vp, _i64, _vp, _i64,             # x, ldx, a, lda
+        _vp, _i64, _vp, _i64,             # W1, ldw1, S_T, lds
+        _vp, _i64, _vp, _i64,             # W2, ldw2, S2_T, lds2
+        _vp, _vp, _vp,                    # dh (float64), b1, b2
+        _vp, _i64, _vp, _vp]),            # out, ldo, labels (int32), stream
+    # F, Kc, H, P, out8
+    "gcnk_score_docs_route": (ctypes.c_int, [_i32, _i32, _i32, _i32, _vp]),
     # rowptr, colind, val, M, hub_index, perm, diag, pre, stream
     "gcnk_factor_diag_f32": (ctypes.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "gcnk_dense_gc1_f32": (ctypes.c_int, [
@@ -252,7 +261,7 @@ SIGNATURES = {
 # added within ABI 13 (gc2 from the hub factor, the backward's and the factored gc1's route reports): absent from
 # variants of an older tree
 NEWER_THAN_SOME_VARIANTS = ("gcnk_hubfactor_gc2_f32", "gcnk_factor_diag_f32", "gcnk_gcn_bwd2_route",
-                            "gcnk_hubfactor_gc1_route")
+                            "gcnk_hubfactor_gc1_route", "gcnk_score_docs_f32", "gcnk_score_docs_route")
 
 _lock = threading.Lock()
 _lib = None

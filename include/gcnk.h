@@ -55,7 +55,8 @@ extern "C" {
 
 /* ABI note: 13 also covers gcnk_factor_diag_f32, gcnk_hubfactor_gc2_f32, the
  * gc2_* fields at the end of gcnk_gcn_fwd and the route reports
- * gcnk_gcn_bwd2_route / gcnk_hubfactor_gc1_route (additions only: no existing
+ * gcnk_gcn_bwd2_route / gcnk_hubfactor_gc1_route and held-graph scoring,
+ * gcnk_score_docs_f32 / gcnk_score_docs_route (additions only: no existing
  * symbol, field offset or meaning changed, so the number stayed). */
 #define GCNK_ABI_VERSION 13
 
@@ -357,6 +358,55 @@ int gcnk_hubfactor_gc2_f32(int32_t M, int32_t H, int32_t P, const int32_t* rec, 
                            const float* diag, const int32_t* pre, const int32_t* hub_ids /* host */,
                            const int32_t* hub_rp /* host */, const int32_t* hub_ci, const float* hub_val,
                            const float* S2, int64_t lds2, const float* b2, float* out, int64_t ldo, void* stream);
+/* ---------------------------------------------------------------------------
+ * Held-graph scoring (csrc/score_docs.hip; within ABI 13, an addition only):
+ * the logits of B documents that are not in the training graph, each as the
+ * row it would have in the transductive forward (GCN.forward layer.py:164-190)
+ * with the hub nodes' state held as the training graph left it -- for the
+ * (A-hat, X) structure above: a document row of A-hat holds its diagonal and
+ * hub columns only, a document row of X the columns k0 .. k0 + Kc.
+ *   x [B x Kc] (ldx)   the document's feature values on columns k0 .. k0 + Kc
+ *   a [B x H] (lda)    its raw edge weight to each hub (0: no edge).  Negative
+ *                      or non-finite weights are the caller's error: they are
+ *                      NOT checked on the device.
+ *   W1 (ldw1)          gc1's weight; rows k0 .. k0 + Kc - 1 are read
+ *   S_T [H x F] (lds)  X[hubs] W1 of the training graph
+ *   W2 [F x P] (ldw2), S2_T [H x P] (lds2) = (H1 W2)[hubs] of its eval forward
+ *   dh [H] float64     the hubs' D^-1/2 (sqrt of A-hat's hub diagonal), device
+ *   b1 [F], b2 [P]     nullable
+ * Per document d (coefficients: A-hat's recipe, float64 rounded to fp32 once):
+ *   deg    = 1 + sum_j a[d, j]                 (float64, j ascending)
+ *   dd     = deg^-1/2,  c_self = fp32(dd dd),  c_j = fp32((dd a[d, j]) dh[j])
+ *   z[n]   = c_self sum_k x[d, k] W1[k0 + k, n] + sum_j c_j S_T[j, n] + b1[n]
+ *   h[n]   = max(z[n], 0)                      (a NaN stays a NaN)
+ *   out[d, p] = c_self sum_n h[n] W2[n, p] + sum_j c_j S2_T[j, p] + b2[p]
+ *   labels[d] = first index of the maximum of out[d, :], a NaN maximal
+ *               (gcnk_class_stats' rule); labels nullable (int32 [B]).
+ * One launch on `stream`, fp32 MFMA with fixed-order sums, no atomics, no
+ * workspace: bitwise reproducible and capturable.  B = 0 returns GCNK_OK
+ * without touching the device.  GCNK_EARG: bad sizes, a null operand, a leading
+ * dimension shorter than its row.  GCNK_EUNSUP outside gcnk_hubfactor_gc1_f32's
+ * range -- F % 4 == 0, F <= 256, Kc <= 128, H <= 128, P <= 32 -- or where the
+ * rows of x, a, W1 or S_T are not 16-B aligned (base and leading dimension).
+ * ------------------------------------------------------------------------- */
+int gcnk_score_docs_f32(int32_t B, int32_t F, int32_t Kc, int32_t H, int32_t P, int32_t k0, const float* x,
+                        int64_t ldx, const float* a, int64_t lda, const float* W1, int64_t ldw1, const float* S_T,
+                        int64_t lds, const float* W2, int64_t ldw2, const float* S2_T, int64_t lds2,
+                        const double* dh, const float* b1, const float* b2, float* out, int64_t ldo,
+                        int32_t* labels, void* stream);
+/* Test aid (an addition only): what gcnk_score_docs_f32 launches for a shape, from
+ * the host function the launch itself is made from (nothing is launched, no GPU
+ * is needed).  out8 =
+ *   0 NTQ, 1 NP, 2 KHQ   the instantiation score_docs_kernel<NTQ, NP, KHQ>: 16-column
+ *                        tiles of F per wave (2, 3, 4), n-tiles of P (1, 2), k-steps
+ *                        of the hub sum per quarter (4, 8)
+ *   3 rows of [W1[k0:k0+Kc]; S_T] staged in LDS at a time (a multiple of 4)
+ *   4 operand row stride in LDS (floats, = 4 mod 64)
+ *   5 operand row columns the kernel writes: [c_self x | c | 0]; the MFMA k-loop
+ *     reads columns 0 .. roundup4(Kc + H) - 1, the hub sum Kc .. Kc + 16 KHQ - 1
+ *   6 dynamic LDS bytes of the launch      7 workgroups per 32 documents (1)
+ * GCNK_EARG / GCNK_EUNSUP where gcnk_score_docs_f32 returns them for these sizes. */
+int gcnk_score_docs_route(int32_t F, int32_t Kc, int32_t H, int32_t P, int64_t* out8);
 /* ---------------------------------------------------------------------------
  * Narrow-feature gc1 (csrc/dense_gc1.hip; GCN.forward layer.py:164-190 through
  * layer.py:102,106,110,182,185 and gc2's support layer.py:102) for a dense X
