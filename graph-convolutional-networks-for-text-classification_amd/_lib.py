@@ -44,6 +44,8 @@ GEMM_EPI_NONE, GEMM_EPI_BIAS, GEMM_EPI_BIAS_RELU, GEMM_EPI_MASK_POS = 0, 1, 2, 5
 (GEMM_ROUTE_NARROW, GEMM_ROUTE_SKINNY, GEMM_ROUTE_SHORTK, GEMM_ROUTE_SMALLM, GEMM_ROUTE_TILED_N16,
  GEMM_ROUTE_TILED) = 1, 2, 3, 4, 5, 6
 GEMM_ROUTE_SPLIT, GEMM_ROUTE_PTR_FETCH = 1, 2
+# gcnk_spmm_route's aligned16 mask (gcnk.h GCNK_SPMM_ALIGNED_*)
+SPMM_ALIGNED_B, SPMM_ALIGNED_C, SPMM_ALIGNED_BIAS, SPMM_ALIGNED_WORKSPACE, SPMM_ALIGNED_ALL = 1, 2, 4, 8, 15
 
 _vp, _i32, _i64, _u64, _f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float
 _f64 = ctypes.c_double
@@ -154,6 +156,8 @@ SIGNATURES = {
         _vp, _i64,                # counters, counter_bytes
         _i32, _vp,                # lanes_hint, stream
     ]),
+    # plan header (host), F, ldb, ldc, aligned16 mask, lanes_hint, P, part, out16
+    "gcnk_spmm_route": (ctypes.c_int, [_vp, _i32, _i64, _i64, _i32, _i32, _i32, _i32, _vp]),
     "gcnk_gemm_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32]),
     "gcnk_gemm_f32": (ctypes.c_int, [
         _i32, _i32, _i32, _i32, _i32,   # transA, transB, M, N, K
@@ -261,7 +265,8 @@ SIGNATURES = {
 # added within ABI 13 (gc2 from the hub factor, the backward's and the factored gc1's route reports): absent from
 # variants of an older tree
 NEWER_THAN_SOME_VARIANTS = ("gcnk_hubfactor_gc2_f32", "gcnk_factor_diag_f32", "gcnk_gcn_bwd2_route",
-                            "gcnk_hubfactor_gc1_route", "gcnk_score_docs_f32", "gcnk_score_docs_route")
+                            "gcnk_hubfactor_gc1_route", "gcnk_score_docs_f32", "gcnk_score_docs_route",
+                            "gcnk_spmm_route")
 
 _lock = threading.Lock()
 _lib = None

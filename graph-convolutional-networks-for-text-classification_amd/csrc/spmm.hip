@@ -1097,36 +1097,176 @@ struct RowLaunch {
   hipStream_t s;
 };
 
-template <int LPR, int VEC, int U, int NP>
-int launch_rows(const RowLaunch& a) {
-  constexpr RowGeom G = row_geom(LPR);
-  constexpr int BLOCK = G.block;
-  const int64_t nhb = ((int64_t)a.rp.nhunits + G.hpb - 1) / G.hpb;                 // heavy workgroups
-  const int64_t nlb = ((int64_t)a.rp.nunits - a.rp.nhunits + G.lpb - 1) / G.lpb;  // light workgroups
-  if (nhb + nlb == 0) return GCNK_OK;
-  if (nhb + nlb > (int64_t)INT32_MAX) {
-    set_error("gcnk_spmm_csr_f32: %lld workgroups exceed the grid", (long long)(nhb + nlb));
+// One column window of the row kernel: at most kMaxColTiles column tiles from
+// column c0 (arrival counters per heavy row x tile; the last arriver re-arms
+// them, so consecutive windows on one stream reuse them).  o32: 32-bit gather
+// offsets, when every byte the launch reads lies within 4 GB of its B base.
+struct RowWindow {
+  int64_t c0;
+  int32_t Fw;
+  bool o32;
+};
+inline RowWindow row_window(int64_t w, int64_t tileF, int32_t F, int32_t K, int64_t ldb) {
+  const int64_t c0 = w * kMaxColTiles * tileF;
+  const int32_t Fw = (int32_t)std::min<int64_t>(F - c0, kMaxColTiles * tileF);
+  return RowWindow{c0, Fw, (int64_t)K * ldb * 4 + (int64_t)Fw * 4 < ((int64_t)1 << 32)};
+}
+
+// The tile kernel's n-tiles per workgroup for column slices of nt_need n-tiles (0: none compiled).
+constexpr int tile_nt(int nt_need) {
+  return nt_need <= 1 ? 1 : nt_need <= 2 ? 2 : nt_need <= 4 ? 4 : nt_need <= 6 ? 6 : nt_need <= 7 ? 7
+       : nt_need <= 8 ? 8 : (kMaxNT > 8 && nt_need <= 13) ? 13 : nt_need <= kMaxNT ? kMaxNT : 0;
+}
+
+// spmm_route decides, from the plan header and the arguments alone, what
+// spmm_impl launches; spmm_impl launches by switching on its result, and
+// gcnk_spmm_route (include/gcnk.h) reports it to tests.
+//
+// Every instantiation this file compiles (tests/spmm_cases.py mirrors the
+// list; tests/test_spmm_cases.py checks on the CPU that the case table reaches
+// each reachable one, tests/test_spmm_routes.py compares each with float64):
+//   spmm_row_kernel<BLOCK, LPR, VEC, kRowU, 0, O32>   LPR 1 2 4 8 16 32 64 x VEC 4 1 x O32: 28, all reachable
+//     (LPR = choose_lpr(F, lanes_hint); VEC = 4 iff F, ldb, ldc % 4 == 0 and B, C, bias, workspace
+//     are 16-B aligned; O32 iff K ldb 4 + Fw 4 < 2^32 for the window's Fw columns)
+//   spmm_row_kernel<256, LPR, 4, 8, NP, O32>          LPR 16 32 64 x NP 8 32 x O32: 12, all reachable
+//     (gcnk_spmm_proj_f32: P <= 8 / <= 32; F <= 4 LPR, no tile chunks, no tops)
+//   spmm_heavy_top_kernel<VEC>                        VEC 4 1: 2, both reachable (plans with tops)
+//   spmm_tile_kernel<VEC4, NT, DIAG>                  VEC4 x NT 1 2 4 x DIAG: 12, all reachable
+//     (NT = tile_nt of the balanced slice: F <= 16, <= 32, wider; DIAG: the plan keeps a diagonal aside)
+//   spmm_tile_kernel<VEC4, NT, DIAG>                  VEC4 x NT 6 7 8 x DIAG: 12, compiled and UNREACHABLE at the
+//     default GCNK_TILE_MAXNT = 4: a balanced slice never needs more than kMaxNT n-tiles, so tile_nt names
+//     them only in a build that raises it (NT 13 is compiled only past GCNK_TILE_MAXNT = 8).  They are left
+//     in launch_tile_v: taking them out renumbers the labels of the kernels after them in `make isa`.
+//   spmm_tile_reduce_kernel                           1, reachable (multi-chunk tile blocks)
+struct SpmmRoute {
+  bool empty;           // an operand of no rows, or F = 0: nothing to do
+  bool rows;            // spmm_row_kernel launches
+  int lpr, vec, np;     // its LPR, VEC and NP (0: no projection)
+  int32_t windows;      // column windows (launches)
+  bool o32_first, o32_last;
+  bool top;             // spmm_heavy_top_kernel<vec> follows
+  int64_t nhb, nlb;     // heavy / light workgroups
+  bool tile;            // spmm_tile_kernel launches
+  bool tile_v4;
+  int tile_nt;
+  bool tile_diag;
+  int32_t tile_slices;  // column slices of tile_nt n-tiles
+  int32_t item0, nitems;  // its chunk items
+  bool tile_reduce;     // spmm_tile_reduce_kernel follows
+};
+
+// ptrs16: B, C, bias and the workspace are 16-B aligned (those that are given).
+// P = 0: no projection.  Returns the launch's code; rt is complete only for GCNK_OK.
+int spmm_route(const int32_t* hdr, int32_t F, int64_t ldb, int64_t ldc, bool ptrs16, int32_t lanes_hint, int32_t P,
+               int32_t part, SpmmRoute& rt) {
+  rt = SpmmRoute{};
+  if (!plan_magic(hdr) || F < 0 || part < 0 || part > 2 || P < 0) {
+    set_error("gcnk_spmm_csr_f32: bad argument (plan/header missing or not a gcnk plan, F=%d)", F);
+    return GCNK_EARG;
+  }
+  if (hdr[kHdrM] == 0 || F == 0) {
+    rt.empty = true;
+    return GCNK_OK;
+  }
+  if (ldb < F || ldc < F) {
+    set_error("gcnk_spmm_csr_f32: leading dimension smaller than F (ldb=%lld ldc=%lld F=%d)", (long long)ldb,
+              (long long)ldc, F);
+    return GCNK_EARG;
+  }
+  const int lpr = choose_lpr(F, lanes_hint);
+  if (hdr[kHdrGroups] != 64 / lpr) {
+    set_error("gcnk_spmm_csr_f32: plan built for %d lane groups per wavefront, this F/lanes uses %d (gcnk_spmm_groups)",
+              hdr[kHdrGroups], 64 / lpr);
+    return GCNK_EARG;
+  }
+  const bool vec4 = (F % 4 == 0) && (ldb % 4 == 0) && (ldc % 4 == 0) && ptrs16;
+  // the projection needs whole rows in one group: row-kernel rows only, float4, one column tile
+  if (P > 0 && (hdr[kHdrNtile] > 0 || !vec4 || F > lpr * 4 || P > 32 || lpr < 16 || tops(hdr))) {
+    set_error("gcnk_spmm_proj_f32: fused projection unsupported here (tile chunks=%d vec4=%d F=%d P=%d lanes=%d)",
+              hdr[kHdrNtile], (int)vec4, F, P, lpr);
     return GCNK_EUNSUP;
   }
+  const Layout L(hdr);
+  const int64_t part_ld = ((int64_t)F + 3) & ~3LL;
+  if ((int64_t)kMaxSeg * part_ld * 4 >= ((int64_t)1 << 31)) {  // partial-slot byte offsets of one heavy row
+    set_error("gcnk_spmm: F = %d too wide for the partial-slot offsets", F);
+    return GCNK_EUNSUP;
+  }
+  // ---- dense blocks: tile kernel (+ slab reduce)
+  if (L.ntile > 0) {
+    // column slices of <= kMaxNT n-tiles on grid.y, balanced (F = 200: 4 x 4 n-tiles),
+    // so two workgroups of a chunk share the staging/MFMA/store phases of a CU
+    const int32_t nt_total = (int32_t)(tile_fpad(F) / 16);
+    const int32_t nslices = (nt_total + kMaxNT - 1) / kMaxNT;
+    if (nslices > 65535) {
+      set_error("gcnk_spmm_csr_f32: F=%d needs %d tile column slices (> 65535)", F, nslices);
+      return GCNK_EUNSUP;
+    }
+    const int nt_need = (nt_total + nslices - 1) / nslices;
+    // part 1: the single-chunk items [0, nsingle); part 2: the rest; 0: all
+    const int32_t nsingle = hdr[kHdrNsingle];
+    rt.item0 = part == 2 ? nsingle : 0;
+    rt.nitems = (part == 1 ? nsingle : (int32_t)L.ntile) - rt.item0;
+    if (rt.nitems > 0) {
+      rt.tile_nt = tile_nt(nt_need);
+      if (!rt.tile_nt) {
+        set_error("spmm_tile_kernel: %d n-tiles exceed %d", nt_need, kMaxNT);
+        return GCNK_EUNSUP;
+      }
+      rt.tile_slices = (int32_t)((F + rt.tile_nt * 16 - 1) / (rt.tile_nt * 16));
+      const int64_t blocks = ((int64_t)rt.nitems + 7) / 8 * 8 * rt.tile_slices;
+      if (blocks > INT32_MAX) {
+        set_error("spmm_tile_kernel: %lld workgroups exceed the grid", (long long)blocks);
+        return GCNK_EUNSUP;
+      }
+      rt.tile = true;
+      rt.tile_v4 = vec4;
+      rt.tile_diag = L.has_diag;
+    }
+    rt.tile_reduce = L.nred > 0 && part != 1;
+  }
+  // ---- remaining rows: row kernel (heavy rows finished in-launch)
+  if (L.nunits > 0 && part != 1) {
+    const RowGeom G = row_geom(lpr);
+    rt.nhb = ((int64_t)L.nhunits + G.hpb - 1) / G.hpb;
+    rt.nlb = ((int64_t)L.nunits - L.nhunits + G.lpb - 1) / G.lpb;
+    if (rt.nhb + rt.nlb > (int64_t)INT32_MAX) {
+      set_error("gcnk_spmm_csr_f32: %lld workgroups exceed the grid", (long long)(rt.nhb + rt.nlb));
+      return GCNK_EUNSUP;
+    }
+    rt.rows = true;
+    rt.lpr = lpr;
+    rt.vec = (P > 0 || vec4) ? 4 : 1;
+    rt.np = P > 0 ? (P <= 8 ? 8 : 32) : 0;
+    const int64_t tileF = (int64_t)lpr * rt.vec;
+    const int64_t tiles = (F + tileF - 1) / tileF;
+    rt.windows = (int32_t)((tiles + kMaxColTiles - 1) / kMaxColTiles);
+    rt.o32_first = row_window(0, tileF, F, hdr[kHdrK], ldb).o32;
+    rt.o32_last = row_window(rt.windows - 1, tileF, F, hdr[kHdrK], ldb).o32;
+    // rows of more than kMaxSeg segments: their groups' sums, after the row kernel
+    rt.top = P == 0 && L.tops;
+  }
+  return GCNK_OK;
+}
+
+template <int LPR, int VEC, int U, int NP>
+int launch_rows(const RowLaunch& a, const SpmmRoute& rt) {
+  constexpr int BLOCK = row_geom(LPR).block;
   const int64_t tileF = (int64_t)LPR * VEC;
-  const int64_t tiles = (a.F + tileF - 1) / tileF;
-  // column windows of at most kMaxColTiles tiles (arrival counters per heavy row x tile;
-  // the last arriver re-arms them, so consecutive windows on one stream reuse them)
-  for (int64_t t0 = 0; t0 < tiles; t0 += kMaxColTiles) {
-    const int64_t c0 = t0 * tileF;
-    const int32_t Fw = (int32_t)std::min<int64_t>(a.F - c0, kMaxColTiles * tileF);
+  for (int64_t w = 0; w < rt.windows; ++w) {
+    const RowWindow rw = row_window(w, tileF, a.F, a.K, a.ldb);
+    const int64_t c0 = rw.c0;
+    const int32_t Fw = rw.Fw;
     Epi e = a.epi;
     e.bias = e.bias ? e.bias + c0 : nullptr;
     e.mask = e.mask ? e.mask + c0 : nullptr;
     e.offset += (uint64_t)c0;  // hash index shifts with the column
-    // 32-bit gather offsets when every byte the launch reads lies within 4 GB of its B base
-    const bool o32 = (int64_t)a.K * a.ldb * 4 + (int64_t)Fw * 4 < ((int64_t)1 << 32);
-    const dim3 grid((unsigned)(nhb + nlb), (unsigned)((Fw + tileF - 1) / tileF));
+    const dim3 grid((unsigned)(rt.nhb + rt.nlb), (unsigned)((Fw + tileF - 1) / tileF));
     auto launch = [&](auto kernel) {
-      hipLaunchKernelGGL(kernel, grid, dim3(BLOCK), 0, a.s, a.rp, (int32_t)nhb, a.B + c0, a.ldb, Fw,
+      hipLaunchKernelGGL(kernel, grid, dim3(BLOCK), 0, a.s, a.rp, (int32_t)rt.nhb, a.B + c0, a.ldb, Fw,
                          a.C ? a.C + c0 : nullptr, a.ldc, e, a.part ? a.part + c0 : nullptr, a.part_ld, a.pa);
     };
-    if (o32) launch(spmm_row_kernel<BLOCK, LPR, VEC, U, NP, true>);
+    if (rw.o32) launch(spmm_row_kernel<BLOCK, LPR, VEC, U, NP, true>);
     else launch(spmm_row_kernel<BLOCK, LPR, VEC, U, NP, false>);
     const int rc = launch_check("spmm_row_kernel");
     if (rc) return rc;
@@ -1135,29 +1275,29 @@ int launch_rows(const RowLaunch& a) {
 }
 
 template <int VEC>
-int dispatch_rows(int lpr, const RowLaunch& a) {
-  switch (lpr) {
-    case 1: return launch_rows<1, VEC, kRowU, 0>(a);
-    case 2: return launch_rows<2, VEC, kRowU, 0>(a);
-    case 4: return launch_rows<4, VEC, kRowU, 0>(a);
-    case 8: return launch_rows<8, VEC, kRowU, 0>(a);
-    case 16: return launch_rows<16, VEC, kRowU, 0>(a);
-    case 32: return launch_rows<32, VEC, kRowU, 0>(a);
-    case 64: return launch_rows<64, VEC, kRowU, 0>(a);
+int dispatch_rows(const RowLaunch& a, const SpmmRoute& rt) {
+  switch (rt.lpr) {
+    case 1: return launch_rows<1, VEC, kRowU, 0>(a, rt);
+    case 2: return launch_rows<2, VEC, kRowU, 0>(a, rt);
+    case 4: return launch_rows<4, VEC, kRowU, 0>(a, rt);
+    case 8: return launch_rows<8, VEC, kRowU, 0>(a, rt);
+    case 16: return launch_rows<16, VEC, kRowU, 0>(a, rt);
+    case 32: return launch_rows<32, VEC, kRowU, 0>(a, rt);
+    case 64: return launch_rows<64, VEC, kRowU, 0>(a, rt);
   }
-  set_error("gcnk_spmm_csr_f32: unsupported lanes per group %d", lpr);
+  set_error("gcnk_spmm_csr_f32: unsupported lanes per group %d", rt.lpr);
   return GCNK_EUNSUP;
 }
 
 // Fused projection variants: float4 columns, one column tile, groups of >= 16 lanes.
 template <int NP>
-int dispatch_rows_proj(int lpr, const RowLaunch& a) {
-  switch (lpr) {
-    case 16: return launch_rows<16, 4, 8, NP>(a);
-    case 32: return launch_rows<32, 4, 8, NP>(a);
-    case 64: return launch_rows<64, 4, 8, NP>(a);
+int dispatch_rows_proj(const RowLaunch& a, const SpmmRoute& rt) {
+  switch (rt.lpr) {
+    case 16: return launch_rows<16, 4, 8, NP>(a, rt);
+    case 32: return launch_rows<32, 4, 8, NP>(a, rt);
+    case 64: return launch_rows<64, 4, 8, NP>(a, rt);
   }
-  set_error("gcnk_spmm_proj_f32: no fused-projection kernel for %d lanes per group", lpr);
+  set_error("gcnk_spmm_proj_f32: no fused-projection kernel for %d lanes per group", rt.lpr);
   return GCNK_EUNSUP;
 }
 
@@ -1179,43 +1319,40 @@ struct TileArgs {
 };
 
 template <bool V4, int NT>
-int launch_tile_nt(unsigned nitems, const TileArgs& t, hipStream_t s) {
-  if (nitems == 0) return GCNK_OK;
-  const int32_t slices = (int32_t)((t.F + NT * 16 - 1) / (NT * 16));
-  const int64_t blocks = ((int64_t)nitems + 7) / 8 * 8 * slices;
-  if (blocks > INT32_MAX) {
-    set_error("spmm_tile_kernel: %lld workgroups exceed the grid", (long long)blocks);
-    return GCNK_EUNSUP;
-  }
-  if (t.dval)
+int launch_tile_nt(const SpmmRoute& rt, const TileArgs& t, hipStream_t s) {
+  const int64_t blocks = ((int64_t)rt.nitems + 7) / 8 * 8 * rt.tile_slices;
+  if (rt.tile_diag)
     hipLaunchKernelGGL((spmm_tile_kernel<V4, NT, true>), dim3((unsigned)blocks), dim3(256), 0, s, t.tdesc, t.tcols,
                        t.tfrag, t.trows, t.dval, t.F, t.B, t.ldb, t.C, t.ldc, t.epi, t.slabs, t.slab_ld, t.item0,
-                       (int32_t)nitems, slices);
+                       rt.nitems, rt.tile_slices);
   else
     hipLaunchKernelGGL((spmm_tile_kernel<V4, NT, false>), dim3((unsigned)blocks), dim3(256), 0, s, t.tdesc, t.tcols,
                        t.tfrag, t.trows, t.dval, t.F, t.B, t.ldb, t.C, t.ldc, t.epi, t.slabs, t.slab_ld, t.item0,
-                       (int32_t)nitems, slices);
+                       rt.nitems, rt.tile_slices);
   return launch_check("spmm_tile_kernel");
 }
 
+// The instantiations tile_nt can name.  (6, 7 and 8 stay compiled at the default
+// GCNK_TILE_MAXNT = 4, where no route names them: the list above spmm_route.)
 template <bool V4>
-int launch_tile_v(int nt_need, unsigned nitems, const TileArgs& t, hipStream_t s) {
-  if (nt_need <= 1) return launch_tile_nt<V4, 1>(nitems, t, s);
-  if (nt_need <= 2) return launch_tile_nt<V4, 2>(nitems, t, s);
-  if (nt_need <= 4) return launch_tile_nt<V4, 4>(nitems, t, s);
-  if (nt_need <= 6) return launch_tile_nt<V4, 6>(nitems, t, s);
-  if (nt_need <= 7) return launch_tile_nt<V4, 7>(nitems, t, s);
-  if (nt_need <= 8) return launch_tile_nt<V4, 8>(nitems, t, s);
+int launch_tile_v(const SpmmRoute& rt, const TileArgs& t, hipStream_t s) {
+  const int nt = rt.tile_nt;
+  if (nt == 1) return launch_tile_nt<V4, 1>(rt, t, s);
+  if (nt == 2) return launch_tile_nt<V4, 2>(rt, t, s);
+  if (nt == 4) return launch_tile_nt<V4, 4>(rt, t, s);
+  if (nt == 6) return launch_tile_nt<V4, 6>(rt, t, s);
+  if (nt == 7) return launch_tile_nt<V4, 7>(rt, t, s);
+  if (nt == 8) return launch_tile_nt<V4, 8>(rt, t, s);
   if constexpr (kMaxNT > 8) {
-    if (nt_need <= 13) return launch_tile_nt<V4, 13>(nitems, t, s);
+    if (nt == 13) return launch_tile_nt<V4, 13>(rt, t, s);
   }
-  if (nt_need <= kMaxNT) return launch_tile_nt<V4, kMaxNT>(nitems, t, s);
-  set_error("spmm_tile_kernel: %d n-tiles exceed %d", nt_need, kMaxNT);
+  if (nt == kMaxNT) return launch_tile_nt<V4, kMaxNT>(rt, t, s);
+  set_error("spmm_tile_kernel: no kernel of %d n-tiles", nt);
   return GCNK_EUNSUP;
 }
 
-inline int launch_tile(bool v4, int nt_need, unsigned nitems, const TileArgs& t, hipStream_t s) {
-  return v4 ? launch_tile_v<true>(nt_need, nitems, t, s) : launch_tile_v<false>(nt_need, nitems, t, s);
+inline int launch_tile(const SpmmRoute& rt, const TileArgs& t, hipStream_t s) {
+  return rt.tile_v4 ? launch_tile_v<true>(rt, t, s) : launch_tile_v<false>(rt, t, s);
 }
 
 // Device CSR -> host arrays (one-time setup: synchronises `s`).
@@ -1313,13 +1450,19 @@ static int spmm_impl(const void* plan, const int32_t* hdr, const float* B, int64
                      const ProjArgs& pa, void* stream, int32_t part = 0, const SideReduce* side = nullptr,
                      int* carried = nullptr) {
   if (carried) *carried = 0;
-  if (!plan || !plan_magic(hdr) || F < 0 || part < 0 || part > 2) {
-    set_error("gcnk_spmm_csr_f32: bad argument (plan/header missing or not a gcnk plan, F=%d)", F);
+  // what to launch, and the checks and refusals that depend on the header and the arguments alone
+  const bool proj = pa.W != nullptr;
+  SpmmRoute rt;
+  const bool ptrs16 = aligned16(B) && (!C || aligned16(C)) && (!workspace || aligned16(workspace)) &&
+                      (!bias || aligned16(bias));
+  const int rrc = spmm_route(hdr, F, ldb, ldc, ptrs16, lanes_hint, proj ? pa.P : 0, part, rt);
+  if (rrc) return rrc;
+  if (!plan) {
+    set_error("gcnk_spmm_csr_f32: null pointer");
     return GCNK_EARG;
   }
-  const int32_t M = hdr[kHdrM], K = hdr[kHdrK];
-  if (M == 0 || F == 0) return GCNK_OK;
-  const bool proj = pa.W != nullptr;
+  if (rt.empty) return GCNK_OK;
+  const int32_t K = hdr[kHdrK];
   if (proj && (!pa.C2 || pa.P <= 0 || pa.ldw < pa.P || pa.ldc2 < pa.P)) {
     set_error("gcnk_spmm_proj_f32: bad projection (P=%d)", pa.P);
     return GCNK_EARG;
@@ -1328,21 +1471,10 @@ static int spmm_impl(const void* plan, const int32_t* hdr, const float* B, int64
     set_error("gcnk_spmm_csr_f32: null pointer");
     return GCNK_EARG;
   }
-  if (ldb < F || ldc < F) {
-    set_error("gcnk_spmm_csr_f32: leading dimension smaller than F (ldb=%lld ldc=%lld F=%d)", (long long)ldb,
-              (long long)ldc, F);
-    return GCNK_EARG;
-  }
   Epi e;
   const int erc = make_epi(proj ? "gcnk_spmm_proj_f32" : "gcnk_spmm_csr_f32", bias, epilogue, drop_mask, ldm, drop_scale,
                            keep_prob, seed, offset, rng_base, F, kEpiAllCodes, &e);
   if (erc) return erc;
-  const int lpr = choose_lpr(F, lanes_hint);
-  if (hdr[kHdrGroups] != 64 / lpr) {
-    set_error("gcnk_spmm_csr_f32: plan built for %d lane groups per wavefront, this F/lanes uses %d (gcnk_spmm_groups)",
-              hdr[kHdrGroups], 64 / lpr);
-    return GCNK_EARG;
-  }
   const int64_t need = gcnk_spmm_workspace_bytes(hdr, F);
   if (need > 0 && (!workspace || workspace_bytes < need)) {
     set_error("gcnk_spmm_csr_f32: plan needs %lld B of workspace, got %lld", (long long)need,
@@ -1355,49 +1487,24 @@ static int spmm_impl(const void* plan, const int32_t* hdr, const float* B, int64
               (long long)counter_bytes);
     return GCNK_EARG;
   }
-  const bool vec4 = (F % 4 == 0) && (ldb % 4 == 0) && (ldc % 4 == 0) && aligned16(B) && (!C || aligned16(C)) &&
-                    (!workspace || aligned16(workspace)) && (!bias || aligned16(bias));
   hipStream_t s = (hipStream_t)stream;
-  if (proj) {
-    // the projection needs whole rows in one group: row-kernel rows only, float4, one column tile
-    if (hdr[kHdrNtile] > 0 || !vec4 || F > lpr * 4 || pa.P > 32 || lpr < 16 || tops(hdr)) {
-      set_error("gcnk_spmm_proj_f32: fused projection unsupported here (tile chunks=%d vec4=%d F=%d P=%d lanes=%d)",
-                hdr[kHdrNtile], (int)vec4, F, pa.P, lpr);
-      return GCNK_EUNSUP;
-    }
-  }
   const int32_t* p = (const int32_t*)plan;
   const Layout L(hdr);
   const int64_t part_ld = ((int64_t)F + 3) & ~3LL;
-  if ((int64_t)kMaxSeg * part_ld * 4 >= ((int64_t)1 << 31)) {  // partial-slot byte offsets of one heavy row
-    set_error("gcnk_spmm: F = %d too wide for the partial-slot offsets", F);
-    return GCNK_EUNSUP;
-  }
   const int64_t rows_ws = ((int64_t)hdr[kHdrNslots] * part_ld * 4 + 255) & ~255LL;
   float* slabs = workspace ? reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + rows_ws) : nullptr;
   const int64_t slab_ld = tile_fpad(F);
 
   // ---- dense blocks: tile kernel (+ slab reduce)
-  const float* dval = L.has_diag ? reinterpret_cast<const float*>(p + L.dval) : nullptr;
-  if (L.ntile > 0) {
-    // column slices of <= kMaxNT n-tiles on grid.y, balanced (F = 200: 4 x 4 n-tiles),
-    // so two workgroups of a chunk share the staging/MFMA/store phases of a CU
-    const int32_t nt_total = (int32_t)(slab_ld / 16);
-    const int32_t nslices = (nt_total + kMaxNT - 1) / kMaxNT;
-    if (nslices > 65535) {
-      set_error("gcnk_spmm_csr_f32: F=%d needs %d tile column slices (> 65535)", F, nslices);
-      return GCNK_EUNSUP;
+  if (rt.tile || rt.tile_reduce) {
+    if (rt.tile) {
+      const float* dval = L.has_diag ? reinterpret_cast<const float*>(p + L.dval) : nullptr;
+      TileArgs ta{reinterpret_cast<const int4*>(p + L.tdesc), p + L.tcols, reinterpret_cast<const float*>(p + L.tfrag),
+                  p + L.trows, dval, F, B, ldb, C, ldc, e, slabs, slab_ld, rt.item0};
+      const int rc = launch_tile(rt, ta, s);
+      if (rc) return rc;
     }
-    const int4* td = reinterpret_cast<const int4*>(p + L.tdesc);
-    // part 1: the single-chunk items [0, nsingle); part 2: the rest; 0: all
-    const int32_t nsingle = hdr[kHdrNsingle];
-    const int nt_need = (nt_total + nslices - 1) / nslices;
-    const int32_t i0 = part == 2 ? nsingle : 0, i1 = part == 1 ? nsingle : (int32_t)L.ntile;
-    TileArgs ta{td, p + L.tcols, reinterpret_cast<const float*>(p + L.tfrag), p + L.trows, dval, F, B,
-                ldb, C, ldc, e, slabs, slab_ld, i0};
-    const int rc = launch_tile(vec4, nt_need, (unsigned)(i1 - i0), ta, s);
-    if (rc) return rc;
-    if (L.nred > 0 && part != 1) {
+    if (rt.tile_reduce) {
       // a carried side reduce takes extra x columns of the grid (kRB x column tiles workgroups each)
       const int64_t per_x = (int64_t)kRB * ((F + 63) / 64);
       const int64_t side_x = side ? (side_reduce_blocks(*side) + per_x - 1) / per_x : 0;
@@ -1411,18 +1518,17 @@ static int spmm_impl(const void* plan, const int32_t* hdr, const float* B, int64
     }
   }
   // ---- remaining rows: row kernel (heavy rows finished in-launch)
-  if (L.nunits > 0 && part != 1) {
+  if (rt.rows) {
     RowPlan rp{reinterpret_cast<const int2*>(p + L.items), reinterpret_cast<const int4*>(p + L.units),
                reinterpret_cast<const int4*>(p + L.heavy), counters, (int32_t)L.nunits, (int32_t)L.nhunits,
                L.segp > 0 ? reinterpret_cast<const int2*>(p + L.hitems) : nullptr, (int32_t)L.segp};
     RowLaunch a{rp, K, B, ldb, F, C, ldc, e, workspace, part_ld, pa, s};
-    if (proj) return pa.P <= 8 ? dispatch_rows_proj<8>(lpr, a) : dispatch_rows_proj<32>(lpr, a);
-    const int rc = vec4 ? dispatch_rows<4>(lpr, a) : dispatch_rows<1>(lpr, a);
-    if (rc || !L.tops) return rc;
+    if (rt.np) return rt.np == 8 ? dispatch_rows_proj<8>(a, rt) : dispatch_rows_proj<32>(a, rt);
+    const int rc = rt.vec == 4 ? dispatch_rows<4>(a, rt) : dispatch_rows<1>(a, rt);
+    if (rc || !rt.top) return rc;
     // rows of more than kMaxSeg segments: their groups' sums, after the row kernel
-    const int vec = vec4 ? 4 : 1;
-    const dim3 grid((unsigned)L.nheavy, (unsigned)((F + 256 * vec - 1) / (256 * vec)));
-    hipLaunchKernelGGL(vec4 ? spmm_heavy_top_kernel<4> : spmm_heavy_top_kernel<1>, grid, dim3(256), 0, s,
+    const dim3 grid((unsigned)L.nheavy, (unsigned)((F + 256 * rt.vec - 1) / (256 * rt.vec)));
+    hipLaunchKernelGGL(rt.vec == 4 ? spmm_heavy_top_kernel<4> : spmm_heavy_top_kernel<1>, grid, dim3(256), 0, s,
                        reinterpret_cast<const int4*>(p + L.heavy), (int32_t)L.nheavy, workspace, part_ld, F, C, ldc, e);
     return launch_check("spmm_heavy_top_kernel");
   }
@@ -1473,4 +1579,21 @@ extern "C" int gcnk_spmm_proj_f32(const void* plan, const int32_t* hdr, const fl
   const ProjArgs pa{W, ldw, P, C2, ldc2, C != nullptr};
   return spmm_impl(plan, hdr, B, ldb, F, C, ldc, bias, epilogue, drop_mask, ldm, drop_scale, keep_prob, seed, offset,
                    rng_base, workspace, workspace_bytes, counters, counter_bytes, lanes_hint, pa, stream);
+}
+
+extern "C" int gcnk_spmm_route(const int32_t* hdr, int32_t F, int64_t ldb, int64_t ldc, int32_t aligned16_mask,
+                               int32_t lanes_hint, int32_t P, int32_t part, int32_t* out16) {
+  if (!out16) {
+    set_error("gcnk_spmm_route: null out16");
+    return GCNK_EARG;
+  }
+  std::fill(out16, out16 + 16, 0);
+  SpmmRoute rt;
+  const int rc = spmm_route(hdr, F, ldb, ldc, (aligned16_mask & GCNK_SPMM_ALIGNED_ALL) == GCNK_SPMM_ALIGNED_ALL,
+                            lanes_hint, P, part, rt);
+  if (rc) return rc;
+  const int32_t out[16] = {rt.rows, rt.lpr, rt.vec, rt.np, rt.windows, rt.o32_first, rt.o32_last, rt.top,
+                           rt.tile, rt.tile_v4, rt.tile_nt, rt.tile_diag, rt.tile_slices, rt.tile_reduce, 0, 0};
+  std::copy(out, out + 16, out16);
+  return GCNK_OK;
 }

@@ -55,7 +55,7 @@ extern "C" {
 
 /* ABI note: 13 also covers gcnk_factor_diag_f32, gcnk_hubfactor_gc2_f32, the
  * gc2_* fields at the end of gcnk_gcn_fwd and the route reports
- * gcnk_gcn_bwd2_route / gcnk_hubfactor_gc1_route and held-graph scoring,
+ * gcnk_gcn_bwd2_route / gcnk_hubfactor_gc1_route / gcnk_spmm_route and held-graph scoring,
  * gcnk_score_docs_f32 / gcnk_score_docs_route (additions only: no existing
  * symbol, field offset or meaning changed, so the number stayed). */
 #define GCNK_ABI_VERSION 13
@@ -206,6 +206,29 @@ int gcnk_spmm_proj_f32(const void* plan, const int32_t* plan_header,
                        float* workspace, int64_t workspace_bytes,
                        int32_t* counters, int64_t counter_bytes,
                        int32_t lanes_hint, void* stream);
+
+/* Test aid (ABI 13): what gcnk_spmm_csr_f32 / _part / gcnk_spmm_proj_f32 launch
+ * for a plan header and these arguments, decided by the one host function the
+ * launch itself switches on (host only: nothing is launched, no device access,
+ * no stream).  aligned16: bit mask of the base pointers that are 16-B aligned
+ * (a null pointer counts as aligned); P = 0: no projection; part as in
+ * gcnk_spmm_csr_f32_part.  Returns what the launch returns for the same
+ * arguments where that depends on them alone (GCNK_EUNSUP for a refused
+ * projection, GCNK_EARG for a plan built for another group count, ...).
+ * out16 (all 0 where nothing is launched):
+ *   0 the row kernel launches  1 LPR  2 VEC (4 / 1)  3 NP (0, or 8 / 32 with a
+ *   projection)  4 column windows (launches of <= 64 column tiles)
+ *   5, 6 O32 of the first / last window (32-bit gather byte offsets)
+ *   7 spmm_heavy_top_kernel<VEC> follows
+ *   8 the tile kernel launches  9 VEC4  10 NT  11 DIAG  12 column slices
+ *   13 spmm_tile_reduce_kernel follows  14, 15 reserved (0) */
+#define GCNK_SPMM_ALIGNED_B 1
+#define GCNK_SPMM_ALIGNED_C 2
+#define GCNK_SPMM_ALIGNED_BIAS 4
+#define GCNK_SPMM_ALIGNED_WORKSPACE 8
+#define GCNK_SPMM_ALIGNED_ALL 15
+int gcnk_spmm_route(const int32_t* plan_header, int32_t F, int64_t ldb, int64_t ldc, int32_t aligned16,
+                    int32_t lanes_hint, int32_t P, int32_t part, int32_t* out16);
 
 /* ---------------------------------------------------------------------------
  * fp32 GEMM on MFMA (v_mfma_f32_16x16x4_f32; exact fp32 FMA chains):
