@@ -256,6 +256,17 @@ SIGNATURES = {
     "gcnk_bernoulli_mt19937_wait": (ctypes.c_int, [_vp]),
     "gcnk_sym_normalize_workspace_bytes": (_i64, [_i32, _i64]),
     "gcnk_sym_normalize": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "gcnk_topic_graph_chunk": (_i32, []),
+    "gcnk_topic_graph_max_topics": (_i32, []),
+    "gcnk_topic_graph_nnz_bound": (_i64, [_i32, _i32, _i32]),       # D, K, has_sim
+    "gcnk_topic_graph_workspace_bytes": (_i64, [_i32, _i32]),       # D, K
+    "gcnk_topic_graph_build": (ctypes.c_int, [
+        _vp, _i32, _i64, _vp, _i32, _i64,   # theta, theta_f32, ldt, sim (nullable), sim_f32, lds
+        _i32, _i32, _f64, _f64,             # D, K, doc_topic_threshold, topic_topic_threshold
+        _vp, _vp, _vp, _i64, _vp,           # rowptr, colind, val, capacity, edges (nullable, int32[2])
+        _vp, _i64, _vp]),                   # workspace, workspace_bytes, stream
+    # emb, emb_f32, lde, K, dim, sim (float64), lds, stream
+    "gcnk_topic_cosine_f64": (ctypes.c_int, [_vp, _i32, _i64, _i32, _i32, _vp, _i64, _vp]),
     "gcnk_csr_transpose_workspace_bytes": (_i64, [_i32, _i32, _i64]),
     "gcnk_coo_to_csr_workspace_bytes": (_i64, [_i64, _i32, _i32]),
     "gcnk_coo_to_csr": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
@@ -266,7 +277,9 @@ SIGNATURES = {
 # variants of an older tree
 NEWER_THAN_SOME_VARIANTS = ("gcnk_hubfactor_gc2_f32", "gcnk_factor_diag_f32", "gcnk_gcn_bwd2_route",
                             "gcnk_hubfactor_gc1_route", "gcnk_score_docs_f32", "gcnk_score_docs_route",
-                            "gcnk_spmm_route")
+                            "gcnk_spmm_route", "gcnk_topic_graph_chunk", "gcnk_topic_graph_max_topics",
+                            "gcnk_topic_graph_nnz_bound", "gcnk_topic_graph_workspace_bytes",
+                            "gcnk_topic_graph_build", "gcnk_topic_cosine_f64")
 
 _lock = threading.Lock()
 _lib = None

@@ -21,6 +21,8 @@
  *   utils.py:185-213 preprocess_adj / normalize_adj          -> gcnk_sym_normalize (device, bit-exact)
  *   utils.py:25-109  accuracy / macro_f1 counts              -> gcnk_class_stats (one launch, no per-class syncs)
  *   trainer.py:98-148 edge list -> symmetric adjacency        -> gcnk_edgelist_size / _csr (host, no networkx)
+ *   build_graph.py:99-133 theta, topic similarities -> graph   -> gcnk_topic_graph_build (device, straight to A-hat)
+ *   build_graph.py:118 cosine_similarity(topic_embeddings)     -> gcnk_topic_cosine_f64
  *   layer.py:185 th.dropout keep-mask draw (CPU generator)    -> gcnk_bernoulli_mt19937 (host, same stream)
  *   trainer.py:307, 358-361, 383-384 CrossEntropyLoss on logits[idx] -> gcnk_ce_forward_f32 / gcnk_ce_backward_f32
  *   trainer.py:308, 359, 362 th.optim.Adam step (and zero_grad)   -> gcnk_adam_f32 (one launch per 8 tensors)
@@ -56,7 +58,8 @@ extern "C" {
 /* ABI note: 13 also covers gcnk_factor_diag_f32, gcnk_hubfactor_gc2_f32, the
  * gc2_* fields at the end of gcnk_gcn_fwd and the route reports
  * gcnk_gcn_bwd2_route / gcnk_hubfactor_gc1_route / gcnk_spmm_route and held-graph scoring,
- * gcnk_score_docs_f32 / gcnk_score_docs_route (additions only: no existing
+ * gcnk_score_docs_f32 / gcnk_score_docs_route, and the graph built on the
+ * device, gcnk_topic_graph_* / gcnk_topic_cosine_f64 (additions only: no existing
  * symbol, field offset or meaning changed, so the number stayed). */
 #define GCNK_ABI_VERSION 13
 
@@ -960,6 +963,53 @@ int gcnk_keep_best_f32(const gcnk_keep_tensor* t /* host */, int32_t ntensors, c
  * ------------------------------------------------------------------------- */
 int gcnk_edgelist_size(const char* path, int64_t* n_nodes, int64_t* nnz);
 int gcnk_edgelist_csr(const char* path, int64_t n_nodes, int64_t nnz, int32_t* rowptr, int32_t* colind, float* val);
+
+/* ---------------------------------------------------------------------------
+ * The doc-topic graph built on the device (csrc/topic_graph.hip; additions
+ * within ABI 13): the topic model's output -> the CSR of A-hat, without the
+ * nx.Graph, the text edge list and scipy of build_graph.py:99-133 and
+ * trainer.py:98-151.  N = D + K nodes: documents 0 .. D-1, topics D .. N-1.
+ *   theta [D x K], sim [K x K] (nullable: no topic-topic edges): row-major
+ *     fp64 (*_f32 = 0) or fp32 (*_f32 = 1, widened exactly), leading
+ *     dimensions ldt / lds in elements.
+ *   edge (d, D+k)    iff theta[d,k] >= doc_topic_threshold, in float64
+ *                    (build_graph.py:106), weight float32(theta[d,k]);
+ *   edge (D+i, D+j)  i < j, iff sim[i,j] > topic_topic_threshold (strict,
+ *                    build_graph.py:124), weight float32(sim[i,j]); the lower
+ *                    triangle and the diagonal of sim are never read;
+ *   A_hat = D^-1/2 (A + I) D^-1/2 with gcnk_sym_normalize's arithmetic: float64
+ *     row sums taken sequentially in ascending column order with the diagonal
+ *     at its sorted place, d = rowsum^-0.5 (inf -> 0), (d[r] a) d[c] rounded
+ *     to fp32 once -- bit for bit what the reference's path gives.
+ * Unlike the reference, a document or topic without a kept edge is still a
+ * node (its row is the diagonal alone, A_hat = 1.0), and NaN / negative theta
+ * is not looked for (a NaN compares false and is dropped).
+ * Output: rowptr int32[N + 1] (rowptr[N] = nnz, readable once the stream
+ * completes), colind / val of `capacity` >= gcnk_topic_graph_nnz_bound(D, K,
+ * sim != NULL) entries, columns ascending in every row; edges (nullable)
+ * int32[2] = doc-topic edges, topic-topic edges (undirected counts:
+ * nnz = N + 2 (edges[0] + edges[1])).  Nothing is allocated; six launches on
+ * `stream`.  GCNK_EARG: D < 1, K < 1, a threshold not > 0 (0 would keep
+ * explicit zeros), a null pointer, a leading dimension < K, a short capacity
+ * or workspace.  GCNK_EUNSUP: K > gcnk_topic_graph_max_topics() (128), or
+ * N + the nnz bound >= 2^31.  Every refusal comes before any HIP call.
+ * gcnk_topic_graph_chunk(): documents per workgroup (256) -- a topic column's
+ * entries are ranked per 64-document segment of such a chunk, in order.
+ * ------------------------------------------------------------------------- */
+int32_t gcnk_topic_graph_chunk(void);
+int32_t gcnk_topic_graph_max_topics(void);
+int64_t gcnk_topic_graph_nnz_bound(int32_t D, int32_t K, int32_t has_sim);
+int64_t gcnk_topic_graph_workspace_bytes(int32_t D, int32_t K);
+int gcnk_topic_graph_build(const void* theta, int32_t theta_f32, int64_t ldt, const void* sim, int32_t sim_f32,
+                           int64_t lds, int32_t D, int32_t K, double doc_topic_threshold,
+                           double topic_topic_threshold, int32_t* rowptr, int32_t* colind, float* val,
+                           int64_t capacity, int32_t* edges, void* workspace, int64_t workspace_bytes, void* stream);
+/* sim [K x K] fp64 = the cosine similarity of the rows of emb [K x dim] (fp64,
+ * or fp32 with emb_f32 = 1), build_graph.py:118: dot products and squared
+ * norms as float64 sums in ascending index order, dot / (|a| |b|); a zero row
+ * gives 0.  sim is written symmetric, diagonal included. */
+int gcnk_topic_cosine_f64(const void* emb, int32_t emb_f32, int64_t lde, int32_t K, int32_t dim, double* sim,
+                          int64_t lds, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Dropout keep-mask exactly as the reference's CPU th.dropout draws it
