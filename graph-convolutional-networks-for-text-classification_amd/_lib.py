@@ -267,6 +267,19 @@ SIGNATURES = {
         _vp, _i64, _vp]),                   # workspace, workspace_bytes, stream
     # emb, emb_f32, lde, K, dim, sim (float64), lds, stream
     "gcnk_topic_cosine_f64": (ctypes.c_int, [_vp, _i32, _i64, _i32, _i32, _vp, _i64, _vp]),
+    "gcnk_lda_max_topics": (_i32, []),
+    "gcnk_lda_tile_words": (_i32, []),
+    "gcnk_lda_docs_per_block": (_i32, []),
+    # components / exp_topic_word (float64 [K x V]), its row stride, K, V, table, ldt, stream
+    "gcnk_lda_exp_dirichlet_f64": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _i64, _vp]),
+    "gcnk_lda_table_from_exp_f64": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _i64, _vp]),
+    "gcnk_lda_estep_f64": (ctypes.c_int, [
+        _vp, _vp, _vp, _i32,                # indptr, indices, counts, counts_kind (0 f64, 1 i32, 2 i64)
+        _i32, _i32, _i32, _vp, _i64,        # B, V, K, table, ldt
+        _f64, _f64, _i32,                   # alpha, tol, max_iter
+        _vp, _i64, _vp, _vp,                # theta, ldth, gamma, iters (int32[B]); each nullable
+        _vp, _i64, _vp, _i64, _f64,         # x, ldx, a, lda (nullable together), threshold
+        _vp]),                              # stream
     "gcnk_csr_transpose_workspace_bytes": (_i64, [_i32, _i32, _i64]),
     "gcnk_coo_to_csr_workspace_bytes": (_i64, [_i64, _i32, _i32]),
     "gcnk_coo_to_csr": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
@@ -279,7 +292,9 @@ NEWER_THAN_SOME_VARIANTS = ("gcnk_hubfactor_gc2_f32", "gcnk_factor_diag_f32", "g
                             "gcnk_hubfactor_gc1_route", "gcnk_score_docs_f32", "gcnk_score_docs_route",
                             "gcnk_spmm_route", "gcnk_topic_graph_chunk", "gcnk_topic_graph_max_topics",
                             "gcnk_topic_graph_nnz_bound", "gcnk_topic_graph_workspace_bytes",
-                            "gcnk_topic_graph_build", "gcnk_topic_cosine_f64")
+                            "gcnk_topic_graph_build", "gcnk_topic_cosine_f64", "gcnk_lda_max_topics",
+                            "gcnk_lda_tile_words", "gcnk_lda_docs_per_block", "gcnk_lda_exp_dirichlet_f64",
+                            "gcnk_lda_table_from_exp_f64", "gcnk_lda_estep_f64")
 
 _lock = threading.Lock()
 _lib = None

@@ -55,6 +55,12 @@ template <int POLICY = kBufPlain>
 __device__ __forceinline__ f32x4 buf_load_f32x4(__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff = 0) {
   return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, POLICY));
 }
+// (two doubles: the 16-byte access of a float64 row)
+typedef double f64x2 __attribute__((ext_vector_type(2)));
+template <int POLICY = kBufPlain>
+__device__ __forceinline__ f64x2 buf_load_f64x2(__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff = 0) {
+  return __builtin_bit_cast(f64x2, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, POLICY));
+}
 template <int POLICY = kBufPlain>
 __device__ __forceinline__ void buf_store_f32(float v, __amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff = 0) {
   __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), r, (int)voff, (int)soff, POLICY);

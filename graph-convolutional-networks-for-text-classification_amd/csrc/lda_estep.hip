@@ -1,0 +1,428 @@
+// Documents' topic mixtures on the device: the LDA E-step of sklearn's LatentDirichletAllocation.transform,
+// which the reference calls in topic_model.py:133-164 (twice an experiment: build_graph.py, trainer.py:179).
+// Per document d with word ids `ids`, counts c and beta_kw = exp(E[log beta])[k, ids[w]]
+// (_lda.py _update_doc_distribution, then transform's row normalisation):
+//     gamma = 1;  etheta_k = exp(psi(1) - psi(K))
+//     at most max_doc_update_iter times:
+//         phi_w    = sum_k etheta_k beta_kw + 2^-52
+//         gamma'_k = etheta_k * sum_w (c_w / phi_w) beta_kw + alpha
+//         etheta_k = exp(psi(gamma'_k) - psi(sum_k gamma'_k))
+//         stop after this update if sum_k |gamma_k - gamma'_k| / K < tol;   gamma = gamma'
+//     theta = gamma / sum_k gamma
+// psi is Bernardo's AS 103 exactly as sklearn's _online_lda_fast.pyx states it ("optimized for speed, not
+// accuracy"): an accurate digamma does not reproduce sklearn's theta.  All float64, and nothing is contracted
+// to an FMA but the two dot products, which say fma().
+//
+// Schedule: ONE WAVE PER DOCUMENT, no communication between waves, no atomics, no workspace.  The model is a
+// transposed table [V x ldt], so a word's K values are one contiguous row.  A wave gathers the rows of up to
+// kTile words into LDS (16-byte buffer loads, sixteen in flight), then iterates on LDS alone:
+//     phase 1  lane = word   phi_w, an in-lane sum over k ascending (etheta broadcast from LDS)
+//     phase 2  lane = topic  sum_w, an in-lane sum over w in stored order (c_w / phi_w broadcast from LDS);
+//                            lanes hold topics lane and lane + 64
+//     then every lane adds gamma' and |gamma - gamma'| over k ascending from LDS, so the stop decision is the
+//     same in all of them.
+// A document of more than kTile words walks chunks of kTile words in stored order every iteration, staging
+// each again from the table (which stays in L2); the phase-2 sums run on through the chunks, so every sum's
+// order depends on the document's own word order and on K alone -- not on B, the document's place in the
+// batch, kTile or the launch geometry.
+// Bounded loops: psi shifts at most six times (NaN and x <= 1e-6 leave at once), the update loop runs at
+// most max_iter <= kMaxIter times (a NaN makes the stop test false and runs to the cap), a document's waves
+// stop independently.  A word id outside [0, V) is the caller's error and is not looked for; the table is
+// read through a buffer resource, so such an id reads another row or zeros, never outside the table.
+#include "gcnk_common.h"
+
+#pragma clang fp contract(off)
+
+namespace gcnk {
+namespace {
+
+constexpr int kTile = 64;          // words a wave holds in LDS: one per lane
+constexpr int kDocs = 2;           // documents (waves) per workgroup: 2 x 68 KB of LDS at K = 128
+constexpr int kMaxTopics = 128;    // two topics a lane
+constexpr int kStage = 16;         // table rows a wave has in flight while it stages (64 VGPRs; LDS, not registers, sets the occupancy)
+constexpr int kMaxIter = 10000;
+constexpr double kEuler = 0.577215664901532860606512090082402431;
+constexpr double kEps = 2.220446049250313080847263336181640625e-16;   // np.finfo(np.float64).eps
+
+static_assert(kTile == 64 && kMaxTopics == 2 * 64, "a lane per word, two topics per lane");
+
+// _online_lda_fast.pyx psi(), operation for operation
+__device__ __forceinline__ double psi(double x) {
+  if (x <= 1e-6) return -kEuler - 1.0 / x;
+  double result = 0.0;
+  for (int i = 0; i < 6 && x < 6.0; ++i) {   // x > 1e-6 is past 6 after six shifts
+    result -= 1.0 / x;
+    x += 1.0;
+  }
+  double r = 1.0 / x;
+  result += log(x) - 0.5 * r;
+  r = r * r;
+  result -= r * ((1.0 / 12.0) - r * ((1.0 / 120.0) - r * (1.0 / 252.0)));
+  return result;
+}
+
+// LDS written by some lanes of this wave is read by others: order the accesses, nothing else
+__device__ __forceinline__ void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ __forceinline__ double readlane_f64(double v, int j) {
+  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), j),
+                          __builtin_amdgcn_readlane(__double2loint(v), j));
+}
+
+__host__ __device__ constexpr int tile_stride(int K) { return K | 1; }   // odd: a lane per row reads without bank conflicts
+__host__ __device__ constexpr int topics_even(int K) { return (K + 1) & ~1; }
+// a wave's LDS in doubles: tile | etheta | gamma' | |gamma - gamma'| | c / phi
+__host__ __device__ constexpr int wave_doubles(int K) { return kTile * tile_stride(K) + 3 * topics_even(K) + kTile; }
+
+struct EStep {
+  const int32_t* indptr;
+  const int32_t* indices;
+  const void* counts;
+  int32_t counts_kind;   // 0 float64, 1 int32, 2 int64
+  int32_t B, K;
+  const double* table;
+  uint32_t row_bytes, table_bytes;
+  double alpha, tol;
+  int32_t max_iter;
+  double* theta;
+  double* gamma;
+  int64_t ldth;
+  int32_t* iters;
+  float* x;
+  int64_t ldx;
+  float* a;
+  int64_t lda;
+  double threshold;
+};
+
+__device__ __forceinline__ double count_at(const EStep& p, int64_t i) {
+  if (p.counts_kind == 0) return static_cast<const double*>(p.counts)[i];
+  if (p.counts_kind == 1) return (double)static_cast<const int32_t*>(p.counts)[i];
+  return (double)static_cast<const int64_t*>(p.counts)[i];
+}
+
+// tile[w * Ks + k] = table[id_w, k] for the m words whose ids the lanes hold (lane w: word w)
+__device__ __forceinline__ void stage_words(__amdgpu_buffer_rsrc_t table, uint32_t row_bytes, int K, int Ks, int32_t id,
+                                            int m, int lane, double* tile) {
+  const bool c0 = 2 * lane < K, c1 = 2 * lane + 1 < K;
+  for (int w0 = 0; w0 < m; w0 += kStage) {
+    f64x2 v[kStage];
+#pragma unroll
+    for (int u = 0; u < kStage; ++u) {
+      const int w = w0 + u;
+      const uint32_t row = (uint32_t)__builtin_amdgcn_readlane(id, w & 63);
+      v[u] = buf_load_f64x2(table, w < m && c0 ? row * row_bytes + 16u * (uint32_t)lane : kBufOob);
+    }
+#pragma unroll
+    for (int u = 0; u < kStage; ++u) {
+      const int w = w0 + u;
+      if (w < m) {
+        if (c0) tile[w * Ks + 2 * lane] = v[u][0];
+        if (c1) tile[w * Ks + 2 * lane + 1] = v[u][1];
+      }
+    }
+  }
+}
+
+__global__ void __launch_bounds__(64 * kDocs)
+lda_estep_kernel(EStep p) {
+  extern __shared__ double lds[];
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int32_t d = (int32_t)blockIdx.x * kDocs + wv;
+  if (d >= p.B) return;
+  const int K = p.K, Ks = tile_stride(K), Kr = topics_even(K);
+  double* tile = lds + (size_t)wv * wave_doubles(K);
+  double* et = tile + kTile * Ks;
+  double* gm = et + Kr;
+  double* df = gm + Kr;
+  double* rr = df + Kr;
+  const int64_t b = p.indptr[d];
+  const int64_t e = p.indptr[d + 1];
+  const int32_t n = e > b ? (int32_t)(e - b) : 0;
+  const int nchunk = (n + kTile - 1) / kTile;
+  const __amdgpu_buffer_rsrc_t table = buffer_rsrc(p.table, p.table_bytes);
+
+  const int k0 = lane, k1 = lane + 64;
+  const bool on0 = k0 < K, on1 = k1 < K;
+  const int r0 = on0 ? k0 : K - 1, r1 = on1 ? k1 : K - 1;   // (a lane without a topic repeats the last one, unstored)
+  const bool two = K > 64;
+
+  int32_t id = 0;
+  double cnt = 0.0;
+  auto load_words = [&](int c) {
+    const int32_t w = c * kTile + lane;
+    id = w < n ? p.indices[b + w] : 0;
+    cnt = w < n ? count_at(p, b + w) : 0.0;
+  };
+
+  double g0 = 1.0, g1 = 1.0;
+  double e0 = exp(psi(1.0) - psi((double)K)), e1 = e0;
+  double total = (double)K;   // sum_k gamma_k, ascending
+  if (on0) et[k0] = e0;
+  if (on1) et[k1] = e1;
+  if (nchunk == 1) {
+    load_words(0);
+    stage_words(table, p.row_bytes, K, Ks, id, n, lane, tile);
+  }
+  wave_sync();
+
+  int32_t its = 0;
+  for (int it = 0; it < p.max_iter; ++it) {
+    double a0 = 0.0, a1 = 0.0;
+    for (int c = 0; c < nchunk; ++c) {
+      const int m = min(kTile, n - c * kTile);
+      if (nchunk > 1) {
+        load_words(c);
+        stage_words(table, p.row_bytes, K, Ks, id, m, lane, tile);
+        wave_sync();
+      }
+      // phase 1, lane = word (a lane past the chunk's end computes on stale LDS and is not read)
+      const double* mine = tile + lane * Ks;
+      double phi = 0.0;
+      for (int k = 0; k < K; ++k) phi = fma(et[k], mine[k], phi);
+      phi += kEps;
+      rr[lane] = cnt / phi;
+      wave_sync();
+      // phase 2, lane = topic
+      if (two) {
+        for (int w = 0; w < m; ++w) {
+          const double r = rr[w];
+          a0 = fma(r, tile[w * Ks + r0], a0);
+          a1 = fma(r, tile[w * Ks + r1], a1);
+        }
+      } else {
+        for (int w = 0; w < m; ++w) a0 = fma(rr[w], tile[w * Ks + r0], a0);
+      }
+      wave_sync();   // (the next chunk rewrites tile and rr)
+    }
+    const double n0 = e0 * a0 + p.alpha, n1 = e1 * a1 + p.alpha;
+    if (on0) {
+      gm[k0] = n0;
+      df[k0] = fabs(g0 - n0);
+    }
+    if (on1) {
+      gm[k1] = n1;
+      df[k1] = fabs(g1 - n1);
+    }
+    wave_sync();
+    double change = 0.0;
+    total = 0.0;
+    for (int k = 0; k < K; ++k) {
+      total += gm[k];
+      change += df[k];
+    }
+    const double psi_total = psi(total);
+    e0 = exp(psi(n0) - psi_total);
+    e1 = exp(psi(n1) - psi_total);
+    g0 = n0;
+    g1 = n1;
+    if (on0) et[k0] = e0;
+    if (on1) et[k1] = e1;
+    wave_sync();
+    ++its;
+    if (__builtin_amdgcn_readfirstlane((int)(change / (double)K < p.tol))) break;
+  }
+
+  const double t0 = g0 / total, t1 = g1 / total;
+  const int64_t row = (int64_t)d * p.ldth;
+  if (p.theta) {
+    if (on0) p.theta[row + k0] = t0;
+    if (on1) p.theta[row + k1] = t1;
+  }
+  if (p.gamma) {
+    if (on0) p.gamma[row + k0] = g0;
+    if (on1) p.gamma[row + k1] = g1;
+  }
+  if (p.iters && lane == 0) p.iters[d] = its;
+  if (!p.x) return;
+
+  // what the scorer reads, as inductive.from_theta makes it from this theta: x = theta / (sum theta + 1e-8)
+  // rounded to fp32, over its float64 norm, rounded to fp32; a = theta where theta >= threshold
+  if (on0) gm[k0] = t0;
+  if (on1) gm[k1] = t1;
+  wave_sync();
+  double s = 0.0;
+  for (int k = 0; k < K; ++k) s += gm[k];
+  const double den = s + 1e-8;
+  const double q0 = (double)(float)(t0 / den), q1 = (double)(float)(t1 / den);
+  if (on0) df[k0] = q0 * q0;
+  if (on1) df[k1] = q1 * q1;
+  wave_sync();
+  double ss = 0.0;
+  for (int k = 0; k < K; ++k) ss += df[k];
+  double norm = sqrt(ss);
+  if (norm == 0.0) norm = 1.0;
+  if (on0) {
+    p.x[(int64_t)d * p.ldx + k0] = (float)(q0 / norm);
+    p.a[(int64_t)d * p.lda + k0] = t0 >= p.threshold ? (float)t0 : 0.0f;
+  }
+  if (on1) {
+    p.x[(int64_t)d * p.ldx + k1] = (float)(q1 / norm);
+    p.a[(int64_t)d * p.lda + k1] = t1 >= p.threshold ? (float)t1 : 0.0f;
+  }
+}
+
+// A workgroup per topic: exp(psi(lambda_kw) - psi(sum_w lambda_kw)) into column k of the table.  Every wave
+// takes the row sum for itself, serially and ascending in w: 64 values a load, added one after the other
+// (a lane past the row's end holds +0, which leaves the sum as it is).
+__global__ void __launch_bounds__(256)
+lda_exp_dirichlet_kernel(const double* __restrict__ lam, int64_t ldc, int32_t V, double* __restrict__ table,
+                         int64_t ldt) {
+  const int k = blockIdx.x, lane = threadIdx.x & 63;
+  const double* row = lam + (int64_t)k * ldc;
+  double s = 0.0;
+  for (int32_t base = 0; base < V; base += 4 * 64) {
+    double v[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) v[u] = base + 64 * u + lane < V ? row[base + 64 * u + lane] : 0.0;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      if (base + 64 * u >= V) break;
+#pragma unroll
+      for (int j = 0; j < 64; ++j) s += readlane_f64(v[u], j);
+    }
+  }
+  const double psi_row = psi(s);
+  for (int32_t w = threadIdx.x; w < V; w += 256) table[(int64_t)w * ldt + k] = exp(psi(row[w]) - psi_row);
+}
+
+__global__ void __launch_bounds__(256)
+lda_transpose_kernel(const double* __restrict__ src, int64_t lde, int32_t K, int32_t V, double* __restrict__ table,
+                     int64_t ldt) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (int64_t)K * V) return;
+  const int32_t w = (int32_t)(i / K), k = (int32_t)(i - (int64_t)w * K);
+  table[(int64_t)w * ldt + k] = src[(int64_t)k * lde + w];
+}
+
+// K in range, the table's rows 16-byte accesses, every byte offset into it below kBufOob
+int check_table(const char* who, int32_t K, int32_t V, const void* table, int64_t ldt) {
+  if (K < 1 || V < 1) {
+    set_error("%s: needs K >= 1 and V >= 1 (K=%d V=%d)", who, K, V);
+    return GCNK_EARG;
+  }
+  if (K > kMaxTopics) {
+    set_error("%s: K=%d topics, the kernels take at most %d", who, K, kMaxTopics);
+    return GCNK_EUNSUP;
+  }
+  if (!table || !aligned16(table) || ldt < K || (ldt & 1)) {
+    set_error("%s: the table must be non-null, 16-byte aligned, with an even ldt >= K (ldt=%lld K=%d)", who,
+              (long long)ldt, K);
+    return GCNK_EARG;
+  }
+  if ((int64_t)V * ldt * 8 >= (int64_t)kBufOob) {
+    set_error("%s: a table of %lld bytes is past the 32-bit offsets of its buffer resource (V=%d ldt=%lld)", who,
+              (long long)((int64_t)V * ldt * 8), V, (long long)ldt);
+    return GCNK_EUNSUP;
+  }
+  return GCNK_OK;
+}
+
+}  // namespace
+}  // namespace gcnk
+
+using namespace gcnk;
+
+extern "C" int32_t gcnk_lda_max_topics(void) { return kMaxTopics; }
+
+extern "C" int32_t gcnk_lda_tile_words(void) { return kTile; }
+
+extern "C" int32_t gcnk_lda_docs_per_block(void) { return kDocs; }
+
+extern "C" int gcnk_lda_exp_dirichlet_f64(const double* components, int64_t ldc, int32_t K, int32_t V, double* table,
+                                          int64_t ldt, void* stream) {
+  const char* who = "gcnk_lda_exp_dirichlet_f64";
+  const int rc = check_table(who, K, V, table, ldt);
+  if (rc) return rc;
+  if (!components || ldc < V) {
+    set_error("%s: null components or ldc=%lld < V=%d", who, (long long)ldc, V);
+    return GCNK_EARG;
+  }
+  hipLaunchKernelGGL(lda_exp_dirichlet_kernel, dim3((unsigned)K), dim3(256), 0, (hipStream_t)stream, components, ldc, V,
+                     table, ldt);
+  return launch_check("lda_exp_dirichlet_kernel");
+}
+
+extern "C" int gcnk_lda_table_from_exp_f64(const double* exp_topic_word, int64_t lde, int32_t K, int32_t V,
+                                           double* table, int64_t ldt, void* stream) {
+  const char* who = "gcnk_lda_table_from_exp_f64";
+  const int rc = check_table(who, K, V, table, ldt);
+  if (rc) return rc;
+  if (!exp_topic_word || lde < V) {
+    set_error("%s: null exp_topic_word or lde=%lld < V=%d", who, (long long)lde, V);
+    return GCNK_EARG;
+  }
+  const int64_t nblk = ((int64_t)K * V + 255) / 256;
+  hipLaunchKernelGGL(lda_transpose_kernel, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, exp_topic_word, lde,
+                     K, V, table, ldt);
+  return launch_check("lda_transpose_kernel");
+}
+
+extern "C" int gcnk_lda_estep_f64(const int32_t* indptr, const int32_t* indices, const void* counts,
+                                  int32_t counts_kind, int32_t B, int32_t V, int32_t K, const double* table,
+                                  int64_t ldt, double alpha, double tol, int32_t max_iter, double* theta, int64_t ldth,
+                                  double* gamma, int32_t* iters, float* x, int64_t ldx, float* a, int64_t lda,
+                                  double threshold, void* stream) {
+  const char* who = "gcnk_lda_estep_f64";
+  const int rc = check_table(who, K, V, table, ldt);
+  if (rc) return rc;
+  if (B < 1 || !indptr || !indices || !counts) {
+    set_error("%s: needs B >= 1 and non-null indptr, indices and counts (B=%d)", who, B);
+    return GCNK_EARG;
+  }
+  if (counts_kind < 0 || counts_kind > 2) {
+    set_error("%s: counts_kind %d is not 0 (float64), 1 (int32) or 2 (int64)", who, counts_kind);
+    return GCNK_EARG;
+  }
+  if (max_iter < 0 || max_iter > kMaxIter) {
+    set_error("%s: max_iter=%d is outside [0, %d]", who, max_iter, kMaxIter);
+    return GCNK_EARG;
+  }
+  if ((x == nullptr) != (a == nullptr)) {
+    set_error("%s: x and a are given together or not at all", who);
+    return GCNK_EARG;
+  }
+  if (!theta && !gamma && !iters && !x) {
+    set_error("%s: no output requested (theta, gamma, iters, x and a are all null)", who);
+    return GCNK_EARG;
+  }
+  if (((theta || gamma) && ldth < K) || (x && (ldx < K || lda < K))) {
+    set_error("%s: an output's leading dimension is shorter than K=%d (ldth=%lld ldx=%lld lda=%lld)", who, K,
+              (long long)ldth, (long long)ldx, (long long)lda);
+    return GCNK_EARG;
+  }
+  EStep p;
+  p.indptr = indptr;
+  p.indices = indices;
+  p.counts = counts;
+  p.counts_kind = counts_kind;
+  p.B = B;
+  p.K = K;
+  p.table = table;
+  p.row_bytes = (uint32_t)(ldt * 8);
+  p.table_bytes = (uint32_t)((int64_t)V * ldt * 8);
+  p.alpha = alpha;
+  p.tol = tol;
+  p.max_iter = max_iter;
+  p.theta = theta;
+  p.gamma = gamma;
+  p.ldth = ldth;
+  p.iters = iters;
+  p.x = x;
+  p.ldx = ldx;
+  p.a = a;
+  p.lda = lda;
+  p.threshold = threshold;
+  static std::atomic<uint64_t> done{0};
+  const int lds_bytes = kDocs * wave_doubles(K) * (int)sizeof(double);
+  const hipError_t attr = dyn_lds_attr(done, reinterpret_cast<const void*>(&lda_estep_kernel), 160 * 1024);
+  if (attr != hipSuccess) return hip_check(attr, "lda_estep_kernel LDS attribute");
+  const unsigned nblk = (unsigned)(((int64_t)B + kDocs - 1) / kDocs);
+  hipLaunchKernelGGL(lda_estep_kernel, dim3(nblk), dim3(64 * kDocs), (size_t)lds_bytes, (hipStream_t)stream, p);
+  return launch_check("lda_estep_kernel");
+}

@@ -23,6 +23,7 @@
  *   trainer.py:98-148 edge list -> symmetric adjacency        -> gcnk_edgelist_size / _csr (host, no networkx)
  *   build_graph.py:99-133 theta, topic similarities -> graph   -> gcnk_topic_graph_build (device, straight to A-hat)
  *   build_graph.py:118 cosine_similarity(topic_embeddings)     -> gcnk_topic_cosine_f64
+ *   topic_model.py:133-164 LatentDirichletAllocation.transform -> gcnk_lda_estep_f64 (device, a wave per document)
  *   layer.py:185 th.dropout keep-mask draw (CPU generator)    -> gcnk_bernoulli_mt19937 (host, same stream)
  *   trainer.py:307, 358-361, 383-384 CrossEntropyLoss on logits[idx] -> gcnk_ce_forward_f32 / gcnk_ce_backward_f32
  *   trainer.py:308, 359, 362 th.optim.Adam step (and zero_grad)   -> gcnk_adam_f32 (one launch per 8 tensors)
@@ -59,7 +60,8 @@ extern "C" {
  * gc2_* fields at the end of gcnk_gcn_fwd and the route reports
  * gcnk_gcn_bwd2_route / gcnk_hubfactor_gc1_route / gcnk_spmm_route and held-graph scoring,
  * gcnk_score_docs_f32 / gcnk_score_docs_route, and the graph built on the
- * device, gcnk_topic_graph_* / gcnk_topic_cosine_f64 (additions only: no existing
+ * device, gcnk_topic_graph_* / gcnk_topic_cosine_f64, and the topic mixtures
+ * inferred on the device, gcnk_lda_* (additions only: no existing
  * symbol, field offset or meaning changed, so the number stayed). */
 #define GCNK_ABI_VERSION 13
 
@@ -1010,6 +1012,69 @@ int gcnk_topic_graph_build(const void* theta, int32_t theta_f32, int64_t ldt, co
  * gives 0.  sim is written symmetric, diagonal included. */
 int gcnk_topic_cosine_f64(const void* emb, int32_t emb_f32, int64_t lde, int32_t K, int32_t dim, double* sim,
                           int64_t lds, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Documents' topic mixtures on the device (csrc/lda_estep.hip; additions within
+ * ABI 13): the LDA E-step behind topic_model.py:133-164, sklearn's
+ * LatentDirichletAllocation.transform, restated in float64 with sklearn's own
+ * rules -- its AS 103 psi (_online_lda_fast.pyx, not an accurate digamma),
+ * gamma = 1 at the start, eps = 2^-52 added to phi, the mean-change stop rule
+ * taken after the prior is added.
+ *
+ * The model is held as a transposed table [V x ldt] float64, ldt even and >= K,
+ * 16-byte aligned, V * ldt * 8 < 2^31 - 2^20: table[w * ldt + k] =
+ * exp(E[log beta_kw]).  Columns K .. ldt-1 are never read into a sum and never
+ * written.
+ *   gcnk_lda_exp_dirichlet_f64   from components (lambda, [K x V], row stride
+ *       ldc): exp(psi(lambda_kw) - psi(sum_w lambda_kw)), the row sum serial and
+ *       ascending in w (_dirichlet_expectation_2d, then exp).
+ *   gcnk_lda_table_from_exp_f64  the transpose of a model's own
+ *       exp_dirichlet_component_ ([K x V], row stride lde), bit for bit.
+ *
+ * gcnk_lda_estep_f64: B documents as a CSR over the vocabulary -- indptr
+ * int32[B + 1], indices int32, counts float64 / int32 / int64 (counts_kind 0 /
+ * 1 / 2, widened exactly) -- one wave each, one launch:
+ *     gamma = 1;  etheta_k = exp(psi(1) - psi(K))
+ *     at most max_iter times:
+ *       phi_w    = sum_k etheta_k table[id_w, k] + 2^-52
+ *       gamma'_k = etheta_k * sum_w (c_w / phi_w) table[id_w, k] + alpha
+ *       etheta_k = exp(psi(gamma'_k) - psi(sum_k gamma'_k))
+ *       stop after this update if sum_k |gamma_k - gamma'_k| / K < tol
+ *     theta = gamma / sum_k gamma
+ * Sums over k ascend, sums over a document's words run in stored order (the two
+ * dot products by fma, nothing else contracted): a document's row depends on its
+ * own words and K alone, not on B, its place in the batch or the launch.  No
+ * atomics, no workspace, no synchronisation.  Outputs, each nullable:
+ *   theta, gamma  float64 [B x ldth]  (gamma: sklearn's _unnormalized_transform)
+ *   iters         int32 [B], the updates run (0 .. max_iter)
+ *   x, a          fp32 [B x ldx], [B x lda], given together: what
+ *       gcnk_score_docs_f32 reads, made from this launch's theta as the
+ *       reference makes them (trainer.py:205-221, build_graph.py:105-110):
+ *       x = theta / (sum_k theta + 1e-8) rounded to fp32, over its float64 L2
+ *       norm (a zero row stays zero), rounded to fp32; a = fp32(theta) where
+ *       theta >= threshold in float64, else 0.  The two sums ascend in k.
+ * A word id outside [0, V) is the caller's error and is not checked on the
+ * device (the table is read through a bounds-checked buffer resource: such an id
+ * reads another row or zeros).  indptr must ascend within the arrays given.
+ * GCNK_EARG: B < 1, K < 1, V < 1, a null input, a bad table (see above),
+ * counts_kind outside 0..2, max_iter outside [0, 10000], x without a or a
+ * without x, no output at all, a leading dimension < K.  GCNK_EUNSUP: K >
+ * gcnk_lda_max_topics() (128), a table past 32-bit byte offsets.  Every refusal
+ * comes before any HIP call.  gcnk_lda_tile_words(): the words a wave holds in
+ * LDS (64; a longer document walks chunks of that many, re-read every update);
+ * gcnk_lda_docs_per_block(): waves per workgroup (2).
+ * ------------------------------------------------------------------------- */
+int32_t gcnk_lda_max_topics(void);
+int32_t gcnk_lda_tile_words(void);
+int32_t gcnk_lda_docs_per_block(void);
+int gcnk_lda_exp_dirichlet_f64(const double* components, int64_t ldc, int32_t K, int32_t V, double* table, int64_t ldt,
+                               void* stream);
+int gcnk_lda_table_from_exp_f64(const double* exp_topic_word, int64_t lde, int32_t K, int32_t V, double* table,
+                                int64_t ldt, void* stream);
+int gcnk_lda_estep_f64(const int32_t* indptr, const int32_t* indices, const void* counts, int32_t counts_kind,
+                       int32_t B, int32_t V, int32_t K, const double* table, int64_t ldt, double alpha, double tol,
+                       int32_t max_iter, double* theta, int64_t ldth, double* gamma, int32_t* iters, float* x,
+                       int64_t ldx, float* a, int64_t lda, double threshold, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Dropout keep-mask exactly as the reference's CPU th.dropout draws it
