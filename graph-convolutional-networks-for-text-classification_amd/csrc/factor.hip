@@ -18,8 +18,8 @@
 // hub rows (the (A X) W association; fp32 rounding differs from A (X W) by
 // ~1e-6 relative), and the document rows never read or write their S1 rows.
 //
-// One workgroup = 32 rows (512 threads, 8 waves: 2 row strips x 4 quarters of the
-// F columns):
+// One workgroup = one block of hub_block.h (32 rows, 8 waves: 2 row strips x 4
+// quarters of the F columns):
 //   0. every operand of the block in one round of loads: W1[Kc] and S_T into LDS,
 //      the block's U rows into LDS (16-B DMA; or its U fragments into registers),
 //      its A_H record into LDS, the wave's W2 fragments into registers;
@@ -29,44 +29,29 @@
 //   3. S2 = H1 W2 on MFMA from the same LDS tile (K split over the two halves,
 //      summed in a fixed order).
 // No atomics, no hand-off between workgroups: bitwise reproducible.
-#include "gcnk_common.h"
+#include "hub_block.h"
 
-
-#include <algorithm>
 #include <type_traits>
 
 namespace gcnk {
 namespace {
 
-constexpr int kRB = 32;         // rows per workgroup
-constexpr int kThreads = 512;   // 8 waves: 2 row strips x 4 column quarters
 constexpr int kMaxKsteps = 32;  // Kc <= 128
-constexpr int kProjMax = 32;    // projection width: P <= 32 (NP = 1 or 2 MFMA n-tiles)
-// zero floats after the staged W1[Kc]: the last real n-tile reads up to column
-// 16 ceil(F / 16) - 1 of the last k-row; the pad (64 NTQ - F, at least 64) is
-// sized for every tile up to column 64 NTQ - 1, which the kernel once computed
-__host__ __device__ constexpr int bpad(int f, int ntq) { return 64 * ntq - f > 64 ? 64 * ntq - f : 64; }
-// block record (factor.py): 33 row offsets, 3 pad | 32 row ids (-1 past M) |
-// A_H items int2 {hub, value}.  Block b holds rows perm[32 b .. 32 b + 31]: the
-// host spreads the hub rows (long item lists) over the blocks, U's rows are in
-// that order, outputs go to the row ids.
-constexpr int kRecRow = 36, kRecHead = 68;
 // compile-time shapes (every MFMA unconditional, operands in fixed registers):
 // KS k-steps of U W1[Kc] (Kc <= 4 KS; U columns past Kc read as zero, W1 rows
-// past Kc staged as zero) and up to NTQ 16-column tiles per wave (F <= 64 NTQ;
-// only tiles holding a column of F are computed; the last one's columns past F
-// come from zeroed or W1 LDS words and are never used)
+// past Kc staged as zero) beside the block's NTQ and NP (only tiles holding a
+// column of F are computed; the last one's columns past F come from zeroed or
+// W1 LDS words and are never used)
 // (18: the 20ng-shaped X's 70 topic-weight columns, whose W1 rows at 25 k-steps
 // would take the block's LDS past 160 KiB)
 __host__ __device__ constexpr int pick_ks(int kc) { return kc <= 52 ? 13 : kc <= 72 ? 18 : kc <= 100 ? 25 : 32; }
-__host__ __device__ constexpr int pick_ntq(int f) { return f <= 128 ? 2 : f <= 192 ? 3 : 4; }
 
 struct FactorArgs {
   int32_t M, F, Kc, nhub, P;
   const float* U; int64_t ldu;          // [M x >= Kc], rows in block order
   const float* W; int64_t ldw; int32_t k0;  // W1 rows k0 .. k0 + Kc - 1 (ldw == F: staged flat)
   const float* S; int64_t lds;          // S_T [nhub x F]
-  const int32_t* rec; int32_t rec_words;  // per 32-row block: off[33] | pad | row ids | items int2 {hub, val}
+  const int32_t* rec; int32_t rec_words;  // the blocks' records
   const float* W2; int64_t ldw2;        // [F x P]
   int32_t u_lds;                        // 1: the block's U rows staged in LDS by 16-B DMA (ldu % 4 == 0, aligned)
   float* H; int64_t ldh;                // nullable
@@ -74,13 +59,8 @@ struct FactorArgs {
   Epi epi;
 };
 
-template <int KS>
-__host__ __device__ constexpr int region1_floats(int F, int ntq) {
-  return (4 * KS * F + bpad(F, ntq)) > kRB * (64 * ntq + 4) ? (4 * KS * F + bpad(F, ntq)) : kRB * (64 * ntq + 4);
-}
-
 template <int KS, int NTQ, int NP>
-__global__ void __launch_bounds__(kThreads)
+__global__ void __launch_bounds__(kHubThreads)
 hubfactor_gc1_kernel(FactorArgs a) {
   resolve_rng(a.epi);
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -88,80 +68,71 @@ hubfactor_gc1_kernel(FactorArgs a) {
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int strip = wv & 1, quarter = wv >> 1;
   const int F = a.F, Q = F / 4;
-  constexpr int Fp = 64 * NTQ, Fz = Fp + 4;  // s_Z row stride: 16-B rows, conflict-free MFMA-layout accesses
+  constexpr int Fp = 64 * NTQ, Fz = hub_z_stride(NTQ);
   constexpr int Kr = 4 * KS;
   const int blk = (int)blockIdx.x;
-  const int64_t m0 = (int64_t)blk * kRB;  // position in the block order (U's rows)
-  // LDS: region1 = s_B [Kr][F] + bpad zeros (phase 1), then s_Z [kRB][Fz]
+  const int64_t m0 = (int64_t)blk * kHubRows;  // position in the block order (U's rows)
+  // LDS: region1 = s_B [Kr][F] + hub_bpad zeros (phase 1), then s_Z [kHubRows][Fz]
   //      | s_S [nhub][F] | s_bias [F] | s_rec | s_red [NP][3][2][64][4]
   // Every global operand is staged here in the one round of loads that opens the
   // kernel: a global load behind an LDS-read index costs a full memory round trip
   // under load (~1-2 us each, measured), so nothing after the first wait touches
   // global memory except the stores.
-  const int r1 = region1_floats<KS>(F, NTQ);
+  const int r1 = hub_region1_floats(Kr, F, NTQ);
   float* s_B = smem;
   float* s_Z = smem;
   float* s_S = smem + r1;
   float* s_bias = s_S + a.nhub * F;
   int32_t* s_rec = reinterpret_cast<int32_t*>(s_bias + F);
   float* s_red = reinterpret_cast<float*>(s_rec + a.rec_words);
-  // u_lds: U's 32 rows [kRB][KPU] after s_red; row stride = 4 (mod 64), so lane
+  // u_lds: U's 32 rows [kHubRows][KPU] after s_red; row stride = 4 (mod 64), so lane
   // (row c, quadrant q) reading k = 4 s + q hits bank 4 c + q (conflict-free)
   constexpr int KPU = 64 * ((4 * KS - 4 + 63) / 64) + 4;
-  float* s_U = s_red + NP * 3 * 2 * 64 * 4;
+  float* s_U = s_red + hub_red_floats(NP);
 
   // ---- 0. loads, all issued before the first wait: zeros first (no LDS-DMA in
   //      flight yet), then LDS-DMA of W1[Kc] (flat), U's rows (u_lds; else the
   //      U fragments straight into registers below), the block's record, S_T
   //      and b1; phase 3's W2 fragments straight into registers
-  for (int e = a.Kc * F + tid; e < Kr * F + bpad(F, NTQ); e += kThreads) s_B[e] = 0.f;
+  for (int e = a.Kc * F + tid; e < Kr * F + hub_bpad(F, NTQ); e += kHubThreads) s_B[e] = 0.f;
   if (!a.epi.bias)
-    for (int e = tid; e < F; e += kThreads) s_bias[e] = 0.f;
+    for (int e = tid; e < F; e += kHubThreads) s_bias[e] = 0.f;
   // (splitting these loads by wave role -- waves 0-3 phase 1's operands, the
   // first barrier waiting only for those -- measured 9.28 against 9.35 us:
   // profiles/r05_factor_ulds_ab.log; not kept)
   {
     const int n4 = a.Kc * Q;  // float4 pieces of W1[k0 .. k0 + Kc) (rows of F floats, ldw == F)
     const float* wsrc = a.W + (int64_t)a.k0 * a.ldw;
-    for (int e0 = wv * 64; e0 < n4; e0 += kThreads)
+    for (int e0 = wv * 64; e0 < n4; e0 += kHubThreads)
       if (e0 + lane < n4) lds_dma16(wsrc + 4 * (e0 + lane), s_B + 4 * e0);
     // U's rows by 16-B DMA (the per-lane fragment loads -- 16 rows x 16 B per
     // instruction -- cost ~1.1 us of the block: profiles/r05_factor_ulds_ab.log);
     // one instruction per row, pieces covering Kc (inside the row: ldu % 4 == 0)
     if (a.u_lds)
-      for (int r = wv; r < kRB; r += kThreads / 64)
+      for (int r = wv; r < kHubRows; r += kHubThreads / 64)
         if (m0 + r < a.M && 4 * lane < a.Kc) lds_dma16(a.U + (m0 + r) * a.ldu + 4 * lane, s_U + r * KPU);
     const int32_t* rec = a.rec + (int64_t)blk * a.rec_words;
-    for (int e0 = wv * 64; e0 < a.rec_words / 4; e0 += kThreads)
+    for (int e0 = wv * 64; e0 < a.rec_words / 4; e0 += kHubThreads)
       if (e0 + lane < a.rec_words / 4) lds_dma16(rec + 4 * (e0 + lane), s_rec + 4 * e0);
     const int s4 = a.nhub * Q;  // S_T [nhub x F] flat (lds == F)
-    for (int e0 = wv * 64; e0 < s4; e0 += kThreads)
+    for (int e0 = wv * 64; e0 < s4; e0 += kHubThreads)
       if (e0 + lane < s4) lds_dma16(a.S + 4 * (e0 + lane), s_S + 4 * e0);
     if (a.epi.bias)
-      for (int e0 = wv * 64; e0 < Q; e0 += kThreads)
+      for (int e0 = wv * 64; e0 < Q; e0 += kHubThreads)
         if (e0 + lane < Q) lds_dma16(a.epi.bias + 4 * (e0 + lane), s_bias + 4 * e0);
   }
   // Phase 3's B fragments, W2[k][16 t + n] for this wave's quarter of the K = F
-  // sum (ldw2 == P), through a buffer resource over exactly W2's F P floats: a
-  // row k >= F lies past it and reads 0 with no compare.  A column 16 t + n >= P
-  // would land inside the next row, so its lane starts from an offset past the
-  // resource, chosen once per n-tile.  W2 depends on nothing the kernel
-  // computes: read from LDS after the phase-2 barrier, each fragment sat behind
-  // its own compare, exec mask and 32-bit multiply (~150 instructions a wave on
-  // the block's serial path).
+  // sum (ldw2 == P; rows past F and columns past P read 0).  W2 depends on
+  // nothing the kernel computes: read from LDS after the phase-2 barrier, each
+  // fragment sat behind its own compare, exec mask and 32-bit multiply (~150
+  // instructions a wave on the block's serial path).
   constexpr int kq = Fp / 16;  // k-steps per quarter
   float bw[NP][kq];
   {
     const __amdgpu_buffer_rsrc_t rw = buffer_rsrc(a.W2, F * a.P * 4);
-    const int kstep = 16 * a.P;   // bytes between the lane's consecutive k (4 rows of P floats)
 #pragma unroll
-    for (int t = 0; t < NP; ++t) {
-      const int col = 16 * t + (lane & 15);
-      int off = col < a.P ? ((4 * quarter * kq + (lane >> 4)) * a.P + col) * 4 : (int)kBufOob;
-#pragma unroll
-      for (int j = 0; j < kq; ++j, off += kstep)
-        bw[t][j] = buf_load_f32(rw, off);
-    }
+    for (int t = 0; t < NP; ++t)
+      hub_proj_frags(bw[t], rw, 4 * quarter * kq + (lane >> 4), a.P, 16 * t + (lane & 15), a.P);
   }
   float af[KS];
   const int64_t urow = m0 + 16 * strip + (lane & 15);
@@ -191,20 +162,13 @@ hubfactor_gc1_kernel(FactorArgs a) {
   for (int i = 0; i < NTQ; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
   // The phase is bound by MFMA issue (the fragment reads hide behind the other
   // wave of the SIMD: reading them ahead of the MFMAs changed nothing or lost,
-  // DESIGN section 5), so n-tiles that hold no column of F are not computed.
-  // The T = ceil(F / 16) real tiles are dealt round-robin over the column
-  // quarters, in opposite directions in the two strips (tile g of strip 0 to
-  // quarter g % 4, of strip 1 to quarter 3 - g % 4): whether the eight waves sit
-  // on the four SIMDs by wave id modulo 4 or in pairs, no SIMD carries more
-  // than ceil(T / 2) tiles a k-step (R8: 7, 7, 6, 6 in place of 8 each).  A slot
-  // without a real tile keeps its zero accumulator and stores it: those columns
-  // of s_Z feed phase 3 against zero W2 rows and must be finite.
-  const int qe = strip ? 3 - quarter : quarter;
-  const int c0 = qe * 16 + (lane & 15);
-  constexpr int kTileStep = 64;   // columns between a wave's consecutive tiles
+  // DESIGN section 5), so only the real tiles of F are computed, as hub_deal
+  // deals them.  A slot without a real tile stores its zero accumulator: those
+  // columns of s_Z feed phase 3 against zero W2 rows and must be finite.
+  const HubDeal deal = hub_deal(strip, quarter, lane, F, NTQ);
+  const int c0 = deal.c0;
   {
-    const int T = (F + 15) >> 4;
-    const int nt = __builtin_amdgcn_readfirstlane(min(max((T - qe + 3) >> 2, 0), NTQ));
+    const int nt = deal.nt;
     auto run = [&](auto ntc) __attribute__((always_inline)) {
       constexpr int NT = decltype(ntc)::value;
 #pragma unroll
@@ -212,7 +176,7 @@ hubfactor_gc1_kernel(FactorArgs a) {
         const float* br = s_B + (4 * s + (lane >> 4)) * F + c0;
         float bf[NT];
 #pragma unroll
-        for (int i = 0; i < NT; ++i) bf[i] = br[i * kTileStep];
+        for (int i = 0; i < NT; ++i) bf[i] = br[i * kHubTileStep];
 #pragma unroll
         for (int i = 0; i < NT; ++i) acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[s], bf[i], acc[i], 0, 0, 0);
       }
@@ -227,7 +191,7 @@ hubfactor_gc1_kernel(FactorArgs a) {
         const float* br = s_B + (4 * s + (lane >> 4)) * F + c0;
 #pragma unroll
         for (int i = 0; i < NTQ - 2; ++i)
-          if (i < nt) acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[s], br[i * kTileStep], acc[i], 0, 0, 0);
+          if (i < nt) acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[s], br[i * kHubTileStep], acc[i], 0, 0, 0);
       }
     }
   }
@@ -238,7 +202,7 @@ hubfactor_gc1_kernel(FactorArgs a) {
   for (int i = 0; i < NTQ; ++i)
 #pragma unroll
     for (int r = 0; r < 4; ++r)
-      s_Z[(16 * strip + (lane >> 4) * 4 + r) * Fz + c0 + i * kTileStep] = acc[i][r];
+      s_Z[(16 * strip + (lane >> 4) * 4 + r) * Fz + c0 + i * kHubTileStep] = acc[i][r];
   __syncthreads();
 
   // ---- 2. row-major epilogue, 16 threads per row, NTQ float4 columns each
@@ -248,11 +212,11 @@ hubfactor_gc1_kernel(FactorArgs a) {
   //      LDS reads issue together.
   {
     const int r = tid >> 4, c16 = tid & 15;
-    const int64_t row = s_rec[kRecRow + r];  // output row (-1 past M)
+    const int64_t row = s_rec[kHubRecRow + r];  // output row (-1 past M)
     float4 z[NTQ];
 #pragma unroll
     for (int u = 0; u < NTQ; ++u) z[u] = *reinterpret_cast<const float4*>(s_Z + r * Fz + 4 * (c16 + 16 * u));
-    const int2* it = reinterpret_cast<const int2*>(s_rec + kRecHead);
+    const HubItem* it = reinterpret_cast<const HubItem*>(s_rec + kHubRecHead);
     const int k1 = s_rec[r + 1];
     // b1's slots with the z reads, one wait for all of them (slots past F read
     // the words after s_bias -- inside the block's LDS -- and are dropped)
@@ -269,10 +233,10 @@ hubfactor_gc1_kernel(FactorArgs a) {
     {
       int k = s_rec[r];
       const int kl = k1 - 1;
-      int2 p = it[max(min(k, kl), 0)];
+      HubItem p = it[max(min(k, kl), 0)];
 #pragma unroll 2
       for (; k < k1; ++k) {
-        const int2 pn = it[min(k + 1, kl)];
+        const HubItem pn = it[min(k + 1, kl)];
         const float v = __int_as_float(p.y);
         const float* srow = s_S + p.x * F + 4 * c16;
         float4 sv[NTQ];
@@ -342,7 +306,7 @@ hubfactor_gc1_kernel(FactorArgs a) {
       *reinterpret_cast<f32x4*>(s_red + (((t * 3 + quarter - 1) * 2 + strip) * 64 + lane) * 4) = pc[t];
   // the lane's four output row ids: one 16-B read ahead of the barrier (a read
   // per store, each behind its own wait, was four round trips after it)
-  const int4 orow = *reinterpret_cast<const int4*>(s_rec + kRecRow + 16 * strip + (lane >> 4) * 4);
+  const int4 orow = *reinterpret_cast<const int4*>(s_rec + kHubRecRow + 16 * strip + (lane >> 4) * 4);
   __syncthreads();
   if (quarter == 0) {
     const int rid[4] = {orow.x, orow.y, orow.z, orow.w};
@@ -380,29 +344,22 @@ __global__ void __launch_bounds__(1024) lds_poison_kernel(uint32_t word) {
 using namespace gcnk;
 
 extern "C" int gcnk_debug_poison_lds(uint32_t word, void* stream) {
-  static std::atomic<uint64_t> done{0};
-  const hipError_t attr = dyn_lds_attr(done, reinterpret_cast<const void*>(&lds_poison_kernel), 160 * 1024);
-  if (attr != hipSuccess) return hip_check(attr, "lds_poison_kernel LDS attribute");
-  hipLaunchKernelGGL(lds_poison_kernel, dim3(1024), dim3(1024), 160 * 1024, reinterpret_cast<hipStream_t>(stream), word);
-  return launch_check("lds_poison_kernel");
+  return launch_big_lds<lds_poison_kernel>("lds_poison_kernel", dim3(1024), dim3(1024), 160 * 1024, stream, word);
 }
-
-static int pick_np(int32_t P) { return P <= 16 ? 1 : 2; }
 
 static int64_t hubfactor_lds_bytes(int32_t F, int32_t Kc, int32_t nhub, int32_t rec_words, int32_t P) {
-  const int64_t Fz = 64 * pick_ntq(F) + 4, Kr = 4 * pick_ks(Kc);
-  const int64_t r1 = std::max<int64_t>(Kr * F + bpad(F, pick_ntq(F)), (int64_t)kRB * Fz);
-  return 4 * (r1 + (int64_t)nhub * F + F + rec_words + pick_np(P) * 3 * 2 * 64 * 4);
+  const int64_t r1 = hub_region1_floats(4 * pick_ks(Kc), F, hub_pick_ntq(F));
+  return 4 * (r1 + (int64_t)nhub * F + F + rec_words + hub_red_floats(hub_pick_np(P)));
 }
 
-// U's staged rows (u_lds): kRB rows of 4 KS floats at a stride of 4 (mod 64)
+// U's staged rows (u_lds): kHubRows rows of 4 KS floats at a stride of 4 (mod 64)
 static int64_t hubfactor_u_bytes(int32_t Kc) {
   const int64_t ks = pick_ks(Kc);
-  return 4 * (int64_t)kRB * (64 * ((4 * ks - 4 + 63) / 64) + 4);
+  return 4 * (int64_t)kHubRows * (64 * ((4 * ks - 4 + 63) / 64) + 4);
 }
 
 extern "C" int64_t gcnk_hubfactor_lds_bytes(int32_t F, int32_t Kc, int32_t nhub, int32_t rec_words, int32_t P) {
-  if (F <= 0 || Kc <= 0 || nhub <= 0 || rec_words < kRecHead || P <= 0 || P > kProjMax) return GCNK_EARG;
+  if (F <= 0 || Kc <= 0 || nhub <= 0 || rec_words < kHubRecHead || P <= 0 || P > kHubProjMax) return GCNK_EARG;
   return hubfactor_lds_bytes(F, Kc, nhub, rec_words, P);
 }
 
@@ -421,9 +378,9 @@ static int hubfactor_route(int32_t F, int32_t Kc, int32_t nhub, int32_t rec_word
                            bool u_aligned16, FactorRoute& rt) {
   rt = FactorRoute{};
   if (F <= 0 || Kc <= 0 || nhub <= 0 || P <= 0) return 1;
-  if (ldu < Kc || rec_words < kRecHead || rec_words % 4) return 2;
-  if (F % 4 || F > 256 || Kc > 4 * kMaxKsteps || P > kProjMax) return 3;
-  rt.ks = pick_ks(Kc); rt.ntq = pick_ntq(F); rt.np = pick_np(P);
+  if (ldu < Kc || !hub_rec_words_ok(rec_words)) return 2;
+  if (F % 4 || F > 256 || Kc > 4 * kMaxKsteps || P > kHubProjMax) return 3;
+  rt.ks = pick_ks(Kc); rt.ntq = hub_pick_ntq(F); rt.np = hub_pick_np(P);
   rt.lds_b = hubfactor_lds_bytes(F, Kc, nhub, rec_words, P);
   if (rt.lds_b > 160 * 1024) return 5;
   // U's rows through LDS where they fit (R8: 95 + 8.7 KB; the 20ng-shaped 70
@@ -452,17 +409,10 @@ extern "C" int gcnk_hubfactor_gc1_route(int32_t F, int32_t Kc, int32_t nhub, int
   return GCNK_OK;
 }
 
-// The dynamic-LDS limit is raised once per kernel instantiation and device
-// (dyn_lds_attr), then the launch.
 template <int KS, int NTQ, int NP>
 static int launch_factor(const FactorArgs& a, int64_t nblk, int64_t lds_b, void* stream) {
-  static std::atomic<uint64_t> done{0};
-  const hipError_t attr =
-      dyn_lds_attr(done, reinterpret_cast<const void*>(&hubfactor_gc1_kernel<KS, NTQ, NP>), 160 * 1024);
-  if (attr != hipSuccess) return hip_check(attr, "hubfactor_gc1_kernel LDS attribute");
-  hipLaunchKernelGGL((hubfactor_gc1_kernel<KS, NTQ, NP>), dim3((unsigned)nblk), dim3(kThreads), (size_t)lds_b,
-                     reinterpret_cast<hipStream_t>(stream), a);
-  return launch_check("hubfactor_gc1_kernel");
+  return launch_big_lds<hubfactor_gc1_kernel<KS, NTQ, NP>>("hubfactor_gc1_kernel", dim3((unsigned)nblk),
+                                                           dim3(kHubThreads), (size_t)lds_b, stream, a);
 }
 
 extern "C" int gcnk_hubfactor_gc1_f32(int32_t M, int32_t F, int32_t Kc, int32_t nhub, int32_t P, const float* U,
@@ -501,7 +451,7 @@ extern "C" int gcnk_hubfactor_gc1_f32(int32_t M, int32_t F, int32_t Kc, int32_t 
   a.U = U; a.ldu = ldu; a.W = W; a.ldw = ldw; a.k0 = k0;
   a.S = S; a.lds = lds; a.rec = rec; a.rec_words = rec_words;
   a.W2 = W2; a.ldw2 = ldw2; a.H = H; a.ldh = ldh; a.C2 = C2; a.ldc2 = ldc2;
-  const int64_t nblk = ((int64_t)M + kRB - 1) / kRB;
+  const int64_t nblk = hub_blocks(M);
   const int ks = rt.ks, ntq = rt.ntq, np = rt.np;
   const int64_t lds_l = rt.lds_launch;
 #define GCNK_FACTOR_CASE(KS_, NTQ_)                                                   \

@@ -15,9 +15,8 @@
 // point (hand-made CSRs, bitwise against numpy, sentinels around every output);
 // tests/test_gpu_parity.py pins the whole build to the host restatement.
 //
-// A_H is stored as one record per 32-row block of `perm` (csrc/factor.hip):
-// 33 block-relative item offsets, 3 pad words, 32 row ids (-1 past M), then
-// the block's rows' hub-column items {hub index, value bits} in CSR order.
+// A_H is stored as one record per 32-row block of `perm`, in the format of
+// hub_block.h; a row's hub-column items are in CSR order.
 //
 // Both kernels are one-time setup: latency-bound gathers over ~M rows, a few
 // hundred microseconds for R8 against ~80 ms for the host build they replace.
@@ -29,7 +28,7 @@
 // gcnk_*_gather_rows) -- the torch element-wise / nonzero / repeat_interleave /
 // index kernels factor.py used for them cost ~120 ms of first-use module loads
 // in a fresh process (the first forward's largest piece, scripts/first_forward.py).
-#include "gcnk_common.h"
+#include "hub_block.h"
 
 #include <climits>
 
@@ -37,9 +36,6 @@ namespace gcnk {
 namespace {
 
 constexpr int kBuildRows = 4;      // rows (one wave each) per 256-thread workgroup
-constexpr int kRecRows = 32;       // csrc/factor.hip kRB
-constexpr int kRecHeadW = 68;      // csrc/factor.hip kRecHead
-constexpr int kRecRowIds = 36;
 
 // One wave per output position p: row r = perm[p]; lane c owns columns c and
 // c + 64 (Kcp <= 128).  Items are read in CSR order; loads of four items are
@@ -107,14 +103,14 @@ __global__ void __launch_bounds__(64) factor_rec_kernel(const int32_t* __restric
                                                         const int32_t* __restrict__ hub_index,
                                                         const int32_t* __restrict__ perm, int32_t* __restrict__ rec,
                                                         int32_t rec_words, int32_t* __restrict__ overflow) {
-  __shared__ int s_off[kRecRows + 1];
-  __shared__ int s_row[kRecRows];
+  __shared__ int s_off[kHubRows + 1];
+  __shared__ int s_row[kHubRows];
   const int lane = threadIdx.x;
   const int64_t b = blockIdx.x;
   int32_t* rb = rec + b * rec_words;
-  const int64_t p = b * kRecRows + lane;
+  const int64_t p = b * kHubRows + lane;
   int r = -1, cnt = 0;
-  if (lane < kRecRows && p < M) {
+  if (lane < kHubRows && p < M) {
     r = perm[p];
     for (int j = rowptr[r]; j < rowptr[r + 1]; ++j) cnt += hub_index[colind[j]] >= 0;
   }
@@ -125,19 +121,19 @@ __global__ void __launch_bounds__(64) factor_rec_kernel(const int32_t* __restric
     const int o = __shfl_up(incl, s, 64);
     if (lane >= s) incl += o;
   }
-  if (lane < kRecRows) {
+  if (lane < kHubRows) {
     s_off[lane] = incl - cnt;
     s_row[lane] = r;
   }
-  if (lane == kRecRows - 1) s_off[kRecRows] = incl;
+  if (lane == kHubRows - 1) s_off[kHubRows] = incl;
   __syncthreads();
-  if (lane <= kRecRows) rb[lane] = s_off[lane];
-  if (lane < kRecRows) rb[kRecRowIds + lane] = s_row[lane];
+  if (lane <= kHubRows) rb[lane] = s_off[lane];
+  if (lane < kHubRows) rb[kHubRecRow + lane] = s_row[lane];
   int dropped = 0;
-  for (int i = 0; i < kRecRows; ++i) {
+  for (int i = 0; i < kHubRows; ++i) {
     const int ri = s_row[i];
     if (ri < 0) break;
-    int base = kRecHeadW + 2 * s_off[i];
+    int base = kHubRecHead + 2 * s_off[i];
     const int e = rowptr[ri + 1];
     for (int j0 = rowptr[ri]; j0 < e; j0 += 64) {
       const int j = j0 + lane;
@@ -468,7 +464,7 @@ extern "C" int gcnk_factor_diag_f32(const int32_t* rowptr, const int32_t* colind
     set_error("gcnk_factor_diag_f32: bad sizes or null operand (M=%d)", M);
     return GCNK_EARG;
   }
-  const int64_t npos = ((int64_t)M + kRecRows - 1) / kRecRows * kRecRows;
+  const int64_t npos = hub_blocks(M) * kHubRows;
   hipLaunchKernelGGL(factor_diag_kernel, dim3((unsigned)((npos + 255) / 256)), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), rowptr, colind, val, M, (int32_t)npos, hub_index, perm,
                      diag, pre);
@@ -478,12 +474,12 @@ extern "C" int gcnk_factor_diag_f32(const int32_t* rowptr, const int32_t* colind
 extern "C" int gcnk_factor_records(const int32_t* rowptr, const int32_t* colind, const float* val, int32_t M,
                                    const int32_t* hub_index, const int32_t* perm, int32_t* rec, int32_t rec_words,
                                    int32_t* overflow, void* stream) {
-  if (M <= 0 || rec_words < kRecHeadW || rec_words % 4 || !rowptr || !colind || !val || !hub_index || !perm ||
+  if (M <= 0 || !hub_rec_words_ok(rec_words) || !rowptr || !colind || !val || !hub_index || !perm ||
       !rec || !overflow) {
     set_error("gcnk_factor_records: bad sizes or null operand (M=%d rec_words=%d)", M, rec_words);
     return GCNK_EARG;
   }
-  const unsigned nblk = (unsigned)(((int64_t)M + kRecRows - 1) / kRecRows);
+  const unsigned nblk = (unsigned)hub_blocks(M);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   int rc = hip_check(hipMemsetAsync(rec, 0, (size_t)nblk * rec_words * 4, s), "records memset");
   if (!rc) rc = hip_check(hipMemsetAsync(overflow, 0, 4, s), "overflow memset");

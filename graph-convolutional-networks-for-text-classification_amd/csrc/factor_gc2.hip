@@ -26,7 +26,7 @@
 //
 // Out-of-range lanes go through buffer resources sized to the operands (loads
 // return 0, stores are dropped); no global partials, counters or atomics.
-#include "gcnk_common.h"
+#include "hub_block.h"
 
 #include <algorithm>
 
@@ -34,8 +34,6 @@ namespace gcnk {
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kRB = 32;                    // rows per block record (csrc/factor.hip)
-constexpr int kRecRow = 36, kRecHead = 68;
 constexpr int kMaxHubs = 128;
 constexpr int kHubU = 16;                  // items (and gathers) in flight per lane of a hub-row workgroup
 constexpr int kDocU = 8;                   // items of a document row read from LDS per batch
@@ -85,11 +83,11 @@ __device__ __forceinline__ void stamp2(const Gc2Args& a, int k) {
 // AND on the value: a select per product element made the chain ~36 instructions
 // a term, 1.4 us of a lone wave's issue.)
 template <int P4>
-__device__ __forceinline__ void doc_chain(f32x4& acc, const int2* s_items, const float* s_hub, int zero_off, int c,
+__device__ __forceinline__ void doc_chain(f32x4& acc, const HubItem* s_items, const float* s_hub, int zero_off, int c,
                                           int jb, int je) {
   constexpr int P = 4 * P4;
   for (int j0 = jb; j0 < je; j0 += kDocU) {
-    int2 it[kDocU];
+    HubItem it[kDocU];
     f32x4 hv[kDocU];
 #pragma unroll
     for (int u = 0; u < kDocU; ++u) it[u] = s_items[min(j0 + u, je - 1)];
@@ -193,7 +191,7 @@ __global__ void __launch_bounds__(kThreads) factored_spmm_row_kernel(Gc2Args a) 
   int32_t* s_rec = reinterpret_cast<int32_t*>(smem);
   float* s_hub = smem + a.rec_words;                       // [H][P], then a zero row
   const int i = tid / P4;                                  // row of the block (threads past 32 rows: none)
-  const bool rowt = i < kRB;
+  const bool rowt = i < kHubRows;
   // round 1 (b2 above): the record by LDS-DMA; per row thread its diag, precede
   // count and row id; per thread the hub id of each 16-B piece of S2[hubs] it
   // stages (a vector load from the argument block: scalar loads of the ids cost
@@ -204,11 +202,11 @@ __global__ void __launch_bounds__(kThreads) factored_spmm_row_kernel(Gc2Args a) 
     for (int e0 = wv * 64; e0 < rw4; e0 += kThreads)
       if (e0 + lane < rw4) lds_dma16(rec + 4 * (e0 + lane), s_rec + 4 * e0);
   }
-  const uint32_t pos4 = rowt ? 4u * (uint32_t)(blk * kRB + i) : kBufOob;
+  const uint32_t pos4 = rowt ? 4u * (uint32_t)(blk * kHubRows + i) : kBufOob;
   const float dg = buf_load_f32(buffer_rsrc(a.diag, a.pos_bytes), pos4);
   const int32_t pre = (int32_t)buf_load_u32(buffer_rsrc(a.pre, a.pos_bytes), pos4);
   const int32_t rid =
-      (int32_t)buf_load_u32(buffer_rsrc(rec, 4u * (uint32_t)a.rec_words), rowt ? 4u * (uint32_t)(kRecRow + i) : kBufOob);
+      (int32_t)buf_load_u32(buffer_rsrc(rec, 4u * (uint32_t)a.rec_words), rowt ? 4u * (uint32_t)(kHubRecRow + i) : kBufOob);
   constexpr int NQ = (kMaxHubs * P4 + kThreads - 1) / kThreads;   // pieces of S2[hubs] per thread
   const int nh4 = a.H * P4;
   int32_t hid[NQ];
@@ -236,7 +234,7 @@ __global__ void __launch_bounds__(kThreads) factored_spmm_row_kernel(Gc2Args a) 
   // diagonal: diag and the unloaded own row are both 0, and fma(0, 0, acc) is acc),
   // the other items
   const int32_t off0 = s_rec[i], off1 = s_rec[i + 1];
-  const int2* s_items = reinterpret_cast<const int2*>(s_rec + kRecHead);
+  const HubItem* s_items = reinterpret_cast<const HubItem*>(s_rec + kHubRecHead);
   const int jb = doc ? off0 : 0, je = doc ? off1 : 0, jm = doc ? min(off0 + pre, off1) : 0;
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   doc_chain<P4>(acc, s_items, s_hub, a.H * P, c, jb, jm);
@@ -266,12 +264,12 @@ extern "C" int gcnk_hubfactor_gc2_f32(int32_t M, int32_t H, int32_t P, const int
                                       const float* S2, int64_t lds2, const float* b2, float* out, int64_t ldo,
                                       void* stream) {
   if (M <= 0 || H <= 0 || P <= 0 || !rec || !diag || !pre || !hub_ids || !hub_rp || !hub_ci || !hub_val || !S2 ||
-      !out || rec_words < kRecHead || rec_words % 4 || lds2 < P || ldo < P) {
+      !out || !hub_rec_words_ok(rec_words) || lds2 < P || ldo < P) {
     set_error("gcnk_hubfactor_gc2_f32: bad sizes or null operand (M=%d hubs=%d P=%d rec_words=%d)", M, H, P,
               rec_words);
     return GCNK_EARG;
   }
-  const int64_t nblk = ((int64_t)M + kRB - 1) / kRB;
+  const int64_t nblk = hub_blocks(M);
   const int64_t s2_bytes = 4 * ((int64_t)(M - 1) * lds2 + P), out_bytes = 4 * ((int64_t)(M - 1) * ldo + P);
   const int64_t lds_doc = 4 * ((int64_t)rec_words + ((int64_t)H + 1) * P);   // record | S2[hubs] | a zero row
   const int64_t lds_hub = 16 * (int64_t)(kPartSlots + kCollect * 8);
@@ -288,7 +286,7 @@ extern "C" int gcnk_hubfactor_gc2_f32(int32_t M, int32_t H, int32_t P, const int
   a.S2 = S2; a.b2 = b2; a.out = out;
   a.ld4 = (uint32_t)(4 * lds2); a.ldo4 = (uint32_t)(4 * ldo);
   a.s2_bytes = (uint32_t)s2_bytes; a.out_bytes = (uint32_t)out_bytes;
-  a.pos_bytes = (uint32_t)(nblk * kRB * 4); a.b2_bytes = b2 ? 4u * (uint32_t)P : 0u;
+  a.pos_bytes = (uint32_t)(nblk * kHubRows * 4); a.b2_bytes = b2 ? 4u * (uint32_t)P : 0u;
   a.stamps = debug_stamps();
   for (int j = 0; j < kMaxHubs; ++j) a.hub_id[j] = j < H ? hub_ids[j] : 0;
   for (int j = 0; j <= kMaxHubs; ++j) a.hub_rp[j] = hub_rp[j <= H ? j : H];

@@ -46,6 +46,20 @@ inline hipError_t dyn_lds_attr(std::atomic<uint64_t>& done, const void* fn, int 
   return e;
 }
 
+// The launch of a kernel whose dynamic LDS may exceed the default limit: the limit is raised to the CU's 160 KiB
+// first (dyn_lds_attr; the per-device bit set belongs to this instantiation, so to `Kernel` alone).
+template <auto Kernel, typename... Args>
+int launch_big_lds(const char* name, dim3 grid, dim3 block, size_t lds_bytes, void* stream, const Args&... args) {
+  static std::atomic<uint64_t> done{0};
+  const hipError_t attr = dyn_lds_attr(done, reinterpret_cast<const void*>(Kernel), 160 * 1024);
+  if (attr != hipSuccess) {
+    set_error("%s LDS attribute: %s", name, hipGetErrorString(attr));
+    return GCNK_EHIP;
+  }
+  hipLaunchKernelGGL(Kernel, grid, block, lds_bytes, reinterpret_cast<hipStream_t>(stream), args...);
+  return launch_check(name);
+}
+
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // The hand-off of a launch whose workgroups all read (or store) something that only the last
@@ -128,6 +142,23 @@ __device__ __forceinline__ float hash_uniform(uint32_t seed_lo, uint32_t seed_hi
   h = mix32(h ^ (uint32_t)(idx >> 32) ^ seed_hi);
   h = mix32(h + 0x9e3779b9U);
   return (float)(h >> 8) * (1.0f / 16777216.0f);
+}
+
+// A-hat = D^-1/2 (A + I) D^-1/2 in the reference's arithmetic (utils.py:198,209-212): d = rowsum^-0.5 in float64
+// with inf -> 0, and an entry (d[r] a) d[c] in float64, rounded to fp32 once.
+__device__ __forceinline__ double ahat_inv_sqrt_degree(double rowsum) {
+  const double p = pow(rowsum, -0.5);
+  return isinf(p) ? 0.0 : p;
+}
+__device__ __forceinline__ float ahat_value(double dr, double a, double dc) { return (float)((dr * a) * dc); }
+
+// The label of a row of scores is the first index of its maximum, a NaN maximal (as torch.max): one step of the walk
+// over the row in order, score v at index c against the best so far.
+__device__ __forceinline__ void label_step(float& best_v, int32_t& best, float v, int32_t c) {
+  if (!(best_v != best_v) && (v > best_v || v != v)) {   // a NaN wins and stays
+    best_v = v;
+    best = c;
+  }
 }
 
 // `b` is bias[col] (0 when there is no bias), preloaded by the caller.

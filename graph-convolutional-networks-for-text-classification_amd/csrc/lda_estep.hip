@@ -418,11 +418,7 @@ extern "C" int gcnk_lda_estep_f64(const int32_t* indptr, const int32_t* indices,
   p.a = a;
   p.lda = lda;
   p.threshold = threshold;
-  static std::atomic<uint64_t> done{0};
   const int lds_bytes = kDocs * wave_doubles(K) * (int)sizeof(double);
-  const hipError_t attr = dyn_lds_attr(done, reinterpret_cast<const void*>(&lda_estep_kernel), 160 * 1024);
-  if (attr != hipSuccess) return hip_check(attr, "lda_estep_kernel LDS attribute");
   const unsigned nblk = (unsigned)(((int64_t)B + kDocs - 1) / kDocs);
-  hipLaunchKernelGGL(lda_estep_kernel, dim3(nblk), dim3(64 * kDocs), (size_t)lds_bytes, (hipStream_t)stream, p);
-  return launch_check("lda_estep_kernel");
+  return launch_big_lds<lda_estep_kernel>("lda_estep_kernel", dim3(nblk), dim3(64 * kDocs), (size_t)lds_bytes, stream, p);
 }

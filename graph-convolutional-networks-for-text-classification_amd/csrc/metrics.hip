@@ -29,7 +29,7 @@ class_stats_kernel(const float* __restrict__ logits, int64_t ld, const int64_t* 
     float bv = p[0];
     for (int32_t c = 1; c < nclass; ++c) {
       const float v = p[c];
-      if (!(bv != bv) && (v > bv || v != v)) {  // first maximum; a NaN wins and stays
+      if (!(bv != bv) && (v > bv || v != v)) {  // label_step's rule, in place: through the call this loop compiles differently
         bv = v;
         best = c;
       }

@@ -53,7 +53,7 @@ __global__ void norm_rows_kernel(const int32_t* __restrict__ rowptr, const int32
   }
   if (!placed) s += 1.0;
   counts[r] = (e - b) + (has ? 0 : 1);
-  const double p = pow(s, -0.5);
+  const double p = pow(s, -0.5);   // ahat_inv_sqrt_degree, in place: through the call the registers are dealt differently
   d[r] = isinf(p) ? 0.0 : p;
 }
 
@@ -72,7 +72,7 @@ __global__ void norm_fill_kernel(const int32_t* __restrict__ rowptr, const int32
     const int32_t c = colind[k];
     if (!placed && c > r) {
       colind_out[o] = r;
-      val_out[o++] = (float)((dr * 1.0) * dr);
+      val_out[o++] = ahat_value(dr, 1.0, dr);
       placed = true;
     }
     double a = (double)val[k];
@@ -81,11 +81,11 @@ __global__ void norm_fill_kernel(const int32_t* __restrict__ rowptr, const int32
       placed = true;
     }
     colind_out[o] = c;
-    val_out[o++] = (float)((dr * a) * d[c]);
+    val_out[o++] = ahat_value(dr, a, d[c]);
   }
   if (!placed) {
     colind_out[o] = r;
-    val_out[o] = (float)((dr * 1.0) * dr);
+    val_out[o] = ahat_value(dr, 1.0, dr);
   }
 }
 

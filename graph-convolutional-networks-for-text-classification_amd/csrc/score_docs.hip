@@ -12,12 +12,12 @@
 //   dd     = deg^-1/2,  c_self = fp32(dd dd),  c_j = fp32((dd a[d, j]) dh[j])
 //   z[n]   = c_self sum_k x[d, k] W1[k0 + k, n] + sum_j c_j S_T[j, n] + b1[n]
 //   out[p] = c_self sum_n relu(z[n]) W2[n, p] + sum_j c_j S2_T[j, p] + b2[p]
-// -- the coefficients are normalize.hip's recipe for A-hat (float64, rounded to
+// -- the coefficients are A-hat's arithmetic (ahat_value: float64, rounded to
 // fp32 once), dh[j] = D^-1/2 of hub j.  No document depends on another: one
 // launch, no hand-off between workgroups, no atomics, bitwise reproducible.
 //
-// One workgroup = 32 documents (512 threads, 8 waves: 2 row strips x 4 quarters
-// of the F columns), the shape of hubfactor_gc1_kernel (factor.hip):
+// One workgroup = 32 documents as one block of hub_block.h (8 waves: 2 row
+// strips x 4 quarters of the F columns):
 //   0. every operand in one round of loads: the block's x / a / dh values into
 //      registers, B = [W1[k0 : k0 + Kc]; S_T] into LDS by 16-B DMA (rows of F
 //      floats; in chunks of rows where it exceeds the LDS left over: Kc + H = 256
@@ -32,7 +32,7 @@
 //      in a fixed order), out = c_self s2 + e + b2, the argmax per row from LDS.
 // Rows past B, columns past F / P and a missing b1 / b2 go through buffer
 // resources (device_mem.h): no compares in the loops.
-#include "gcnk_common.h"
+#include "hub_block.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -40,16 +40,9 @@
 namespace gcnk {
 namespace {
 
-constexpr int kRB = 32;         // documents per workgroup
-constexpr int kThreads = 512;   // 8 waves: 2 row strips x 4 column quarters
-constexpr int kProjMax = 32;    // P <= 32 (NP = 1 or 2 MFMA n-tiles)
 constexpr int kMaxKc = 128, kMaxHubs = 128;
-constexpr int kOutLd = kProjMax + 1;   // s_out row stride
+constexpr int kOutLd = kHubProjMax + 1;   // s_out row stride
 constexpr int kLdsFloats = 160 * 1024 / 4;
-// zero floats after a staged chunk of B: the last n-tile of a wave reads up to
-// column 64 NTQ - 1 of the chunk's last k-row (factor.hip's bpad)
-__host__ __device__ constexpr int bpad(int f, int ntq) { return 64 * ntq - f > 64 ? 64 * ntq - f : 64; }
-__host__ __device__ constexpr int pick_ntq(int f) { return f <= 128 ? 2 : f <= 192 ? 3 : 4; }
 // Columns of an operand row [c_self x (Kc) | c (H) | 0 ...] that the kernel writes: phase 3 reads the c
 // columns up to Kc + 16 KHQ, phase 1 every column up to Kc + H rounded up to 4 -- which lies up to 3
 // columns past Kc + 16 KHQ where H = 16 KHQ and Kc % 4 != 0 (and K % 4 != 0 in general)
@@ -80,7 +73,7 @@ __device__ __forceinline__ float relu_keep_nan(float v) { return !(v <= 0.f) ? v
 // NTQ: 16-column tiles of F per wave (F <= 64 NTQ); NP: n-tiles of P; KHQ: k-steps of
 // the hub sum c S2_T per quarter (H <= 16 KHQ)
 template <int NTQ, int NP, int KHQ>
-__global__ void __launch_bounds__(kThreads)
+__global__ void __launch_bounds__(kHubThreads)
 score_docs_kernel(ScoreArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -89,21 +82,21 @@ score_docs_kernel(ScoreArgs a) {
   const int c = lane & 15, q = lane >> 4;
   const int F = a.F, Q = F / 4, Kc = a.Kc, H = a.H, P = a.P;
   const int K = Kc + H, Kp = (K + 3) & ~3;
-  constexpr int Fp = 64 * NTQ, Fz = Fp + 4;   // s_Z row stride: 16-B rows, conflict-free MFMA-layout accesses
+  constexpr int Fp = 64 * NTQ, Fz = hub_z_stride(NTQ);
   constexpr int kq = Fp / 16;                 // k-steps of h W2 per quarter
   const int kpa = a.kpa;
-  const int64_t d0 = (int64_t)blockIdx.x * kRB;
-  const int rows_here = (int)min<int64_t>(kRB, a.B - d0);   // >= 1
-  // LDS: region1 = s_B [<= ch][F] + bpad zeros (phase 1), then s_Z [kRB][Fz]
-  //      | s_A [kRB][kpa]: the operand rows [c_self x (Kc) | c (H) | 0 .. operand_cols], kpa = 4 (mod 64)
-  //      | s_red [NP][2][3][2][64][4] | s_out [kRB][kOutLd] | s_cs [kRB] | s_dd [kRB] (double)
+  const int64_t d0 = (int64_t)blockIdx.x * kHubRows;
+  const int rows_here = (int)min<int64_t>(kHubRows, a.B - d0);   // >= 1
+  // LDS: region1 = s_B [<= ch][F] + hub_bpad zeros (phase 1), then s_Z [kHubRows][Fz]
+  //      | s_A [kHubRows][kpa]: the operand rows [c_self x (Kc) | c (H) | 0 .. operand_cols], kpa = 4 (mod 64)
+  //      | s_red (two projected sums) | s_out [kHubRows][kOutLd] | s_cs [kHubRows] | s_dd [kHubRows] (double)
   float* s_B = smem;
   float* s_Z = smem;
   float* s_A = smem + a.r1;
-  float* s_red = s_A + kRB * kpa;
-  float* s_out = s_red + NP * 2 * 3 * 2 * 64 * 4;
-  float* s_cs = s_out + kRB * kOutLd;
-  double* s_dd = reinterpret_cast<double*>(s_cs + kRB);
+  float* s_red = s_A + kHubRows * kpa;
+  float* s_out = s_red + hub_red_floats(NP, 2);
+  float* s_cs = s_out + kHubRows * kOutLd;
+  double* s_dd = reinterpret_cast<double*>(s_cs + kHubRows);
 
   // ---- 0. loads.  First the block's x / a / dh values (the coefficients wait for
   //      these only), 16 threads per document, thread c16 the columns c16 + 16 i.
@@ -137,9 +130,9 @@ score_docs_kernel(ScoreArgs a) {
   // K: the operand rows are 0 there, and 0 x a stale NaN is a NaN) and the pad
   auto stage = [&](int g0) __attribute__((always_inline)) {
     const int rows4 = min(a.ch, Kp - g0), rows = min(rows4, K - g0);
-    for (int e = rows * F + tid; e < rows4 * F + bpad(F, NTQ); e += kThreads) s_B[e] = 0.f;
+    for (int e = rows * F + tid; e < rows4 * F + hub_bpad(F, NTQ); e += kHubThreads) s_B[e] = 0.f;
     const int n4 = rows * Q;
-    for (int e0 = wv * 64; e0 < n4; e0 += kThreads) {
+    for (int e0 = wv * 64; e0 < n4; e0 += kHubThreads) {
       const int e = e0 + lane;
       if (e < n4) {
         const int rr = e / Q, g = g0 + rr, q4 = 4 * (e - rr * Q);
@@ -149,13 +142,11 @@ score_docs_kernel(ScoreArgs a) {
     }
   };
   stage(0);
-  // Phase 3's B fragments through buffer resources over exactly the operands: a
-  // row past F (W2) or H (S2_T) lies past them and reads 0; a column past P
-  // starts from an offset past every resource.  b1 / b2 the same way (a missing
-  // one: the zero-byte resource).
+  // Phase 3's B fragments of W2 (rows past F read 0) and S2_T (rows past H),
+  // b1 / b2 the same way (a missing one: the zero-byte resource).
   float bw[NP][kq], bs[NP][KHQ], b1v[NTQ], b2v[NP];
-  const int qe = strip ? 3 - quarter : quarter;   // phase 1's tiles: dealt in opposite directions in the two strips
-  const int c0 = qe * 16 + c;
+  const HubDeal deal = hub_deal(strip, quarter, lane, F, NTQ);   // phase 1's tiles
+  const int c0 = deal.c0;
   {
     const __amdgpu_buffer_rsrc_t rw = buffer_rsrc(a.W2, (uint32_t)(((F - 1) * a.ldw2 + P) * 4));
     const __amdgpu_buffer_rsrc_t rs = buffer_rsrc(a.S2, (uint32_t)(((H - 1) * a.lds2 + P) * 4));
@@ -164,16 +155,12 @@ score_docs_kernel(ScoreArgs a) {
 #pragma unroll
     for (int t = 0; t < NP; ++t) {
       const int col = 16 * t + c;
-      uint32_t off = col < P ? (uint32_t)(((4 * quarter * kq + q) * a.ldw2 + col) * 4) : kBufOob;
-#pragma unroll
-      for (int j = 0; j < kq; ++j, off += (uint32_t)(16 * a.ldw2)) bw[t][j] = buf_load_f32(rw, off);
-      off = col < P ? (uint32_t)(((4 * quarter * KHQ + q) * a.lds2 + col) * 4) : kBufOob;
-#pragma unroll
-      for (int j = 0; j < KHQ; ++j, off += (uint32_t)(16 * a.lds2)) bs[t][j] = buf_load_f32(rs, off);
+      hub_proj_frags(bw[t], rw, 4 * quarter * kq + q, (int)a.ldw2, col, P);
+      hub_proj_frags(bs[t], rs, 4 * quarter * KHQ + q, (int)a.lds2, col, P);
       b2v[t] = buf_load_f32(rb2, col < P ? 4u * col : kBufOob);
     }
 #pragma unroll
-    for (int i = 0; i < NTQ; ++i) b1v[i] = buf_load_f32(rb1, 4u * (c0 + 64 * i));   // (a column past F: past the resource)
+    for (int i = 0; i < NTQ; ++i) b1v[i] = buf_load_f32(rb1, 4u * (c0 + kHubTileStep * i));   // (a column past F: past the resource)
   }
   // the raw edge weights into the operand row's c columns (0 from H to 16 KHQ) and
   // zeros into the columns phase 1 reads past them (at most 3: operand_cols),
@@ -186,30 +173,26 @@ score_docs_kernel(ScoreArgs a) {
   if (c16 == 0) {
     double s = 0.0;
     for (int j = 0; j < H; ++j) s += (double)arow[Kc + j];
-    s_dd[r] = pow(1.0 + s, -0.5);
+    s_dd[r] = pow(1.0 + s, -0.5);   // (deg >= 1 for the non-negative weights of the contract: no inf -> 0 step)
   }
   __syncthreads();
   {
     const double dd = s_dd[r];
-    const float cs = (float)(dd * dd);
+    const float cs = ahat_value(dd, 1.0, dd);
 #pragma unroll
-    for (int i = 0; i < KHQ; ++i) arow[Kc + c16 + 16 * i] = (float)((dd * (double)av[i]) * dv[i]);
+    for (int i = 0; i < KHQ; ++i) arow[Kc + c16 + 16 * i] = ahat_value(dd, (double)av[i], dv[i]);
 #pragma unroll
     for (int i = 0; i < kMaxKc / 16; ++i)
       if (c16 + 16 * i < Kc) arow[c16 + 16 * i] = cs * xv[i];
     if (c16 == 0) s_cs[r] = cs;
   }
 
-  // ---- 1. Z = [c_self x | c] B for this wave's strip and its tiles of F (the
-  //      T = ceil(F / 16) real tiles dealt round-robin over the quarters, as
-  //      factor.hip deals them; a slot without a real tile keeps its zero
-  //      accumulator)
+  // ---- 1. Z = [c_self x | c] B for this wave's strip and its tiles of F
   f32x4 acc[NTQ];
 #pragma unroll
   for (int i = 0; i < NTQ; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
   {
-    const int T = (F + 15) >> 4;
-    const int nt = __builtin_amdgcn_readfirstlane(min(max((T - qe + 3) >> 2, 0), NTQ));
+    const int nt = deal.nt;
     const float* sa = s_A + (16 * strip + c) * kpa + q;
     for (int g0 = 0; g0 < Kp; g0 += a.ch) {
       if (g0 > 0) {
@@ -228,7 +211,7 @@ score_docs_kernel(ScoreArgs a) {
           const float* br = sb + 4 * s * F;
           float bf[NT];
 #pragma unroll
-          for (int i = 0; i < NT; ++i) bf[i] = br[64 * i];
+          for (int i = 0; i < NT; ++i) bf[i] = br[kHubTileStep * i];
 #pragma unroll
           for (int i = 0; i < NT; ++i) acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(af, bf[i], acc[i], 0, 0, 0);
         }
@@ -243,7 +226,7 @@ score_docs_kernel(ScoreArgs a) {
           const float* br = sb + 4 * s * F;
 #pragma unroll
           for (int i = 0; i < NTQ - 2; ++i)
-            if (i < nt) acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(af, br[64 * i], acc[i], 0, 0, 0);
+            if (i < nt) acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(af, br[kHubTileStep * i], acc[i], 0, 0, 0);
         }
       }
     }
@@ -255,10 +238,10 @@ score_docs_kernel(ScoreArgs a) {
   //      they meet W2's rows past F, which read 0.
 #pragma unroll
   for (int i = 0; i < NTQ; ++i) {
-    const bool live = c0 + 64 * i < F;
+    const bool live = c0 + kHubTileStep * i < F;
 #pragma unroll
     for (int rr = 0; rr < 4; ++rr)
-      s_Z[(16 * strip + 4 * q + rr) * Fz + c0 + 64 * i] = live ? relu_keep_nan(acc[i][rr] + b1v[i]) : 0.f;
+      s_Z[(16 * strip + 4 * q + rr) * Fz + c0 + kHubTileStep * i] = live ? relu_keep_nan(acc[i][rr] + b1v[i]) : 0.f;
   }
   __syncthreads();
 
@@ -319,17 +302,13 @@ score_docs_kernel(ScoreArgs a) {
   }
   if (!a.labels) return;   // (uniform)
   __syncthreads();
-  // the label: first index of the maximum, a NaN maximal (metrics.hip's class_stats)
+  // the label (label_step)
   if (tid < rows_here) {
     const float* o = s_out + tid * kOutLd;
     int best = 0;
     float bv = o[0];
     for (int p = 1; p < P; ++p) {
-      const float v = o[p];
-      if (!(bv != bv) && (v > bv || v != v)) {
-        bv = v;
-        best = p;
-      }
+      label_step(bv, best, o[p], p);
     }
     a.labels[d0 + tid] = best;
   }
@@ -345,30 +324,24 @@ struct ScoreRoute {
 int score_route(int32_t F, int32_t Kc, int32_t H, int32_t P, ScoreRoute& rt) {
   rt = ScoreRoute{};
   if (F <= 0 || Kc <= 0 || H <= 0 || P <= 0) return 1;
-  if (F % 4 || F > 256 || Kc > kMaxKc || H > kMaxHubs || P > kProjMax) return 3;
-  rt.ntq = pick_ntq(F); rt.np = P <= 16 ? 1 : 2; rt.khq = H <= 64 ? 4 : 8;
+  if (F % 4 || F > 256 || Kc > kMaxKc || H > kMaxHubs || P > kHubProjMax) return 3;
+  rt.ntq = hub_pick_ntq(F); rt.np = hub_pick_np(P); rt.khq = H <= 64 ? 4 : 8;
   rt.wd = operand_cols(Kc, H, rt.khq);             // operand row: c_self x | c | zeros
   rt.kpa = 64 * ((rt.wd - 4 + 63) / 64) + 4;       // = 4 (mod 64): conflict-free A-layout reads
-  const int fixed = kRB * rt.kpa + rt.np * 2 * 3 * 2 * 64 * 4 + kRB * kOutLd + kRB + 2 * kRB;
-  const int kp = (Kc + H + 3) & ~3, pad = bpad(F, rt.ntq);
+  const int fixed = kHubRows * rt.kpa + hub_red_floats(rt.np, 2) + kHubRows * kOutLd + kHubRows + 2 * kHubRows;
+  const int kp = (Kc + H + 3) & ~3, pad = hub_bpad(F, rt.ntq);
   // B whole where it fits beside the rest, else in chunks of rows
   rt.ch = std::min(kp, ((kLdsFloats - fixed - pad) / F) & ~3);
   if (rt.ch < 4) return 3;
-  rt.r1 = std::max(rt.ch * F + pad, kRB * (64 * rt.ntq + 4));
+  rt.r1 = hub_region1_floats(rt.ch, F, rt.ntq);
   rt.lds_bytes = 4 * (int64_t)(rt.r1 + fixed);
   return rt.lds_bytes <= 4 * kLdsFloats ? 0 : 3;
 }
 
 template <int NTQ, int NP, int KHQ>
 int launch_score(const ScoreArgs& a, int64_t lds_b, void* stream) {
-  static std::atomic<uint64_t> done{0};
-  const hipError_t attr =
-      dyn_lds_attr(done, reinterpret_cast<const void*>(&score_docs_kernel<NTQ, NP, KHQ>), 160 * 1024);
-  if (attr != hipSuccess) return hip_check(attr, "score_docs_kernel LDS attribute");
-  const int64_t nblk = ((int64_t)a.B + kRB - 1) / kRB;
-  hipLaunchKernelGGL((score_docs_kernel<NTQ, NP, KHQ>), dim3((unsigned)nblk), dim3(kThreads), (size_t)lds_b,
-                     reinterpret_cast<hipStream_t>(stream), a);
-  return launch_check("score_docs_kernel");
+  return launch_big_lds<score_docs_kernel<NTQ, NP, KHQ>>("score_docs_kernel", dim3((unsigned)hub_blocks(a.B)),
+                                                         dim3(kHubThreads), (size_t)lds_b, stream, a);
 }
 
 }  // namespace
@@ -417,8 +390,8 @@ extern "C" int gcnk_score_docs_f32(int32_t B, int32_t F, int32_t Kc, int32_t H, 
   // starts from kBufOob and steps as far again, below 2^32)
   const int64_t lim = (int64_t)kBufOob / 4;
   if (score_route(F, Kc, H, P, rt) || ldx % 4 || lda % 4 || ldw1 % 4 || lds % 4 || !aligned16(x) || !aligned16(a) ||
-      !aligned16(W1) || !aligned16(S_T) || (reinterpret_cast<uintptr_t>(dh) & 7u) || kRB * ldx >= lim ||
-      kRB * lda >= lim || kRB * ldo >= lim || 64 * rt.ntq * ldw2 >= lim || 16 * rt.khq * lds2 >= lim) {
+      !aligned16(W1) || !aligned16(S_T) || (reinterpret_cast<uintptr_t>(dh) & 7u) || kHubRows * ldx >= lim ||
+      kHubRows * lda >= lim || kHubRows * ldo >= lim || 64 * rt.ntq * ldw2 >= lim || 16 * rt.khq * lds2 >= lim) {
     set_error("gcnk_score_docs_f32: unsupported shape (F=%d %% 4, F <= 256, Kc=%d <= 128, H=%d <= 128, P=%d <= 32, "
               "16-B aligned rows of x / a / W1 / S_T)", F, Kc, H, P);
     return GCNK_EUNSUP;

@@ -60,11 +60,6 @@ struct Mat {
   }
 };
 
-__device__ __forceinline__ double inv_sqrt_degree(double s) {
-  const double p = pow(s, -0.5);
-  return isinf(p) ? 0.0 : p;
-}
-
 // tile[r * stride + k] = float32(theta[d0 + r, k]) where kept, else kDropped; returns the rows staged
 __device__ __forceinline__ int stage_tile(const Mat& theta, int32_t D, int32_t K, int32_t d0, double thr, float* tile,
                                           int stride) {
@@ -97,7 +92,7 @@ tg_count_kernel(Mat theta, int32_t D, int32_t K, double thr, int32_t* __restrict
       }
     }
     counts[d0 + t] = n;
-    d[d0 + t] = inv_sqrt_degree(s);
+    d[d0 + t] = ahat_inv_sqrt_degree(s);
   }
   const int wv = t >> 6, lane = t & 63;
   const int r0 = wv * kSegment, r1 = min(rows, r0 + kSegment);
@@ -234,7 +229,7 @@ tg_degree_kernel(int32_t D, const int32_t* __restrict__ rowptr, const float* __r
       for (int j = 0; j < 64; ++j) s += (double)__int_as_float(__builtin_amdgcn_readlane(__float_as_int(v[u]), j));
     }
   }
-  if (lane == 0) d[row] = inv_sqrt_degree(s);
+  if (lane == 0) d[row] = ahat_inv_sqrt_degree(s);
 }
 
 // Workgroups 0 .. ndocblk - 1: a thread per document row; then a workgroup per topic row.
@@ -245,13 +240,13 @@ tg_scale_kernel(int32_t D, int32_t ndocblk, const int32_t* __restrict__ rowptr, 
     const int32_t r = (int32_t)blockIdx.x * kThreads + (int32_t)threadIdx.x;
     if (r >= D) return;
     const double dr = d[r];
-    for (int32_t i = rowptr[r], e = rowptr[r + 1]; i < e; ++i) val[i] = (float)((dr * (double)val[i]) * d[colind[i]]);
+    for (int32_t i = rowptr[r], e = rowptr[r + 1]; i < e; ++i) val[i] = ahat_value(dr, (double)val[i], d[colind[i]]);
     return;
   }
   const int32_t r = D + ((int32_t)blockIdx.x - ndocblk);
   const double dr = d[r];
   for (int32_t i = rowptr[r] + (int32_t)threadIdx.x, e = rowptr[r + 1]; i < e; i += kThreads)
-    val[i] = (float)((dr * (double)val[i]) * d[colind[i]]);
+    val[i] = ahat_value(dr, (double)val[i], d[colind[i]]);
 }
 
 // A thread per pair i <= j: the dot product and both squared norms in one ascending walk.
@@ -394,14 +389,8 @@ extern "C" int gcnk_topic_graph_build(const void* theta, int32_t theta_f32, int6
   const int32_t N = D + K;
   const Mat th{theta, ldt, theta_f32}, sm{sim, lds, sim_f32};
   const int lds_b = kChunk * (K | 1) * (int)sizeof(float);
-  static std::atomic<uint64_t> done_count{0}, done_fill{0};
-  hipError_t attr = dyn_lds_attr(done_count, reinterpret_cast<const void*>(&tg_count_kernel), 160 * 1024);
-  if (attr == hipSuccess) attr = dyn_lds_attr(done_fill, reinterpret_cast<const void*>(&tg_fill_kernel), 160 * 1024);
-  if (attr != hipSuccess) return hip_check(attr, "topic graph LDS attribute");
-
-  hipLaunchKernelGGL(tg_count_kernel, dim3((unsigned)l.nchunk), dim3(kThreads), (size_t)lds_b, s, th, D, K,
-                     doc_topic_threshold, counts, d, segcnt);
-  int rc = launch_check("tg_count_kernel");
+  int rc = launch_big_lds<tg_count_kernel>("tg_count_kernel", dim3((unsigned)l.nchunk), dim3(kThreads), (size_t)lds_b,
+                                           stream, th, D, K, doc_topic_threshold, counts, d, segcnt);
   if (rc) return rc;
   hipLaunchKernelGGL(tg_columns_kernel, dim3(1), dim3(kMaxTopics), 0, s, sm, D, K, topic_topic_threshold, l.nseg,
                      segcnt, doccnt, counts, edges);
@@ -412,9 +401,9 @@ extern "C" int gcnk_topic_graph_build(const void* theta, int32_t theta_f32, int6
                  "topic graph scan");
   if (rc) return rc;
   const int32_t ntopblk = (K + kThreads / 64 - 1) / (kThreads / 64);
-  hipLaunchKernelGGL(tg_fill_kernel, dim3((unsigned)(l.nchunk + ntopblk)), dim3(kThreads), (size_t)lds_b, s, th, sm, D, K,
-                     doc_topic_threshold, topic_topic_threshold, l.nchunk, rowptr, segcnt, doccnt, colind, val);
-  rc = launch_check("tg_fill_kernel");
+  rc = launch_big_lds<tg_fill_kernel>("tg_fill_kernel", dim3((unsigned)(l.nchunk + ntopblk)), dim3(kThreads),
+                                      (size_t)lds_b, stream, th, sm, D, K, doc_topic_threshold, topic_topic_threshold,
+                                      l.nchunk, rowptr, segcnt, doccnt, colind, val);
   if (rc) return rc;
   hipLaunchKernelGGL(tg_degree_kernel, dim3((unsigned)K), dim3(64), 0, s, D, rowptr, val, d);
   rc = launch_check("tg_degree_kernel");

@@ -53,12 +53,13 @@ XHUB_DENSE = os.environ.get("GCNK_XHUB_DENSE", "1") != "0"
 XHUB_DENSE_FILL = 0.5
 XHUB_TRAIN_TILE = os.environ.get("GCNK_XHUB_TRAIN_TILE", "1") != "0"
 MAX_KC = 128      # X's light-row column range (U's width)
-ROWS_PER_BLOCK = 32   # csrc/factor.hip kRB
-# record words before the items: 33 row offsets | 3 pad | 32 row ids (-1 past
-# M) -- csrc/factor.hip kRecHead.  A block's rows are a slice of the row order
+# The block record of csrc/hub_block.h (kHubRows, kHubRecHead, kHubRecRow): 33
+# row offsets | 3 pad | 32 row ids (-1 past M), then the items.  A block's rows
+# are a slice of the row order
 # `perm` (hub rows spread evenly between the light rows, so no block carries
 # more than one or two hub rows' long item lists: the item loop is LDS-bound per
 # workgroup, and R8's contiguous topic rows made three blocks the kernel's tail).
+ROWS_PER_BLOCK = 32
 REC_HEAD = 68
 REC_ROW = 36
 

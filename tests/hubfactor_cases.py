@@ -15,17 +15,16 @@ route it names and that the table reaches every instantiation, both u_lds values
 per KS (0 by an ldu that is no multiple of 4 and by the LDS budget) and both
 sides of every cut, and on the GPU runs every case against float64.
 
-operands(): the construction of tests/test_hubfactor_items.py for any shape.
-Block record layout of csrc/factor.hip: 33 item offsets, 3 pad words, 32 output
-row ids with -1 past M, then int2 {hub, value} items; rec_words the common
-stride, a multiple of 4.
+operands(): the construction of tests/test_hubfactor_items.py for any shape;
+the block records are packed by tests/hub_records.py.
 """
 from typing import NamedTuple
 
 import numpy as np
 
+from hub_records import ROWS, pack, rec_words_for
+
 M = 70                       # three 32-row blocks, the last with 6 real rows
-ROWS, REC_ROW, REC_HEAD = 32, 36, 68
 COUNTS = [0, 1, 2, 3, 4, 5, 7, 8, 9, 16, 17, 0]   # ..., 17, 0, 0, 1, ... down a block
 LONG_POS, LONG_ITEMS = 32 + 13, 200               # the long row: middle block, followed by an empty row
 NAN_BITS = np.int32(0x7FC00000)
@@ -51,8 +50,7 @@ def item_counts():
 
 
 def rec_words():
-    per_block = item_counts().reshape(-1, ROWS).sum(1)
-    return (REC_HEAD + 2 * int(per_block.max()) + 3) // 4 * 4 + 4   # every record keeps a tail
+    return rec_words_for(item_counts(), tail=4)   # every record keeps a tail
 
 
 REC_WORDS = rec_words()
@@ -65,24 +63,11 @@ def operands(nhub, Kc, F, P, ldu):
     rng = np.random.default_rng(1000 * nhub + 10 * Kc + F + P)
     perm = rng.permutation(M)                      # position in block order -> output row
     assert not np.array_equal(perm, np.arange(M))
-    nblk = (M + ROWS - 1) // ROWS
     counts = item_counts()
     hubs = [rng.integers(0, nhub, c) for c in counts]             # repeated hubs allowed
     vals = [rng.uniform(-1.0, 1.0, c).astype(np.float32) for c in counts]
     words = rec_words()
-    rec = np.full((nblk, words), NAN_BITS, np.int32)
-    for b in range(nblk):
-        off = np.concatenate([[0], np.cumsum(counts[b * ROWS:(b + 1) * ROWS])])
-        rec[b, :ROWS + 1] = off
-        rec[b, ROWS + 1:REC_ROW] = 0
-        ids = np.full(ROWS, -1, np.int64)
-        real = min(ROWS, M - b * ROWS)
-        ids[:real] = perm[b * ROWS:b * ROWS + real]
-        rec[b, REC_ROW:REC_HEAD] = ids
-        h = np.concatenate(hubs[b * ROWS:(b + 1) * ROWS]).astype(np.int32)
-        v = np.concatenate(vals[b * ROWS:(b + 1) * ROWS]).astype(np.float32)
-        rec[b, REC_HEAD:REC_HEAD + 2 * len(h):2] = h
-        rec[b, REC_HEAD + 1:REC_HEAD + 2 * len(h):2] = v.view(np.int32)
+    rec = pack([list(zip(h, v)) for h, v in zip(hubs, vals)], perm, M, words, NAN_BITS)
     U = np.zeros((M, ldu), np.float32)
     U[:, :Kc] = rng.standard_normal((M, Kc)) * 0.3
     U[:, Kc:] = np.nan                             # columns past Kc are not the kernel's to read into Z

@@ -26,6 +26,8 @@ import torch
 import gcn_amd  # noqa: F401
 from graph_convolutional_networks_for_text_classification_amd import _lib
 
+from hub_records import REC_HEAD, ROWS, pack
+
 DEV = "cuda"
 gpu = pytest.mark.gpu
 SENT_F = np.float32(-12345.0)
@@ -385,7 +387,7 @@ def test_factor_xl(k0, Kc, Kcp):
 
 # ------------------------------------------------------------------------------ gcnk_factor_records
 
-REC_HEAD, REC_ROW, BLOCK = 68, 36, 32
+BLOCK = ROWS
 REC_SRC = 200                 # sources (columns); hubs: d % 3 == 0 and the sources around the long row's 64th
 BOUNDARY_HUBS = (72, 73, 74, 75, 136, 137, 138, 139)       # and 128th items (items 62 .. 65 and 126 .. 129)
 
@@ -425,24 +427,10 @@ def _records_problem(M, odd):
 
 
 def _records_reference(by_pos, hub_index, perm, M, rec_words):
-    nblk = (M + BLOCK - 1) // BLOCK
-    rec = np.zeros((nblk, rec_words), np.int32)
-    fits = []
-    for b in range(nblk):
-        items = []
-        off = [0]
-        for i in range(BLOCK):
-            p = b * BLOCK + i
-            rec[b, REC_ROW + i] = perm[p] if p < M else -1
-            if p < M:
-                items += [(hub_index[c], v) for c, v in by_pos[p] if hub_index[c] >= 0]
-            off.append(len(items))
-        rec[b, :BLOCK + 1] = off
-        n = min(len(items), (rec_words - REC_HEAD) // 2)
-        fits.append(n == len(items))
-        rec[b, REC_HEAD:REC_HEAD + 2 * n:2] = [h for h, _ in items[:n]]
-        rec[b, REC_HEAD + 1:REC_HEAD + 2 * n:2] = _bits(np.array([v for _, v in items[:n]], np.float32))
-    return rec, fits
+    """The records (unused tail zero) and, per block, whether its items all fit in rec_words."""
+    items = [[(hub_index[c], v) for c, v in row if hub_index[c] >= 0] for row in by_pos]
+    rec = pack(items, perm, M, rec_words, 0)
+    return rec, [2 * int(rec[b, BLOCK]) <= rec_words - REC_HEAD for b in range(len(rec))]
 
 
 def test_records_problems_hold_what_the_tests_are_about():

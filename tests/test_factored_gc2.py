@@ -2,8 +2,7 @@
 from the hub factor, on hand-built operands the analyzer would never produce,
 and the factor build's new operands on the R8 fixture.
 
-Operands are made by hand (block records of csrc/factor.hip: 33 item offsets, 3
-pad words, 32 row ids with -1 past M, int2 {hub index, value} items; diag and
+Operands are made by hand (block records packed by tests/hub_records.py; diag and
 the precede counts per position of the block order; the hub rows as a CSR), so
 the expected values are float64 sums of the same arrays and no row is left out.
 The bound is the one tests/test_gpu_parity.py applies to its F = 8 SpMM
@@ -35,8 +34,9 @@ import gcn_amd  # noqa: F401
 from graph_convolutional_networks_for_text_classification_amd import GCN, _lib, factor, ops
 from graph_convolutional_networks_for_text_classification_amd.sparse import as_csr, from_arrays
 
+from hub_records import REC_HEAD, ROWS, pack, rec_words_for
+
 DEV = "cuda"
-ROWS, REC_ROW, REC_HEAD = 32, 36, 68
 GUARD = 8
 NAN_BITS = np.int32(0x7FC00000)
 LOGIT_TOL = 1e-4            # tests/test_gpu_parity.py
@@ -113,20 +113,8 @@ def _structure(name):
             diag[p] = vals[r][isd][0] if isd.any() else 0.0
             pre[p] = int(np.sum(hubcol & (cols[r] < r)))
     counts = np.array([len(it) for it in items])
-    per_block = counts.reshape(nblk, ROWS).sum(1)
-    rec_words = (REC_HEAD + 2 * int(per_block.max()) + 3) // 4 * 4 + 4    # every record keeps a tail
-    rec = np.full((nblk, rec_words), NAN_BITS, np.int32)
-    for b in range(nblk):
-        rec[b, :ROWS + 1] = np.concatenate([[0], np.cumsum(counts[b * ROWS:(b + 1) * ROWS])])
-        rec[b, ROWS + 1:REC_ROW] = 0
-        ids = np.full(ROWS, -1, np.int64)
-        real = min(ROWS, M - b * ROWS)
-        ids[:real] = perm[b * ROWS:b * ROWS + real]
-        rec[b, REC_ROW:REC_HEAD] = ids
-        flat = [it for p in range(b * ROWS, (b + 1) * ROWS) for it in items[p]]
-        if flat:
-            rec[b, REC_HEAD:REC_HEAD + 2 * len(flat):2] = np.array([h for h, _ in flat], np.int32)
-            rec[b, REC_HEAD + 1:REC_HEAD + 2 * len(flat):2] = np.array([v for _, v in flat], np.float32).view(np.int32)
+    rec_words = rec_words_for(counts, tail=4)    # every record keeps a tail
+    rec = pack(items, perm, M, rec_words, NAN_BITS)
     hub_rp = np.concatenate([[0], np.cumsum([len(cols[r]) for r in hubs])]).astype(np.int32)
     hub_ci = np.concatenate([cols[r] for r in hubs] + [np.zeros(1, np.int64)]).astype(np.int32)   # (never empty)
     hub_val = np.concatenate([vals[r] for r in hubs] + [np.zeros(1, np.float32)]).astype(np.float32)

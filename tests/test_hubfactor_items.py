@@ -14,10 +14,9 @@ also take the three ways the kernel deals its MFMA n-tiles over the waves (all
 slots real or one short; some waves with no real tile).
 
 Operands are made by hand (tests/hubfactor_cases.py operands(), shared with
-tests/test_hubfactor_routes.py; block record layout of csrc/factor.hip: 33 item
-offsets, 3 pad words, 32 output row ids with -1 past M, then int2 {hub, value}
-items; rec_words the common stride, a multiple of 4), so the expected values
-come from the same arrays in float64 numpy and no row is left out.
+tests/test_hubfactor_routes.py; the block records packed by
+tests/hub_records.py), so the expected values come from the same arrays in
+float64 numpy and no row is left out.
 """
 import ctypes
 import os

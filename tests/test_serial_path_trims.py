@@ -22,6 +22,8 @@ import torch
 import gcn_amd  # noqa: F401
 from graph_convolutional_networks_for_text_classification_amd import _lib, gemm
 
+from hub_records import ROWS, pack, rec_words_for
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
@@ -163,16 +165,15 @@ def test_slab_reduce_strided_and_unaligned_c(slab_operands, s, epilogue):
 
 # ------------------------------------------------------------------ factored gc1 projection
 
-FM, ROWS, REC_ROW, REC_HEAD = 70, 32, 36, 68     # 70 rows: three 32-row blocks, the last with 6 real rows
+FM = 70                                          # 70 rows: three 32-row blocks, the last with 6 real rows
 NHUB, KC, K0 = 3, 50, 3
 GUARD = 8
 SENTINEL = -12345.0
 
 
 def _factor_operands(F, P):
-    """Hand-built operands in the block-record layout of csrc/factor.hip (33 item
-    offsets, 3 pad words, 32 output row ids with -1 past M, int2 {hub, value}
-    items), and H1, S2 in float64 from the same arrays."""
+    """Hand-built operands (block records: tests/hub_records.py), and H1, S2 in
+    float64 from the same arrays."""
     rng = np.random.default_rng(100 * F + P)
     M = FM
     perm = rng.permutation(M)
@@ -182,20 +183,8 @@ def _factor_operands(F, P):
     counts[5] = 40                                   # one long row
     hubs = [rng.integers(0, NHUB, c) for c in counts]
     vals = [rng.uniform(-1.0, 1.0, c).astype(np.float32) for c in counts]
-    per_block = counts.reshape(nblk, ROWS).sum(1)
-    rec_words = (REC_HEAD + 2 * int(per_block.max()) + 3) // 4 * 4 + 4
-    rec = np.full((nblk, rec_words), np.int32(0x7FC00000), np.int32)
-    for b in range(nblk):
-        rec[b, :ROWS + 1] = np.concatenate([[0], np.cumsum(counts[b * ROWS:(b + 1) * ROWS])])
-        rec[b, ROWS + 1:REC_ROW] = 0
-        ids = np.full(ROWS, -1, np.int64)
-        real = min(ROWS, M - b * ROWS)
-        ids[:real] = perm[b * ROWS:b * ROWS + real]
-        rec[b, REC_ROW:REC_HEAD] = ids
-        h = np.concatenate(hubs[b * ROWS:(b + 1) * ROWS]).astype(np.int32)
-        v = np.concatenate(vals[b * ROWS:(b + 1) * ROWS]).astype(np.float32)
-        rec[b, REC_HEAD:REC_HEAD + 2 * len(h):2] = h
-        rec[b, REC_HEAD + 1:REC_HEAD + 2 * len(h):2] = v.view(np.int32)
+    rec_words = rec_words_for(counts, tail=4)
+    rec = pack([list(zip(h, v)) for h, v in zip(hubs, vals)], perm, M, rec_words, np.int32(0x7FC00000))
     ldu = KC + 2                                     # a multiple of 4: U's rows staged in LDS
     U = np.full((M, ldu), np.nan, np.float32)
     U[:, :KC] = rng.standard_normal((M, KC)) * 0.3
