@@ -61,6 +61,16 @@ template <int POLICY = kBufPlain>
 __device__ __forceinline__ f64x2 buf_load_f64x2(__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff = 0) {
   return __builtin_bit_cast(f64x2, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, POLICY));
 }
+// (one double)
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+template <int POLICY = kBufPlain>
+__device__ __forceinline__ double buf_load_f64(__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff = 0) {
+  return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, (int)voff, (int)soff, POLICY));
+}
+template <int POLICY = kBufPlain>
+__device__ __forceinline__ void buf_store_f64(double v, __amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff = 0) {
+  __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), r, (int)voff, (int)soff, POLICY);
+}
 template <int POLICY = kBufPlain>
 __device__ __forceinline__ void buf_store_f32(float v, __amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff = 0) {
   __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), r, (int)voff, (int)soff, POLICY);

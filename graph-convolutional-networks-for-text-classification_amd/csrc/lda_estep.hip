@@ -29,6 +29,22 @@
 // most max_iter <= kMaxIter times (a NaN makes the stop test false and runs to the cap), a document's waves
 // stop independently.  A word id outside [0, V) is the caller's error and is not looked for; the table is
 // read through a buffer resource, so such an id reads another row or zeros, never outside the table.
+//
+// The model's fit (sklearn's batch variational EM, _lda.py _em_step(batch_update=True), which the reference
+// runs in topic_model.py:109-117) is three launches an EM iteration, all in this file:
+//     exp_dirichlet   beta = exp(psi(lambda) - psi(row sum)) into the transposed table (as for transform)
+//     fit E-step      the SAME update loop, instantiated a second time (kFit): it starts from a given gamma0
+//                     row instead of 1, and after the loop walks the document's chunks once more with the
+//                     final etheta: phi_w = sum_k etheta_k beta_kw + 2^-52, ratio[indptr[d] + w] = c_w / phi_w.
+//                     It writes etheta [B x K] and that ratio per stored nonzero (and gamma, iterations).
+//     M-step          lambda_kw = eta + S_kw beta_kw with S_kw = sum_d etheta_dk r_dw: ONE WAVE PER WORD, lane =
+//                     topic (lane and lane + 64), down the word's entries in ascending document order through
+//                     a word-major index (wptr, pos, doc) of the document-term matrix: s = s + etheta * r, the
+//                     product rounded and then added as np.outer and += do, never an FMA, never an atomic.
+//                     No word's chain is split: the order is the specification.  The chain's operands are
+//                     loaded kLoads values ahead of the dependent adds.
+// The M-step's loops run over [wptr[w], wptr[w + 1]) clamped to [0, nnz], nnz checked on the host; ratio and
+// etheta are read (and ratio written) through buffer resources, so a bad index reads zeros or writes nothing.
 #include "gcnk_common.h"
 
 #pragma clang fp contract(off)
@@ -97,6 +113,13 @@ struct EStep {
   float* a;
   int64_t lda;
   double threshold;
+  // the fit variant alone
+  const double* gamma0;
+  int64_t ldg0;
+  double* etheta;
+  int64_t lde;
+  double* ratio;
+  uint32_t ratio_bytes;
 };
 
 __device__ __forceinline__ double count_at(const EStep& p, int64_t i) {
@@ -128,6 +151,9 @@ __device__ __forceinline__ void stage_words(__amdgpu_buffer_rsrc_t table, uint32
   }
 }
 
+// kFit false: transform (gamma = 1 at the start; theta, gamma, iterations, the scorer's operands).
+// kFit true: the fit's E-step (gamma0 given; etheta, the ratio of every stored nonzero, gamma, iterations).
+template <bool kFit>
 __global__ void __launch_bounds__(64 * kDocs)
 lda_estep_kernel(EStep p) {
   extern __shared__ double lds[];
@@ -163,6 +189,18 @@ lda_estep_kernel(EStep p) {
   double g0 = 1.0, g1 = 1.0;
   double e0 = exp(psi(1.0) - psi((double)K)), e1 = e0;
   double total = (double)K;   // sum_k gamma_k, ascending
+  if constexpr (kFit) {
+    g0 = p.gamma0[(int64_t)d * p.ldg0 + r0];
+    g1 = p.gamma0[(int64_t)d * p.ldg0 + r1];
+    if (on0) gm[k0] = g0;
+    if (on1) gm[k1] = g1;
+    wave_sync();
+    total = 0.0;
+    for (int k = 0; k < K; ++k) total += gm[k];
+    const double psi_total = psi(total);
+    e0 = exp(psi(g0) - psi_total);
+    e1 = exp(psi(g1) - psi_total);
+  }
   if (on0) et[k0] = e0;
   if (on1) et[k1] = e1;
   if (nchunk == 1) {
@@ -170,6 +208,15 @@ lda_estep_kernel(EStep p) {
     stage_words(table, p.row_bytes, K, Ks, id, n, lane, tile);
   }
   wave_sync();
+
+  // phase 1, lane = word (a lane past the chunk's end computes on stale LDS and is not read): c_w / phi_w
+  auto ratio_of_lane = [&]() {
+    const double* mine = tile + lane * Ks;
+    double phi = 0.0;
+    for (int k = 0; k < K; ++k) phi = fma(et[k], mine[k], phi);
+    phi += kEps;
+    return cnt / phi;
+  };
 
   int32_t its = 0;
   for (int it = 0; it < p.max_iter; ++it) {
@@ -181,12 +228,7 @@ lda_estep_kernel(EStep p) {
         stage_words(table, p.row_bytes, K, Ks, id, m, lane, tile);
         wave_sync();
       }
-      // phase 1, lane = word (a lane past the chunk's end computes on stale LDS and is not read)
-      const double* mine = tile + lane * Ks;
-      double phi = 0.0;
-      for (int k = 0; k < K; ++k) phi = fma(et[k], mine[k], phi);
-      phi += kEps;
-      rr[lane] = cnt / phi;
+      rr[lane] = ratio_of_lane();
       wave_sync();
       // phase 2, lane = topic
       if (two) {
@@ -226,6 +268,30 @@ lda_estep_kernel(EStep p) {
     wave_sync();
     ++its;
     if (__builtin_amdgcn_readfirstlane((int)(change / (double)K < p.tol))) break;
+  }
+
+  if constexpr (kFit) {
+    // once more with the final etheta (in LDS since the last update, or the start): every stored nonzero's ratio
+    const __amdgpu_buffer_rsrc_t ratio = buffer_rsrc(p.ratio, p.ratio_bytes);
+    for (int c = 0; c < nchunk; ++c) {
+      const int m = min(kTile, n - c * kTile);
+      if (nchunk > 1) {
+        load_words(c);
+        stage_words(table, p.row_bytes, K, Ks, id, m, lane, tile);
+        wave_sync();
+      }
+      const double r = ratio_of_lane();
+      buf_store_f64(r, ratio, lane < m ? (uint32_t)(b + c * kTile + lane) * 8u : kBufOob);
+      wave_sync();   // (the next chunk rewrites tile)
+    }
+    if (on0) p.etheta[(int64_t)d * p.lde + k0] = e0;
+    if (on1) p.etheta[(int64_t)d * p.lde + k1] = e1;
+    if (p.gamma) {
+      if (on0) p.gamma[(int64_t)d * p.ldth + k0] = g0;
+      if (on1) p.gamma[(int64_t)d * p.ldth + k1] = g1;
+    }
+    if (p.iters && lane == 0) p.iters[d] = its;
+    return;
   }
 
   const double t0 = g0 / total, t1 = g1 / total;
@@ -298,6 +364,101 @@ lda_transpose_kernel(const double* __restrict__ src, int64_t lde, int32_t K, int
   if (i >= (int64_t)K * V) return;
   const int32_t w = (int32_t)(i / K), k = (int32_t)(i - (int64_t)w * K);
   table[(int64_t)w * ldt + k] = src[(int64_t)k * lde + w];
+}
+
+struct MStep {
+  const int32_t* wptr;
+  const int32_t* pos;
+  const int32_t* doc;
+  int64_t nnz;
+  int32_t V, K;
+  const double* ratio;
+  uint32_t ratio_bytes;
+  const double* etheta;
+  uint32_t et_row_bytes, et_bytes;
+  const double* table;
+  int64_t ldt;
+  double eta;
+  double* lambda;
+  int64_t ldl;
+};
+
+constexpr int kWords = 4;    // words (waves) per workgroup
+constexpr int kLoads = 32;   // etheta loads a wave keeps in flight ahead of its add chain (64 VGPRs)
+
+// lambda[k, w] = eta + (sum over the word's entries, ascending document, of etheta[doc, k] * ratio[pos]) * beta[k, w].
+// A wave takes 64 entries' (doc, ratio) a load, lane = entry, the next 64 while it works on these.  Then, lane =
+// topic, the etheta values of the next R entries sit in a ring of R registers (R = kLoads with one topic a lane,
+// kLoads / 2 with two): the wave adds the entry in slot u and at once loads the entry R further on into that
+// slot, from the next 64 when it lies there, so R entries' loads are in flight all the way down the chain.
+template <bool kTwo>
+__global__ void __launch_bounds__(64 * kWords)
+lda_mstep_kernel(MStep p) {
+  constexpr int R = kTwo ? kLoads / 2 : kLoads;
+  static_assert(64 % R == 0 && 64 / R >= 2, "a ring refilled from the next 64 entries in the last group of these");
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int32_t w = (int32_t)blockIdx.x * kWords + wv;
+  if (w >= p.V) return;
+  const int K = p.K;
+  const int k0 = lane, k1 = lane + 64;
+  const bool on0 = k0 < K, on1 = kTwo && k1 < K;
+  const __amdgpu_buffer_rsrc_t ratio = buffer_rsrc(p.ratio, p.ratio_bytes);
+  const __amdgpu_buffer_rsrc_t et = buffer_rsrc(p.etheta, p.et_bytes);
+  const int64_t b = max((int64_t)p.wptr[w], (int64_t)0);
+  const int64_t e = min((int64_t)p.wptr[w + 1], p.nnz);
+
+  int32_t dd = 0, ddn = 0;
+  double rr = 0.0, rrn = 0.0;
+  auto load_entries = [&](int64_t i0, int32_t& d_out, double& r_out) {   // lane = entry
+    const bool live = i0 + lane < e;
+    d_out = live ? p.doc[i0 + lane] : 0;
+    r_out = buf_load_f64(ratio, live ? (uint32_t)p.pos[i0 + lane] * 8u : kBufOob);
+  };
+  double a0[R], a1[R];
+  // slot u <- etheta[document held by lane l of d, this lane's topics] (nothing is read for a dead entry)
+  auto fetch = [&](int u, int32_t d, int l, bool live) {
+    const uint32_t row = (uint32_t)__builtin_amdgcn_readlane(d, l) * p.et_row_bytes;
+    a0[u] = buf_load_f64(et, live && on0 ? row + 8u * (uint32_t)k0 : kBufOob);
+    if (kTwo) a1[u] = buf_load_f64(et, live && on1 ? row + 8u * (uint32_t)k1 : kBufOob);
+  };
+
+  double s0 = 0.0, s1 = 0.0;
+  load_entries(b, dd, rr);
+  {
+    const int m = (int)min((int64_t)64, e - b);
+#pragma unroll
+    for (int u = 0; u < R; ++u) fetch(u, dd, u, u < m);
+  }
+  for (int64_t i0 = b; i0 < e; i0 += 64) {
+    const int m = (int)min((int64_t)64, e - i0);                       // entries here: 1 .. 64
+    const int mn = (int)min((int64_t)64, e - i0 - m);                  // and in the next 64: 0 unless m == 64
+    load_entries(i0 + 64, ddn, rrn);
+    for (int u0 = 0; u0 < m; u0 += R) {
+      const bool wrap = u0 + R >= 64;   // the entries R further on are the next 64's first R
+#pragma unroll
+      for (int u = 0; u < R; ++u) {
+        const int j = u0 + u;
+        if (j < m) {
+          const double r = readlane_f64(rr, j);
+          const double q0 = a0[u] * r;   // (rounded, then added: contraction is off in this file)
+          s0 = s0 + q0;
+          if (kTwo) {
+            const double q1 = a1[u] * r;
+            s1 = s1 + q1;
+          }
+        }
+        const int l = (j + R) & 63;
+        fetch(u, wrap ? ddn : dd, l, wrap ? l < mn : j + R < m);
+      }
+    }
+    dd = ddn;
+    rr = rrn;
+  }
+
+  const double* beta = p.table + (int64_t)w * p.ldt;
+  if (on0) p.lambda[(int64_t)k0 * p.ldl + w] = p.eta + s0 * beta[k0];
+  if (on1) p.lambda[(int64_t)k1 * p.ldl + w] = p.eta + s1 * beta[k1];
 }
 
 // K in range, the table's rows 16-byte accesses, every byte offset into it below kBufOob
@@ -396,7 +557,7 @@ extern "C" int gcnk_lda_estep_f64(const int32_t* indptr, const int32_t* indices,
               (long long)ldth, (long long)ldx, (long long)lda);
     return GCNK_EARG;
   }
-  EStep p;
+  EStep p{};
   p.indptr = indptr;
   p.indices = indices;
   p.counts = counts;
@@ -420,5 +581,122 @@ extern "C" int gcnk_lda_estep_f64(const int32_t* indptr, const int32_t* indices,
   p.threshold = threshold;
   const int lds_bytes = kDocs * wave_doubles(K) * (int)sizeof(double);
   const unsigned nblk = (unsigned)(((int64_t)B + kDocs - 1) / kDocs);
-  return launch_big_lds<lda_estep_kernel>("lda_estep_kernel", dim3(nblk), dim3(64 * kDocs), (size_t)lds_bytes, stream, p);
+  return launch_big_lds<lda_estep_kernel<false>>("lda_estep_kernel", dim3(nblk), dim3(64 * kDocs), (size_t)lds_bytes,
+                                                 stream, p);
+}
+
+extern "C" int32_t gcnk_lda_words_per_block(void) { return kWords; }
+
+extern "C" int gcnk_lda_estep_fit_f64(const int32_t* indptr, const int32_t* indices, const void* counts,
+                                      int32_t counts_kind, int32_t B, int32_t V, int32_t K, const double* table,
+                                      int64_t ldt, double alpha, double tol, int32_t max_iter, const double* gamma0,
+                                      int64_t ldg0, int64_t nnz, double* ratio, double* etheta, int64_t lde,
+                                      double* gamma, int64_t ldg, int32_t* iters, void* stream) {
+  const char* who = "gcnk_lda_estep_fit_f64";
+  const int rc = check_table(who, K, V, table, ldt);
+  if (rc) return rc;
+  if (B < 1 || !indptr || !indices || !counts) {
+    set_error("%s: needs B >= 1 and non-null indptr, indices and counts (B=%d)", who, B);
+    return GCNK_EARG;
+  }
+  if (counts_kind < 0 || counts_kind > 2) {
+    set_error("%s: counts_kind %d is not 0 (float64), 1 (int32) or 2 (int64)", who, counts_kind);
+    return GCNK_EARG;
+  }
+  if (max_iter < 0 || max_iter > kMaxIter) {
+    set_error("%s: max_iter=%d is outside [0, %d]", who, max_iter, kMaxIter);
+    return GCNK_EARG;
+  }
+  if (!gamma0 || !ratio || !etheta) {
+    set_error("%s: gamma0, ratio and etheta must be non-null", who);
+    return GCNK_EARG;
+  }
+  if (ldg0 < K || lde < K || (gamma && ldg < K)) {
+    set_error("%s: a leading dimension is shorter than K=%d (ldg0=%lld lde=%lld ldg=%lld)", who, K, (long long)ldg0,
+              (long long)lde, (long long)ldg);
+    return GCNK_EARG;
+  }
+  if (nnz < 0) {
+    set_error("%s: nnz=%lld is negative", who, (long long)nnz);
+    return GCNK_EARG;
+  }
+  if (nnz * 8 >= (int64_t)kBufOob) {
+    set_error("%s: %lld ratios are past the 32-bit offsets of their buffer resource", who, (long long)nnz);
+    return GCNK_EUNSUP;
+  }
+  EStep p{};
+  p.indptr = indptr;
+  p.indices = indices;
+  p.counts = counts;
+  p.counts_kind = counts_kind;
+  p.B = B;
+  p.K = K;
+  p.table = table;
+  p.row_bytes = (uint32_t)(ldt * 8);
+  p.table_bytes = (uint32_t)((int64_t)V * ldt * 8);
+  p.alpha = alpha;
+  p.tol = tol;
+  p.max_iter = max_iter;
+  p.gamma = gamma;
+  p.ldth = ldg;
+  p.iters = iters;
+  p.gamma0 = gamma0;
+  p.ldg0 = ldg0;
+  p.etheta = etheta;
+  p.lde = lde;
+  p.ratio = ratio;
+  p.ratio_bytes = (uint32_t)(nnz * 8);
+  const int lds_bytes = kDocs * wave_doubles(K) * (int)sizeof(double);
+  const unsigned nblk = (unsigned)(((int64_t)B + kDocs - 1) / kDocs);
+  return launch_big_lds<lda_estep_kernel<true>>("lda_estep_fit_kernel", dim3(nblk), dim3(64 * kDocs), (size_t)lds_bytes,
+                                                stream, p);
+}
+
+extern "C" int gcnk_lda_mstep_f64(const int32_t* wptr, const int32_t* pos, const int32_t* doc, int64_t nnz,
+                                  const double* ratio, const double* etheta, int64_t lde, int32_t B, int32_t V,
+                                  int32_t K, const double* table, int64_t ldt, double eta, double* lambda, int64_t ldl,
+                                  void* stream) {
+  const char* who = "gcnk_lda_mstep_f64";
+  const int rc = check_table(who, K, V, table, ldt);
+  if (rc) return rc;
+  if (B < 1 || !wptr || !pos || !doc || !ratio || !etheta || !lambda) {
+    set_error("%s: needs B >= 1 and non-null wptr, pos, doc, ratio, etheta and lambda (B=%d)", who, B);
+    return GCNK_EARG;
+  }
+  if (lde < K || ldl < V) {
+    set_error("%s: lde=%lld < K=%d or ldl=%lld < V=%d", who, (long long)lde, K, (long long)ldl, V);
+    return GCNK_EARG;
+  }
+  if (nnz < 0) {
+    set_error("%s: nnz=%lld is negative", who, (long long)nnz);
+    return GCNK_EARG;
+  }
+  if (nnz * 8 >= (int64_t)kBufOob || (int64_t)B * lde * 8 >= (int64_t)kBufOob) {
+    set_error("%s: %lld ratios or an etheta of %lld bytes are past the 32-bit offsets of their buffer resources", who,
+              (long long)nnz, (long long)((int64_t)B * lde * 8));
+    return GCNK_EUNSUP;
+  }
+  MStep p{};
+  p.wptr = wptr;
+  p.pos = pos;
+  p.doc = doc;
+  p.nnz = nnz;
+  p.V = V;
+  p.K = K;
+  p.ratio = ratio;
+  p.ratio_bytes = (uint32_t)(nnz * 8);
+  p.etheta = etheta;
+  p.et_row_bytes = (uint32_t)(lde * 8);
+  p.et_bytes = (uint32_t)((int64_t)B * lde * 8);
+  p.table = table;
+  p.ldt = ldt;
+  p.eta = eta;
+  p.lambda = lambda;
+  p.ldl = ldl;
+  const unsigned nblk = (unsigned)(((int64_t)V + kWords - 1) / kWords);
+  if (K > 64)
+    hipLaunchKernelGGL(lda_mstep_kernel<true>, dim3(nblk), dim3(64 * kWords), 0, (hipStream_t)stream, p);
+  else
+    hipLaunchKernelGGL(lda_mstep_kernel<false>, dim3(nblk), dim3(64 * kWords), 0, (hipStream_t)stream, p);
+  return launch_check("lda_mstep_kernel");
 }

@@ -24,6 +24,7 @@
  *   build_graph.py:99-133 theta, topic similarities -> graph   -> gcnk_topic_graph_build (device, straight to A-hat)
  *   build_graph.py:118 cosine_similarity(topic_embeddings)     -> gcnk_topic_cosine_f64
  *   topic_model.py:133-164 LatentDirichletAllocation.transform -> gcnk_lda_estep_f64 (device, a wave per document)
+ *   topic_model.py:74-131  LatentDirichletAllocation.fit (batch) -> gcnk_lda_estep_fit_f64 + gcnk_lda_mstep_f64
  *   layer.py:185 th.dropout keep-mask draw (CPU generator)    -> gcnk_bernoulli_mt19937 (host, same stream)
  *   trainer.py:307, 358-361, 383-384 CrossEntropyLoss on logits[idx] -> gcnk_ce_forward_f32 / gcnk_ce_backward_f32
  *   trainer.py:308, 359, 362 th.optim.Adam step (and zero_grad)   -> gcnk_adam_f32 (one launch per 8 tensors)
@@ -61,7 +62,7 @@ extern "C" {
  * gcnk_gcn_bwd2_route / gcnk_hubfactor_gc1_route / gcnk_spmm_route and held-graph scoring,
  * gcnk_score_docs_f32 / gcnk_score_docs_route, and the graph built on the
  * device, gcnk_topic_graph_* / gcnk_topic_cosine_f64, and the topic mixtures
- * inferred on the device, gcnk_lda_* (additions only: no existing
+ * inferred and the topic model fitted on the device, gcnk_lda_* (additions only: no existing
  * symbol, field offset or meaning changed, so the number stayed). */
 #define GCNK_ABI_VERSION 13
 
@@ -1075,6 +1076,50 @@ int gcnk_lda_estep_f64(const int32_t* indptr, const int32_t* indices, const void
                        int32_t B, int32_t V, int32_t K, const double* table, int64_t ldt, double alpha, double tol,
                        int32_t max_iter, double* theta, int64_t ldth, double* gamma, int32_t* iters, float* x,
                        int64_t ldx, float* a, int64_t lda, double threshold, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * The topic model fitted on the device (csrc/lda_estep.hip; additions within
+ * ABI 13): sklearn's batch variational EM behind topic_model.py:74-131,
+ * LatentDirichletAllocation.fit with learning_method='batch' (_lda.py
+ * _em_step(batch_update=True)), all float64.  One EM iteration is three
+ * launches on one stream, none of which synchronises:
+ *   gcnk_lda_exp_dirichlet_f64   the table from lambda (above)
+ *   gcnk_lda_estep_fit_f64       the update loop of gcnk_lda_estep_f64, the same
+ *       device code instantiated a second time, started from gamma0 [B x ldg0]
+ *       (sklearn's fresh Gamma(100, .01) draw of every EM iteration) instead of
+ *       1: etheta_k = exp(psi(gamma0_k) - psi(sum_k gamma0_k)), the sum ascending.
+ *       After the loop it walks the document's words once more with the final
+ *       etheta: ratio[indptr[d] + w] = c_w / (sum_k etheta_k table[id_w, k] +
+ *       2^-52), one per stored nonzero in CSR order (nnz of them), and stores
+ *       etheta [B x lde]; gamma [B x ldg] and iters int32 [B] are nullable.
+ *   gcnk_lda_mstep_f64           lambda[k * ldl + w] = eta + S_kw * table[w, k],
+ *       S_kw = sum over the documents d that hold w, ASCENDING d, of
+ *       etheta[d, k] * ratio[its entry]: the product rounded, then added (as
+ *       np.outer and += do; no fma, no atomics), one wave per word and no word's
+ *       chain split, so lambda is bit for bit that serial loop.  The word-major
+ *       index of the document-term matrix: wptr int32 [V + 1] (word w's entries
+ *       are [wptr[w], wptr[w + 1])), pos int32 [nnz] (an entry's position in CSR
+ *       order, so in ratio) and doc int32 [nnz] (its document), a word's entries
+ *       in ascending document order (a stable sort of indices).  A word no
+ *       document holds gets exactly eta.
+ * The M-step's chain runs over [wptr[w], wptr[w + 1]) clamped to [0, nnz]; ratio
+ * and etheta are accessed through bounds-checked buffer resources (a bad pos or
+ * doc reads zeros, a bad indptr stores nothing outside ratio).
+ * GCNK_EARG: B < 1, K < 1, V < 1, a null pointer (gamma and iters excepted), a
+ * bad table, counts_kind outside 0..2, max_iter outside [0, 10000], a leading
+ * dimension below K (ldl below V), nnz < 0.  GCNK_EUNSUP: K > 128, a table, nnz
+ * ratios or an etheta of B * lde doubles past 32-bit byte offsets (2^31 - 2^20).
+ * Every refusal comes before any HIP call.  gcnk_lda_words_per_block(): the
+ * M-step's waves per workgroup (4).
+ * ------------------------------------------------------------------------- */
+int32_t gcnk_lda_words_per_block(void);
+int gcnk_lda_estep_fit_f64(const int32_t* indptr, const int32_t* indices, const void* counts, int32_t counts_kind,
+                           int32_t B, int32_t V, int32_t K, const double* table, int64_t ldt, double alpha, double tol,
+                           int32_t max_iter, const double* gamma0, int64_t ldg0, int64_t nnz, double* ratio,
+                           double* etheta, int64_t lde, double* gamma, int64_t ldg, int32_t* iters, void* stream);
+int gcnk_lda_mstep_f64(const int32_t* wptr, const int32_t* pos, const int32_t* doc, int64_t nnz, const double* ratio,
+                       const double* etheta, int64_t lde, int32_t B, int32_t V, int32_t K, const double* table,
+                       int64_t ldt, double eta, double* lambda, int64_t ldl, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Dropout keep-mask exactly as the reference's CPU th.dropout draws it

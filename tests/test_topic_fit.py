@@ -1,0 +1,260 @@
+"""fit_topics on the GPU (csrc/lda_estep.hip: the fit E-step, the M-step and their loop) against the float64
+numpy restatement tests/lda_fit_ref.py, itself pinned on the CPU (test_lda_fit_ref.py) to the reference's
+fit and to sklearn.  Expected values never come from the code under test.
+
+  fit E-step  update counts EQUAL on every document; gamma, etheta and ratio within lda_fit_cases.bound; a
+              document's outputs bit for bit independent of the batch.
+  M-step      on the restatement's own inputs, lambda BIT FOR BIT the restatement's: every operation is a
+              correctly rounded multiply or add in a fixed order.
+  whole fit   on the R8 fixture: update counts equal in all EM iterations, lambda within 16 max(d_ref, d_perm)
+              of the reference's components_; the host draw, a second run and a hipGraph replay bit for bit.
+"""
+import numpy as np
+import pytest
+import torch
+
+import gcn_amd  # noqa: F401
+from graph_convolutional_networks_for_text_classification_amd import TopicInferencer, _lib, fit_topics, topic_fit
+
+import lda_fit_cases
+import lda_fit_ref
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+
+
+def _dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+
+
+def _bits(t):
+    return t.contiguous().view(torch.int64 if t.dtype == torch.float64 else torch.int32)
+
+
+def _table(beta):
+    """exp(E[log beta]) [K x V] as the kernels read it: transposed, rows padded to an even length."""
+    K, V = beta.shape
+    t = torch.zeros((V, (K + 1) // 2 * 2), dtype=torch.float64, device=DEV)
+    t[:, :K] = _dev(beta).t()
+    return t
+
+
+def _estep_fit(c, indptr=None, indices=None, counts=None, gamma0=None):
+    """gcnk_lda_estep_fit_f64 alone on case c (or on the batch given) -> gamma, etheta, ratio, iters."""
+    indptr = c["indptr"] if indptr is None else indptr
+    indices = c["indices"] if indices is None else indices
+    counts = c["counts"] if counts is None else counts
+    gamma0 = c["gamma0"] if gamma0 is None else gamma0
+    B, K, V, nnz = len(indptr) - 1, c["K"], c["V"], len(indices)
+    table = _table(c["beta"])
+    ip, g0 = _dev(indptr), _dev(gamma0)
+    ix = _dev(indices) if nnz else torch.zeros(1, dtype=torch.int32, device=DEV)
+    ct = _dev(counts) if nnz else torch.zeros(1, dtype=torch.float64, device=DEV)
+    gamma = torch.full((B, K), -1.0, dtype=torch.float64, device=DEV)
+    etheta = torch.full((B, K), -1.0, dtype=torch.float64, device=DEV)
+    ratio = torch.full((max(nnz, 1) + 2,), -1.0, dtype=torch.float64, device=DEV)   # (two guard entries)
+    iters = torch.full((B,), -1, dtype=torch.int32, device=DEV)
+    rc = _lib.load().gcnk_lda_estep_fit_f64(ip.data_ptr(), ix.data_ptr(), ct.data_ptr(), 0, B, V, K, table.data_ptr(),
+                                            table.stride(0), c["alpha"], c["tol"], c["max_iter"], g0.data_ptr(), K, nnz,
+                                            ratio.data_ptr(), etheta.data_ptr(), K, gamma.data_ptr(), K,
+                                            iters.data_ptr(), _lib.stream(torch.device(DEV)))
+    _lib.check(rc, "gcnk_lda_estep_fit_f64")
+    assert float(ratio[nnz:].max()) == -1.0 == float(ratio[nnz:].min())   # nothing stored past the nnz ratios
+    return gamma, etheta, ratio[:nnz], iters
+
+
+_worst = {"estep": 0.0}
+
+
+@pytest.mark.parametrize("name", lda_fit_cases.ESTEP_NAMES)
+def test_estep_fit_case_table(name):
+    c = lda_fit_cases.estep_table()[name]
+    rg, re_, rr, ri, _ = lda_fit_cases.estep_reference(name)
+    gamma, etheta, ratio, iters = (t.cpu().numpy() for t in _estep_fit(c))
+    differ = np.flatnonzero(iters != ri)
+    assert differ.size == 0, f"{name}: documents {differ.tolist()} ran {iters[differ]} updates, not {ri[differ]}"
+    bound = lda_fit_cases.bound(ri)
+    frac = 0.0
+    for what, got, want in (("gamma", gamma, rg), ("etheta", etheta, re_)):
+        err = np.abs(got - want).max(1) / np.abs(want).max(1)
+        frac = max(frac, float((err / bound).max()))
+        print(f"{name}: {what}: worst document {int((err / bound).argmax())}: {float((err / bound).max()):.4f} of its bound")
+        assert (err <= bound).all(), (what, np.flatnonzero(~(err <= bound)).tolist(), (err / bound).max())
+    if rr.size:
+        per_entry = np.repeat(bound, np.diff(c["indptr"]))
+        err = np.abs(ratio - rr) / np.abs(rr)
+        frac = max(frac, float((err / per_entry).max()))
+        print(f"{name}: ratio: worst entry {float((err / per_entry).max()):.4f} of its bound")
+        assert (err <= per_entry).all(), ("ratio", float((err / per_entry).max()))
+    _worst["estep"] = max(_worst["estep"], frac)
+    print(f"{name}: largest fraction of the bound {frac:.4f}; over the cases so far {_worst['estep']:.4f}")
+    if c["max_iter"] == 0:
+        assert np.array_equal(gamma, c["gamma0"]) and not iters.any()
+
+
+@pytest.mark.parametrize("name", ["K50-lengths", "K128-lengths", "cap0"])
+def test_a_documents_fit_outputs_do_not_depend_on_the_batch(name):
+    c = lda_fit_cases.estep_table()[name]
+    B = len(c["indptr"]) - 1
+    whole = _estep_fit(c)
+    lengths = np.diff(c["indptr"])
+    longest = int(lengths.argmax())
+    orders = [list(range(B))[::-1], [longest] + list(range(B)) + [0], list(range(B)) * 2 + [longest] * 3]
+    orders += [[d] for d in range(B)]
+    for order in orders:
+        parts = [np.arange(c["indptr"][d], c["indptr"][d + 1]) for d in order]
+        sel = np.concatenate(parts).astype(np.int64)
+        indptr = np.concatenate([[0], np.cumsum([p.size for p in parts])]).astype(np.int32)
+        got = _estep_fit(c, indptr, c["indices"][sel], c["counts"][sel], c["gamma0"][order])
+        rows, ents = torch.tensor(order, device=DEV), torch.from_numpy(sel).to(DEV)
+        assert torch.equal(_bits(got[0]), _bits(whole[0][rows])) and torch.equal(_bits(got[1]), _bits(whole[1][rows]))
+        assert torch.equal(_bits(got[2]), _bits(whole[2][ents])) and torch.equal(got[3], whole[3][rows]), order
+
+
+def _mstep(c):
+    B, K, V, nnz = c["B"], c["K"], c["V"], len(c["indices"])
+    ix = topic_fit.word_index(_dev(c["indptr"]), _dev(c["indices"]), V)
+    if nnz == 0:
+        ix.pos = ix.doc = torch.zeros(1, dtype=torch.int32, device=DEV)
+    table, etheta = _table(c["beta"]), _dev(c["etheta"])
+    ratio = _dev(c["ratio"]) if nnz else torch.zeros(1, dtype=torch.float64, device=DEV)
+    lam = torch.full((K, V), -1.0, dtype=torch.float64, device=DEV)
+    rc = _lib.load().gcnk_lda_mstep_f64(ix.wptr.data_ptr(), ix.pos.data_ptr(), ix.doc.data_ptr(), nnz, ratio.data_ptr(),
+                                        etheta.data_ptr(), K, B, V, K, table.data_ptr(), table.stride(0), c["eta"],
+                                        lam.data_ptr(), V, _lib.stream(torch.device(DEV)))
+    _lib.check(rc, "gcnk_lda_mstep_f64")
+    return lam, ix
+
+
+@pytest.mark.parametrize("name", lda_fit_cases.MSTEP_NAMES)
+def test_mstep_is_bit_for_bit_the_serial_loop(name):
+    c = lda_fit_cases.mstep_table()[name]
+    want = lda_fit_cases.mstep_reference(name)
+    lam, ix = _mstep(c)
+    got = lam.cpu().numpy()
+    off = np.argwhere(got.view(np.int64) != want.view(np.int64))
+    assert off.size == 0, f"{name}: {len(off)} entries differ, first (k, w) = {off[0].tolist()}: {got[tuple(off[0])]!r} != {want[tuple(off[0])]!r}"
+    unheld = np.bincount(c["indices"], minlength=c["V"]) == 0
+    assert np.all(got[:, unheld] == c["eta"])
+    # the word-major index: a word's entries in ascending document order, each where the CSR has it
+    wptr, pos, doc = ix.wptr.cpu().numpy(), ix.pos.cpu().numpy(), ix.doc.cpu().numpy()
+    if len(c["indices"]):
+        assert wptr[0] == 0 and wptr[-1] == len(c["indices"]) and np.array_equal(np.diff(wptr), np.bincount(c["indices"], minlength=c["V"]))
+        assert np.array_equal(c["indices"][pos], np.repeat(np.arange(c["V"]), np.diff(wptr)))
+        assert np.all((c["indptr"][doc] <= pos) & (pos < c["indptr"][doc + 1]))
+        for w in range(c["V"]):
+            assert np.all(np.diff(doc[wptr[w]:wptr[w + 1]]) > 0)
+
+
+@pytest.fixture(scope="module")
+def golden():
+    return lda_fit_ref.load_golden()
+
+
+def _golden_fit(z, init=True, **kw):
+    docs = (_dev(z["indptr"]), _dev(z["indices"]), _dev(z["counts"]))
+    return fit_topics(*docs, int(z["V"]), num_topics=z["components_"].shape[0], max_iter=3,
+                      random_state=int(z["random_state"]), mean_change_tol=float(z["mean_change_tol"]),
+                      max_doc_update_iter=int(z["max_doc_update_iter"]),
+                      init=(_dev(z["lambda0"]), _dev(z["gamma0"])) if init else None, **kw), docs
+
+
+@pytest.fixture(scope="module")
+def fitted(golden):
+    return _golden_fit(golden, return_iterations=True)
+
+
+def test_whole_fit_against_the_reference(golden, fitted):
+    z, (fit, docs) = golden, fitted
+    K, V = z["components_"].shape
+    assert fit.components.device.type == "cuda" and tuple(fit.components.shape) == (K, V)
+    assert fit.doc_topic_prior == float(z["doc_topic_prior_"]) and fit.topic_word_prior == float(z["topic_word_prior_"])
+    its = fit.iterations.cpu().numpy()
+    assert its.dtype == np.int32 and its.shape == (3, 200)
+    differ = np.argwhere(its != z["iterations"])
+    assert differ.size == 0, f"(EM iteration, document) {differ.tolist()} ran {its[its != z['iterations']]} updates"
+    lam = fit.components.cpu().numpy()
+    bound = 16.0 * max(float(z["d_ref"]), float(z["d_perm"]))
+    d = lda_fit_ref.max_rel(lam, z["components_"])
+    d_rest = lda_fit_ref.max_rel(lam, lda_fit_cases.golden_fit()[0])
+    print(f"whole fit: max relative |lambda - reference components_| = {d:.3e} = {d / bound:.4f} of 16 max(d_ref, d_perm) "
+          f"= {bound:.3e}; to the restatement {d_rest:.3e}")
+    assert d <= bound
+    tw = fit.topic_word_distribution.cpu().numpy()
+    assert np.abs(tw.sum(1) - 1).max() <= 1e-12
+    # lambda_kw / sum_w lambda_kw: the numerator within `bound`, the sum of V positive terms within `bound` and
+    # its own V roundings in whatever order, one division
+    assert lda_fit_ref.max_rel(tw, z["topic_word_distribution"]) <= 2 * bound + (V + 1) * 2.0 ** -52
+    # the last table is exp_dirichlet of the fitted lambda
+    want = lda_fit_ref.exp_dirichlet(lam)
+    assert lda_fit_ref.max_rel(fit.exp_topic_word.cpu().numpy(), want) <= 8 * 2.0 ** -52 + V * 2.0 ** -53
+
+
+def test_host_draw_second_run_and_replay_are_bit_for_bit(golden, fitted):
+    z, (fit, docs) = golden, fitted
+    drawn, _ = _golden_fit(z, init=False)                      # RandomState(42) on the host, uploaded
+    assert drawn.iterations is None
+    assert torch.equal(_bits(drawn.components), _bits(fit.components))
+    again, _ = _golden_fit(z, return_iterations=True)
+    assert torch.equal(_bits(again.components), _bits(fit.components)) and torch.equal(again.iterations, fit.iterations)
+    assert torch.equal(_bits(again.topic_word_distribution), _bits(fit.topic_word_distribution))
+    init = (_dev(z["lambda0"]), _dev(z["gamma0"]))
+    args = dict(num_topics=8, max_iter=3, mean_change_tol=float(z["mean_change_tol"]),
+                max_doc_update_iter=int(z["max_doc_update_iter"]), init=init, return_iterations=True)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):                                  # a single chain on one stream
+        cap = fit_topics(*docs, int(z["V"]), **args)
+    g.replay()
+    torch.cuda.synchronize()
+    assert torch.equal(_bits(cap.components), _bits(fit.components)) and torch.equal(cap.iterations, fit.iterations)
+    assert torch.equal(_bits(cap.topic_word_distribution), _bits(fit.topic_word_distribution))
+    del g
+
+
+def test_inferencer_is_from_components_of_the_fit(golden, fitted):
+    z, (fit, docs) = golden, fitted
+    inf = fit.inferencer()
+    other = TopicInferencer.from_components(fit.components, fit.doc_topic_prior, fit.mean_change_tol,
+                                            fit.max_doc_update_iter)
+    theta = inf(*docs)
+    assert tuple(theta.shape) == (200, 8) and torch.equal(_bits(theta), _bits(other(*docs)))
+    assert torch.equal(_bits(inf.exp_topic_word), _bits(fit.exp_topic_word))
+
+
+def test_fit_of_documents_without_a_word_is_the_prior():
+    """No stored nonzero at all: S = 0, so lambda = eta exactly after any number of EM iterations, and every
+    document stops where the restatement does."""
+    B, V, K = 3, 7, 5
+    ip = torch.zeros(B + 1, dtype=torch.int32, device=DEV)
+    ix = torch.zeros(0, dtype=torch.int32, device=DEV)
+    ct = torch.zeros(0, dtype=torch.float64, device=DEV)
+    fit = fit_topics(ip, ix, ct, V, num_topics=K, max_iter=2, random_state=3, topic_word_prior=0.3, return_iterations=True)
+    assert torch.equal(fit.components, torch.full((K, V), 0.3, dtype=torch.float64, device=DEV))
+    lam0, g0s = lda_fit_ref.draws(3, K, V, B, 2)
+    lam, iters, _ = lda_fit_ref.fit(np.zeros(B + 1, np.int32), np.zeros(0, np.int32), np.zeros(0), lam0, g0s, 1.0 / K, 0.3)
+    assert np.all(lam == 0.3) and np.array_equal(fit.iterations.cpu().numpy(), iters)
+    assert float((fit.topic_word_distribution.sum(1) - 1).abs().max()) <= 1e-12
+
+
+def test_python_refusals(golden):
+    z = golden
+    ip, ix, ct = _dev(z["indptr"]), _dev(z["indices"]), _dev(z["counts"])
+    V, lam0, g0 = int(z["V"]), _dev(z["lambda0"]), _dev(z["gamma0"])
+    kw = dict(num_topics=8, max_iter=3)
+    for bad in ((lam0[:, :-1], g0), (lam0, g0[:2]), (lam0, g0[:, :-1]), (lam0.to(torch.float32), g0), (lam0.cpu(), g0),
+                (lam0, g0.cpu()), (lam0,), lam0):
+        with pytest.raises(RuntimeError):
+            fit_topics(ip, ix, ct, V, init=bad, **kw)
+    with pytest.raises(RuntimeError, match="float32 E-step"):
+        fit_topics(ip, ix, ct.to(torch.float32), V, **kw)
+    with pytest.raises(RuntimeError, match="ROCm GPU"):
+        fit_topics(ip.cpu(), ix, ct, V, **kw)
+    with pytest.raises(RuntimeError):
+        fit_topics(ip.to(torch.int64), ix, ct, V, **kw)
+    with pytest.raises(RuntimeError, match="num_topics=129"):
+        fit_topics(ip, ix, ct, V, num_topics=129)
+    with pytest.raises(RuntimeError, match="max_iter"):
+        fit_topics(ip, ix, ct, V, num_topics=8, max_iter=0)
+    with pytest.raises(RuntimeError, match="V >= 1"):
+        fit_topics(ip, ix, ct, 0, **kw)
