@@ -293,6 +293,12 @@ SIGNATURES = {
         _vp, _vp, _i64,                     # ratio, etheta, lde
         _i32, _i32, _i32, _vp, _i64,        # B, V, K, table, ldt
         _f64, _vp, _i64, _vp]),             # eta, lambda, ldl, stream
+    "gcnk_lda_mstep_online_f64": (ctypes.c_int, [
+        _vp, _vp, _vp, _i64, _i32, _i32,    # wptr, pos, doc, nnz, doc_lo, doc_hi
+        _vp, _vp, _i64,                     # ratio, etheta, lde
+        _i32, _i32, _i32, _vp, _i64,        # B, V, K, table, ldt
+        _f64, _f64, _f64,                   # eta, rho, doc_ratio
+        _vp, _i64, _vp]),                   # lambda (in place), ldl, stream
     "gcnk_csr_transpose_workspace_bytes": (_i64, [_i32, _i32, _i64]),
     "gcnk_coo_to_csr_workspace_bytes": (_i64, [_i64, _i32, _i32]),
     "gcnk_coo_to_csr": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
@@ -308,7 +314,7 @@ NEWER_THAN_SOME_VARIANTS = ("gcnk_hubfactor_gc2_f32", "gcnk_factor_diag_f32", "g
                             "gcnk_topic_graph_build", "gcnk_topic_cosine_f64", "gcnk_lda_max_topics",
                             "gcnk_lda_tile_words", "gcnk_lda_docs_per_block", "gcnk_lda_exp_dirichlet_f64",
                             "gcnk_lda_table_from_exp_f64", "gcnk_lda_estep_f64", "gcnk_lda_words_per_block",
-                            "gcnk_lda_estep_fit_f64", "gcnk_lda_mstep_f64")
+                            "gcnk_lda_estep_fit_f64", "gcnk_lda_mstep_f64", "gcnk_lda_mstep_online_f64")
 
 _lock = threading.Lock()
 _lib = None

@@ -43,6 +43,11 @@
 //                     product rounded and then added as np.outer and += do, never an FMA, never an atomic.
 //                     No word's chain is split: the order is the specification.  The chain's operands are
 //                     loaded kLoads values ahead of the dependent adds.
+// The online fit (_em_step(batch_update=False), learning_method='online' and partial_fit) runs the same three
+// launches once per MINIBATCH of documents [doc_lo, doc_hi): the fit E-step on that row range, then
+//     online M-step   lambda_kw = lambda_kw (1 - rho) + rho (eta + doc_ratio (S_kw beta_kw)), in place, S_kw the same
+//                     chain over the word's entries whose document is in the minibatch: a contiguous sub-range of
+//                     the whole matrix's index (entries ascend in document), found by two lower-bound searches.
 // The M-step's loops run over [wptr[w], wptr[w + 1]) clamped to [0, nnz], nnz checked on the host; ratio and
 // etheta are read (and ratio written) through buffer resources, so a bad index reads zeros or writes nothing.
 #include "gcnk_common.h"
@@ -386,27 +391,22 @@ struct MStep {
 constexpr int kWords = 4;    // words (waves) per workgroup
 constexpr int kLoads = 32;   // etheta loads a wave keeps in flight ahead of its add chain (64 VGPRs)
 
-// lambda[k, w] = eta + (sum over the word's entries, ascending document, of etheta[doc, k] * ratio[pos]) * beta[k, w].
+// The M-step's sum for one word: over the entries [b, e) of the word-major index, ascending, of
+// etheta[doc, k] * ratio[pos], into s0 (topic lane) and s1 (topic lane + 64, kTwo alone).  Both M-step kernels
+// instantiate this one chain.
 // A wave takes 64 entries' (doc, ratio) a load, lane = entry, the next 64 while it works on these.  Then, lane =
 // topic, the etheta values of the next R entries sit in a ring of R registers (R = kLoads with one topic a lane,
 // kLoads / 2 with two): the wave adds the entry in slot u and at once loads the entry R further on into that
 // slot, from the next 64 when it lies there, so R entries' loads are in flight all the way down the chain.
 template <bool kTwo>
-__global__ void __launch_bounds__(64 * kWords)
-lda_mstep_kernel(MStep p) {
+__device__ __forceinline__ void mstep_chain(const MStep& p, int64_t b, int64_t e, int lane, double& s0, double& s1) {
   constexpr int R = kTwo ? kLoads / 2 : kLoads;
   static_assert(64 % R == 0 && 64 / R >= 2, "a ring refilled from the next 64 entries in the last group of these");
-  const int lane = threadIdx.x & 63;
-  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int32_t w = (int32_t)blockIdx.x * kWords + wv;
-  if (w >= p.V) return;
   const int K = p.K;
   const int k0 = lane, k1 = lane + 64;
   const bool on0 = k0 < K, on1 = kTwo && k1 < K;
   const __amdgpu_buffer_rsrc_t ratio = buffer_rsrc(p.ratio, p.ratio_bytes);
   const __amdgpu_buffer_rsrc_t et = buffer_rsrc(p.etheta, p.et_bytes);
-  const int64_t b = max((int64_t)p.wptr[w], (int64_t)0);
-  const int64_t e = min((int64_t)p.wptr[w + 1], p.nnz);
 
   int32_t dd = 0, ddn = 0;
   double rr = 0.0, rrn = 0.0;
@@ -423,7 +423,8 @@ lda_mstep_kernel(MStep p) {
     if (kTwo) a1[u] = buf_load_f64(et, live && on1 ? row + 8u * (uint32_t)k1 : kBufOob);
   };
 
-  double s0 = 0.0, s1 = 0.0;
+  s0 = 0.0;
+  s1 = 0.0;
   load_entries(b, dd, rr);
   {
     const int m = (int)min((int64_t)64, e - b);
@@ -455,10 +456,83 @@ lda_mstep_kernel(MStep p) {
     dd = ddn;
     rr = rrn;
   }
+}
+
+// lambda[k, w] = eta + (sum over the word's entries, ascending document, of etheta[doc, k] * ratio[pos]) * beta[k, w]:
+// one wave per word, lane = topic.
+template <bool kTwo>
+__global__ void __launch_bounds__(64 * kWords)
+lda_mstep_kernel(MStep p) {
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int32_t w = (int32_t)blockIdx.x * kWords + wv;
+  if (w >= p.V) return;
+  const int k0 = lane, k1 = lane + 64;
+  const bool on0 = k0 < p.K, on1 = kTwo && k1 < p.K;
+  const int64_t b = max((int64_t)p.wptr[w], (int64_t)0);
+  const int64_t e = min((int64_t)p.wptr[w + 1], p.nnz);
+  double s0, s1;
+  mstep_chain<kTwo>(p, b, e, lane, s0, s1);
 
   const double* beta = p.table + (int64_t)w * p.ldt;
   if (on0) p.lambda[(int64_t)k0 * p.ldl + w] = p.eta + s0 * beta[k0];
   if (on1) p.lambda[(int64_t)k1 * p.ldl + w] = p.eta + s1 * beta[k1];
+}
+
+// The online M-step (_lda.py _em_step(batch_update=False)) of the minibatch of documents [doc_lo, doc_hi), in place:
+//     lambda[k, w] = lambda[k, w] * (1 - rho) + rho * (eta + doc_ratio * (S_kw * beta[k, w]))
+// with S_kw the chain above over the word's entries whose document lies in the minibatch.  The index is the whole
+// matrix's: a word's entries ascend in document, so the minibatch's are one contiguous sub-range, which the wave
+// finds with two lower-bound searches on doc (every lane the same search, wave-uniform loads).  Every word is
+// blended, with S = 0 where the minibatch does not hold it: sklearn's dense read-modify-write.
+struct MStepOnline {
+  MStep m;
+  int32_t doc_lo, doc_hi;
+  double rho, doc_ratio;
+};
+
+// the first i in [b, e) with doc[i] >= d, or e
+__device__ __forceinline__ int64_t doc_lower_bound(const int32_t* __restrict__ doc, int64_t b, int64_t e, int32_t d) {
+  while (b < e) {   // (at most 32 halvings: e - b < 2^31)
+    const int64_t mid = b + ((e - b) >> 1);
+    if (doc[mid] < d)
+      b = mid + 1;
+    else
+      e = mid;
+  }
+  return b;
+}
+
+template <bool kTwo>
+__global__ void __launch_bounds__(64 * kWords)
+lda_mstep_online_kernel(MStepOnline q) {
+  const MStep& p = q.m;
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int32_t w = (int32_t)blockIdx.x * kWords + wv;
+  if (w >= p.V) return;
+  const int k0 = lane, k1 = lane + 64;
+  const bool on0 = k0 < p.K, on1 = kTwo && k1 < p.K;
+  const int64_t wb = max((int64_t)p.wptr[w], (int64_t)0);
+  const int64_t we = max(min((int64_t)p.wptr[w + 1], p.nnz), wb);
+  const int64_t b = doc_lower_bound(p.doc, wb, we, q.doc_lo);
+  const int64_t e = doc_lower_bound(p.doc, b, we, q.doc_hi);
+  const double keep = 1.0 - q.rho;   // (formed once, from the rho passed in; +0 at rho = 1)
+  double s0, s1;
+  mstep_chain<kTwo>(p, b, e, lane, s0, s1);
+
+  const double* beta = p.table + (int64_t)w * p.ldt;
+  auto blend = [&](int k, double s) {
+    double* at = p.lambda + (int64_t)k * p.ldl + w;
+    const double ss = s * beta[k];
+    const double t = q.doc_ratio * ss;
+    const double u = p.eta + t;
+    const double v = q.rho * u;
+    const double a = *at * keep;
+    *at = a + v;
+  };
+  if (on0) blend(k0, s0);
+  if (on1) blend(k1, s1);
 }
 
 // K in range, the table's rows 16-byte accesses, every byte offset into it below kBufOob
@@ -652,11 +726,10 @@ extern "C" int gcnk_lda_estep_fit_f64(const int32_t* indptr, const int32_t* indi
                                                 stream, p);
 }
 
-extern "C" int gcnk_lda_mstep_f64(const int32_t* wptr, const int32_t* pos, const int32_t* doc, int64_t nnz,
-                                  const double* ratio, const double* etheta, int64_t lde, int32_t B, int32_t V,
-                                  int32_t K, const double* table, int64_t ldt, double eta, double* lambda, int64_t ldl,
-                                  void* stream) {
-  const char* who = "gcnk_lda_mstep_f64";
+// the refusals both M-step entry points share, then the kernels' common arguments
+static int mstep_args(const char* who, const int32_t* wptr, const int32_t* pos, const int32_t* doc, int64_t nnz,
+                      const double* ratio, const double* etheta, int64_t lde, int32_t B, int32_t V, int32_t K,
+                      const double* table, int64_t ldt, double eta, double* lambda, int64_t ldl, MStep& p) {
   const int rc = check_table(who, K, V, table, ldt);
   if (rc) return rc;
   if (B < 1 || !wptr || !pos || !doc || !ratio || !etheta || !lambda) {
@@ -676,7 +749,7 @@ extern "C" int gcnk_lda_mstep_f64(const int32_t* wptr, const int32_t* pos, const
               (long long)nnz, (long long)((int64_t)B * lde * 8));
     return GCNK_EUNSUP;
   }
-  MStep p{};
+  p = MStep{};
   p.wptr = wptr;
   p.pos = pos;
   p.doc = doc;
@@ -693,10 +766,54 @@ extern "C" int gcnk_lda_mstep_f64(const int32_t* wptr, const int32_t* pos, const
   p.eta = eta;
   p.lambda = lambda;
   p.ldl = ldl;
+  return GCNK_OK;
+}
+
+extern "C" int gcnk_lda_mstep_f64(const int32_t* wptr, const int32_t* pos, const int32_t* doc, int64_t nnz,
+                                  const double* ratio, const double* etheta, int64_t lde, int32_t B, int32_t V,
+                                  int32_t K, const double* table, int64_t ldt, double eta, double* lambda, int64_t ldl,
+                                  void* stream) {
+  MStep p;
+  const int rc = mstep_args("gcnk_lda_mstep_f64", wptr, pos, doc, nnz, ratio, etheta, lde, B, V, K, table, ldt, eta,
+                            lambda, ldl, p);
+  if (rc) return rc;
   const unsigned nblk = (unsigned)(((int64_t)V + kWords - 1) / kWords);
   if (K > 64)
     hipLaunchKernelGGL(lda_mstep_kernel<true>, dim3(nblk), dim3(64 * kWords), 0, (hipStream_t)stream, p);
   else
     hipLaunchKernelGGL(lda_mstep_kernel<false>, dim3(nblk), dim3(64 * kWords), 0, (hipStream_t)stream, p);
   return launch_check("lda_mstep_kernel");
+}
+
+extern "C" int gcnk_lda_mstep_online_f64(const int32_t* wptr, const int32_t* pos, const int32_t* doc, int64_t nnz,
+                                         int32_t doc_lo, int32_t doc_hi, const double* ratio, const double* etheta,
+                                         int64_t lde, int32_t B, int32_t V, int32_t K, const double* table, int64_t ldt,
+                                         double eta, double rho, double doc_ratio, double* lambda, int64_t ldl,
+                                         void* stream) {
+  const char* who = "gcnk_lda_mstep_online_f64";
+  MStepOnline q{};
+  const int rc = mstep_args(who, wptr, pos, doc, nnz, ratio, etheta, lde, B, V, K, table, ldt, eta, lambda, ldl, q.m);
+  if (rc) return rc;
+  if (doc_lo < 0 || doc_hi > B || doc_lo >= doc_hi) {
+    set_error("%s: the minibatch [%d, %d) is empty or outside the B=%d documents", who, doc_lo, doc_hi, B);
+    return GCNK_EARG;
+  }
+  if (!(rho > 0.0 && rho <= 1.0)) {   // (a NaN fails both)
+    set_error("%s: rho=%g is outside (0, 1]", who, rho);
+    return GCNK_EARG;
+  }
+  if (!(doc_ratio > 0.0 && doc_ratio <= 1.7976931348623157e308)) {   // (NaN and +inf fail)
+    set_error("%s: doc_ratio=%g is not a finite positive number", who, doc_ratio);
+    return GCNK_EARG;
+  }
+  q.doc_lo = doc_lo;
+  q.doc_hi = doc_hi;
+  q.rho = rho;
+  q.doc_ratio = doc_ratio;
+  const unsigned nblk = (unsigned)(((int64_t)V + kWords - 1) / kWords);
+  if (K > 64)
+    hipLaunchKernelGGL(lda_mstep_online_kernel<true>, dim3(nblk), dim3(64 * kWords), 0, (hipStream_t)stream, q);
+  else
+    hipLaunchKernelGGL(lda_mstep_online_kernel<false>, dim3(nblk), dim3(64 * kWords), 0, (hipStream_t)stream, q);
+  return launch_check("lda_mstep_online_kernel");
 }

@@ -2,12 +2,14 @@
 ``TopicInferencer``, ``build_topic_graph`` and ``DocumentScorer``.
 
 The reference fits sklearn's LDA on the host (topic_model.py:74-131,
-``LatentDirichletAllocation(learning_method='batch').fit``).  Here the same batch
-variational EM -- sklearn's rules restated in float64: its AS 103 psi, a fresh
-gamma draw every EM iteration, the mean-change stop rule, the sufficient
-statistics summed document by document in ascending order -- runs as
-``max_iter x (exp_dirichlet -> fit E-step -> M-step)`` launches queued on the
-current stream, then one last ``exp_dirichlet``:
+``LatentDirichletAllocation(learning_method=...).fit``, 'batch' or 'online':
+topic_model.py:46,55,113).  Here sklearn's variational EM -- its rules restated in
+float64: its AS 103 psi, a fresh gamma draw every EM iteration, the mean-change
+stop rule, the sufficient statistics summed document by document in ascending
+order -- runs as launches queued on the current stream.
+
+``learning_method="batch"`` (the default): ``max_iter x (exp_dirichlet -> fit
+E-step -> M-step)``, then one last ``exp_dirichlet``:
 
     indptr, indices, counts = doc_term(vectorizer.fit_transform(texts), "cuda")
     fit = fit_topics(indptr, indices, counts, V=len(vectorizer.vocabulary_), num_topics=50, max_iter=20)
@@ -15,20 +17,39 @@ current stream, then one last ``exp_dirichlet``:
     fit.topic_word_distribution    # lambda over its row sums          (topic_model.py:123-126)
     theta = fit.inferencer()(indptr, indices, counts)
 
+``learning_method="online"``: sklearn's minibatch EM (_lda.py
+``_em_step(batch_update=False)``).  Every EM iteration walks the documents in
+``gen_batches(B, batch_size)`` slices, and every slice is ``exp_dirichlet -> fit
+E-step on the slice's rows -> online M-step``:
+
+    lambda = lambda * (1 - rho) + rho * (eta + (B / slice size) * S o beta)
+
+with ``rho = numpy.power(learning_offset + n, -learning_decay)`` taken on the host
+in float64, n counting the minibatches from 1.  The same launches behind
+``OnlineTopics.partial_fit`` move a fitted model as new documents arrive:
+
+    ot = OnlineTopics(V, num_topics=50, total_samples=1e6)     # or OnlineTopics.from_fit(fit, total_samples=...)
+    ot.partial_fit(indptr, indices, counts)                    # lda.partial_fit(X)
+    theta = ot.inferencer()(indptr, indices, counts)
+
 Nothing between the first launch and the last synchronises with the host, and
-with ``init=`` the whole call can be captured in a hipGraph on one stream.
+with ``init=`` a whole ``fit_topics`` call (either method) can be captured in a
+hipGraph on one stream.
 
 sklearn's random draws are made on the host up front with
 ``numpy.random.RandomState(random_state)``: lambda0 = gamma(100, .01, (K, V)),
 then gamma0 = gamma(100, .01, (max_iter, B, K)) in one call, which is the stream
-of sklearn's successive (B, K) draws; they are uploaded before the first launch.
-``init=(lambda0, gamma0s)`` takes float64 device tensors of those shapes instead
-and draws nothing.
+of sklearn's successive draws (per EM iteration for 'batch', per minibatch for
+'online': rows [b0, b1) of iteration ``it`` are the slice ``[it, b0:b1]``); they
+are uploaded before the first launch.  ``init=(lambda0, gamma0s)`` takes float64
+device tensors of those shapes instead and draws nothing.  ``OnlineTopics`` keeps
+its RandomState and draws a (B, K) gamma0 per ``partial_fit``.
 
-Not restated (sklearn features the reference never uses): ``bound_`` and the
-extra E-step and perplexity sklearn computes for it after the loop,
-``learning_method='online'``, ``evaluate_every > 0``, ``n_jobs`` slicing of the
-documents, float32 input.  A document's word ids must be distinct (a CSR row of a
+Still not restated, out of scope (sklearn features the reference never uses):
+``bound_`` and the extra E-step and perplexity sklearn computes for it after the
+loop (so also ``score`` and ``perplexity``), ``evaluate_every > 0``, ``n_jobs``
+slicing of the documents, float32 input; the online method shuffles nothing, as
+sklearn's does not.  A document's word ids must be distinct (a CSR row of a
 document-term matrix); a word id outside [0, V) is the caller's error.
 """
 import torch
@@ -61,10 +82,12 @@ def word_index(indptr, indices, V):
 
 
 class TopicFit:
-    """What ``fit_topics`` returns; every tensor is on the documents' device."""
+    """What ``fit_topics`` returns; every tensor is on the documents' device.  ``n_batch_iter``
+    is sklearn's ``n_batch_iter_`` after the call: 1 + the M-steps run (EM iterations for
+    'batch', minibatches for 'online')."""
 
     __slots__ = ("components", "topic_word_distribution", "iterations", "doc_topic_prior", "topic_word_prior",
-                 "mean_change_tol", "max_doc_update_iter", "n_iter", "_table", "_work")
+                 "mean_change_tol", "max_doc_update_iter", "n_iter", "n_batch_iter", "_table", "_work")
 
     @property
     def exp_topic_word(self):
@@ -86,17 +109,96 @@ def _init_tensor(t, what, shape, dev):
     return t if t.is_contiguous() else t.contiguous()
 
 
+def _check_online(who, batch_size, learning_decay, learning_offset):
+    """sklearn's own constraints on the online method's parameters -> (batch_size, decay, offset)."""
+    bs, decay, offset = int(batch_size), float(learning_decay), float(learning_offset)
+    if bs < 1:
+        raise RuntimeError(f"{who}: batch_size={batch_size} must be at least 1")
+    if not 0.0 <= decay <= 1.0:
+        raise RuntimeError(f"{who}: learning_decay={learning_decay} is outside [0, 1]")
+    if not 1.0 <= offset < float("inf"):
+        raise RuntimeError(f"{who}: learning_offset={learning_offset} must be a finite number >= 1")
+    return bs, decay, offset
+
+
+def _rho(offset, n, decay):
+    """sklearn's weight of minibatch n (its ``n_batch_iter_``), in float64 on the host."""
+    import numpy as np
+    return float(np.power(offset + n, -decay))
+
+
+def _table_for(K, V, dev):
+    return torch.zeros((V, (K + 1) // 2 * 2), dtype=torch.float64, device=dev)
+
+
+def _exp_dirichlet(lib, stream, lam, table):
+    K, V = lam.shape
+    _lib.check(lib.gcnk_lda_exp_dirichlet_f64(lam.data_ptr(), lam.stride(0), K, V, table.data_ptr(), table.stride(0),
+                                              stream), "gcnk_lda_exp_dirichlet_f64")
+
+
+class _Documents:
+    """A document batch as the online pass reads it: the CSR, its word-major index and the
+    E-step's outputs (etheta [B x K], a ratio per stored nonzero)."""
+
+    __slots__ = ("indptr", "indices", "counts", "B", "nnz", "ix", "etheta", "ratio")
+
+    def __init__(self, indptr, indices, counts, B, V, K):
+        dev = indptr.device
+        self.indptr, indices, counts = indptr.contiguous(), indices.contiguous(), counts.contiguous()
+        self.B, self.nnz = B, indices.numel()
+        self.ix = word_index(self.indptr, indices, V)
+        if self.nnz == 0:   # (no word at all: the entry points still want addresses)
+            indices = torch.zeros(1, dtype=torch.int32, device=dev)
+            counts = torch.zeros(1, dtype=counts.dtype, device=dev)
+            self.ix.pos = self.ix.doc = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.indices, self.counts = indices, counts
+        self.etheta = torch.empty((B, K), dtype=torch.float64, device=dev)
+        self.ratio = torch.empty(max(self.nnz, 1), dtype=torch.float64, device=dev)
+
+
+def _online_pass(lib, stream, docs, lam, table, gamma0, iters, alpha, eta, tol, cap, bs, decay, offset, total, n):
+    """One walk over ``docs`` in minibatches of ``bs``: fit E-step on the rows -> online M-step
+    -> exp_dirichlet, the table being current on entry and on return.  ``gamma0`` [B x K] and
+    ``iters`` (int32 [B] or None) are the walk's; ``n`` is sklearn's n_batch_iter_ on entry ->
+    on return.  A row range needs no copy: the E-step takes indptr, gamma0, etheta and iters
+    advanced by b0 rows (8-byte scalar accesses, so any row offset is aligned) with the whole
+    ratio array, where it stores at absolute CSR positions; the M-step takes the whole index."""
+    K, V = lam.shape
+    B, ix = docs.B, docs.ix
+    for b0 in range(0, B, bs):
+        b1 = min(b0 + bs, B)
+        _lib.check(lib.gcnk_lda_estep_fit_f64(
+            docs.indptr[b0:].data_ptr(), docs.indices.data_ptr(), docs.counts.data_ptr(), _COUNTS[docs.counts.dtype],
+            b1 - b0, V, K, table.data_ptr(), table.stride(0), alpha, tol, cap, gamma0[b0:].data_ptr(), gamma0.stride(0),
+            docs.nnz, docs.ratio.data_ptr(), docs.etheta[b0:].data_ptr(), docs.etheta.stride(0), None, 0,
+            None if iters is None else iters[b0:].data_ptr(), stream), "gcnk_lda_estep_fit_f64")
+        _lib.check(lib.gcnk_lda_mstep_online_f64(
+            ix.wptr.data_ptr(), ix.pos.data_ptr(), ix.doc.data_ptr(), docs.nnz, b0, b1, docs.ratio.data_ptr(),
+            docs.etheta.data_ptr(), docs.etheta.stride(0), B, V, K, table.data_ptr(), table.stride(0), eta,
+            _rho(offset, n, decay), float(total) / (b1 - b0), lam.data_ptr(), lam.stride(0), stream),
+            "gcnk_lda_mstep_online_f64")
+        _exp_dirichlet(lib, stream, lam, table)
+        n += 1
+    return n
+
+
 def fit_topics(indptr, indices, counts, V, num_topics=50, max_iter=20, random_state=42, doc_topic_prior=None,
                topic_word_prior=None, mean_change_tol=1e-3, max_doc_update_iter=100, init=None,
-               return_iterations=False):
-    """sklearn's batch LDA fit of the documents (a CSR over V words, as ``doc_term`` gives it)
+               return_iterations=False, learning_method="batch", batch_size=128, learning_decay=0.7,
+               learning_offset=10.0):
+    """sklearn's LDA fit of the documents (a CSR over V words, as ``doc_term`` gives it)
     -> TopicFit.  ``doc_topic_prior`` / ``topic_word_prior`` default to 1 / num_topics as
     sklearn's do.  ``init``: (lambda0 [K x V], gamma0s [max_iter x B x K]) float64 on the
     documents' device instead of the host draw.  ``return_iterations``: ``fit.iterations`` is the
     int32 [max_iter x B] count of updates every document ran in every EM iteration.
+    ``learning_method``: 'batch' or 'online'; ``batch_size``, ``learning_decay`` and
+    ``learning_offset`` are the online method's (sklearn's names and defaults) and are not
+    looked at for 'batch'.
     RuntimeError, never a fallback: more than 128 topics, max_iter < 1, V < 1, an update cap
-    outside [0, 10000], a bad ``init``, and check_documents' refusals (float32 counts, CPU
-    tensors, dtypes)."""
+    outside [0, 10000], a bad ``init``, an unknown ``learning_method``, batch_size < 1,
+    learning_decay outside [0, 1], learning_offset < 1, and check_documents' refusals (float32
+    counts, CPU tensors, dtypes)."""
     K, V, max_iter, cap = int(num_topics), int(V), int(max_iter), int(max_doc_update_iter)
     if not 1 <= K <= MAX_TOPICS:
         raise RuntimeError(f"fit_topics: num_topics={K} is outside [1, {MAX_TOPICS}] (unsupported: two topics a lane)")
@@ -104,6 +206,11 @@ def fit_topics(indptr, indices, counts, V, num_topics=50, max_iter=20, random_st
         raise RuntimeError(f"fit_topics: needs max_iter >= 1 and V >= 1 (max_iter={max_iter} V={V})")
     if not 0 <= cap <= MAX_UPDATE_ITER:
         raise RuntimeError(f"fit_topics: max_doc_update_iter={cap} is outside [0, {MAX_UPDATE_ITER}]")
+    if learning_method not in ("batch", "online"):
+        raise RuntimeError(f"fit_topics: learning_method={learning_method!r} is neither 'batch' nor 'online'")
+    online = learning_method == "online"
+    if online:
+        bs, decay, offset = _check_online("fit_topics", batch_size, learning_decay, learning_offset)
     B = check_documents(indptr, indices, counts, getattr(indptr, "device", None))
     dev = indptr.device
     alpha = 1.0 / K if doc_topic_prior is None else float(doc_topic_prior)
@@ -121,41 +228,39 @@ def fit_topics(indptr, indices, counts, V, num_topics=50, max_iter=20, random_st
         lam0 = _init_tensor(init[0], "lambda0", (K, V), dev)
         gamma0s = _init_tensor(init[1], "gamma0s", (max_iter, B, K), dev)
 
-    indptr, indices, counts = indptr.contiguous(), indices.contiguous(), counts.contiguous()
-    nnz = indices.numel()
-    ix = word_index(indptr, indices, V)
-    if nnz == 0:   # (no word at all: the entry points still want addresses)
-        indices = torch.zeros(1, dtype=torch.int32, device=dev)
-        counts = torch.zeros(1, dtype=counts.dtype, device=dev)
-        ix.pos = ix.doc = torch.zeros(1, dtype=torch.int32, device=dev)
-    table = torch.zeros((V, (K + 1) // 2 * 2), dtype=torch.float64, device=dev)
-    lam = torch.empty((K, V), dtype=torch.float64, device=dev)
-    etheta = torch.empty((B, K), dtype=torch.float64, device=dev)
-    ratio = torch.empty(max(nnz, 1), dtype=torch.float64, device=dev)
+    docs = _Documents(indptr, indices, counts, B, V, K)
+    indptr, indices, counts, nnz, ix, etheta, ratio = (docs.indptr, docs.indices, docs.counts, docs.nnz, docs.ix,
+                                                       docs.etheta, docs.ratio)
+    table = _table_for(K, V, dev)
     iters = torch.empty((max_iter, B), dtype=torch.int32, device=dev) if return_iterations else None
 
     lib = _lib.load()
     ldt = table.stride(0)
     with torch.cuda.device(dev):
         stream = _lib.stream(dev)
-
-        def exp_dirichlet(src):
-            _lib.check(lib.gcnk_lda_exp_dirichlet_f64(src.data_ptr(), src.stride(0), K, V, table.data_ptr(), ldt, stream),
-                       "gcnk_lda_exp_dirichlet_f64")
-
-        for it in range(max_iter):
-            exp_dirichlet(lam0 if it == 0 else lam)
-            g0 = gamma0s[it]
-            _lib.check(lib.gcnk_lda_estep_fit_f64(
-                indptr.data_ptr(), indices.data_ptr(), counts.data_ptr(), _COUNTS[counts.dtype], B, V, K,
-                table.data_ptr(), ldt, alpha, tol, cap, g0.data_ptr(), g0.stride(0), nnz, ratio.data_ptr(),
-                etheta.data_ptr(), etheta.stride(0), None, 0, None if iters is None else iters[it].data_ptr(), stream),
-                "gcnk_lda_estep_fit_f64")
-            _lib.check(lib.gcnk_lda_mstep_f64(
-                ix.wptr.data_ptr(), ix.pos.data_ptr(), ix.doc.data_ptr(), nnz, ratio.data_ptr(), etheta.data_ptr(),
-                etheta.stride(0), B, V, K, table.data_ptr(), ldt, eta, lam.data_ptr(), lam.stride(0), stream),
-                "gcnk_lda_mstep_f64")
-        exp_dirichlet(lam)
+        if online:
+            lam = lam0.clone()   # (the online M-step works in place)
+            _exp_dirichlet(lib, stream, lam, table)
+            n = 1
+            for it in range(max_iter):
+                n = _online_pass(lib, stream, docs, lam, table, gamma0s[it], None if iters is None else iters[it],
+                                 alpha, eta, tol, cap, bs, decay, offset, B, n)
+        else:
+            lam = torch.empty((K, V), dtype=torch.float64, device=dev)
+            for it in range(max_iter):
+                _exp_dirichlet(lib, stream, lam0 if it == 0 else lam, table)
+                g0 = gamma0s[it]
+                _lib.check(lib.gcnk_lda_estep_fit_f64(
+                    indptr.data_ptr(), indices.data_ptr(), counts.data_ptr(), _COUNTS[counts.dtype], B, V, K,
+                    table.data_ptr(), ldt, alpha, tol, cap, g0.data_ptr(), g0.stride(0), nnz, ratio.data_ptr(),
+                    etheta.data_ptr(), etheta.stride(0), None, 0, None if iters is None else iters[it].data_ptr(),
+                    stream), "gcnk_lda_estep_fit_f64")
+                _lib.check(lib.gcnk_lda_mstep_f64(
+                    ix.wptr.data_ptr(), ix.pos.data_ptr(), ix.doc.data_ptr(), nnz, ratio.data_ptr(), etheta.data_ptr(),
+                    etheta.stride(0), B, V, K, table.data_ptr(), ldt, eta, lam.data_ptr(), lam.stride(0), stream),
+                    "gcnk_lda_mstep_f64")
+            _exp_dirichlet(lib, stream, lam, table)
+            n = 1 + max_iter
 
     fit = TopicFit()
     fit.components = lam
@@ -163,7 +268,122 @@ def fit_topics(indptr, indices, counts, V, num_topics=50, max_iter=20, random_st
     fit.iterations = iters
     fit.doc_topic_prior, fit.topic_word_prior = alpha, eta
     fit.mean_change_tol, fit.max_doc_update_iter, fit.n_iter = tol, cap, max_iter
+    fit.n_batch_iter = n
     fit._table = table
     # (a captured call's launches keep reading these through raw pointers: held as long as the result is)
-    fit._work = (indptr, indices, counts, lam0, gamma0s, ix, etheta, ratio)
+    fit._work = (docs, lam0, gamma0s)
     return fit
+
+
+class OnlineTopics:
+    """A topic model that keeps learning on the device: sklearn's
+    ``LatentDirichletAllocation(learning_method='online').partial_fit``.
+
+    The first construction draws lambda0 = gamma(100, .01, (K, V)) from
+    ``RandomState(random_state)`` on the host, as sklearn's ``_init_latent_vars`` does at its
+    first ``partial_fit``; ``init_components`` takes a float64 [K x V] device tensor instead
+    (it is copied).  ``total_samples`` is sklearn's: the corpus size the minibatches are
+    scaled to.  ``n_batch_iter`` (sklearn's ``n_batch_iter_``) lives on the host; nothing
+    synchronises."""
+
+    def __init__(self, V, num_topics=50, total_samples=1e6, batch_size=128, learning_decay=0.7, learning_offset=10.0,
+                 random_state=42, doc_topic_prior=None, topic_word_prior=None, mean_change_tol=1e-3,
+                 max_doc_update_iter=100, device="cuda", init_components=None):
+        import numpy as np
+        K, V, cap = int(num_topics), int(V), int(max_doc_update_iter)
+        if not 1 <= K <= MAX_TOPICS:
+            raise RuntimeError(f"OnlineTopics: num_topics={K} is outside [1, {MAX_TOPICS}] (unsupported: two topics a lane)")
+        if V < 1:
+            raise RuntimeError(f"OnlineTopics: needs V >= 1 (V={V})")
+        if not 0 <= cap <= MAX_UPDATE_ITER:
+            raise RuntimeError(f"OnlineTopics: max_doc_update_iter={cap} is outside [0, {MAX_UPDATE_ITER}]")
+        self.batch_size, self.learning_decay, self.learning_offset = _check_online(
+            "OnlineTopics", batch_size, learning_decay, learning_offset)
+        self.total_samples = float(total_samples)
+        if not 0.0 < self.total_samples < float("inf"):
+            raise RuntimeError(f"OnlineTopics: total_samples={total_samples} must be a finite positive number")
+        self.num_topics, self.V = K, V
+        self.doc_topic_prior = 1.0 / K if doc_topic_prior is None else float(doc_topic_prior)
+        self.topic_word_prior = 1.0 / K if topic_word_prior is None else float(topic_word_prior)
+        self.mean_change_tol, self.max_doc_update_iter = float(mean_change_tol), cap
+        self.n_batch_iter = 1
+        self.iterations = None
+        self._rs = random_state if isinstance(random_state, np.random.RandomState) else np.random.RandomState(random_state)
+        if init_components is None:
+            dev = torch.device(device)
+            if dev.type != "cuda":
+                raise RuntimeError(f"OnlineTopics needs a ROCm GPU device, got {dev}")
+            self._lam = torch.from_numpy(self._rs.gamma(100.0, 0.01, (K, V))).to(dev)
+        else:
+            require_device(init_components, "init_components")
+            self._lam = _init_tensor(init_components, "init_components", (K, V), init_components.device).clone()
+        self._table = None   # (made at the first use: construction launches nothing)
+        self._work = None
+
+    @classmethod
+    def from_fit(cls, fit, total_samples, random_state=42, batch_size=128, learning_decay=0.7, learning_offset=10.0):
+        """Go on from a ``fit_topics`` result (batch or online): its lambda (copied), priors,
+        tolerance, update cap and ``n_batch_iter``.  ``random_state`` seeds the gamma0 draws of
+        the ``partial_fit`` calls to come."""
+        K, V = fit.components.shape
+        ot = cls(V, num_topics=K, total_samples=total_samples, batch_size=batch_size, learning_decay=learning_decay,
+                 learning_offset=learning_offset, random_state=random_state, doc_topic_prior=fit.doc_topic_prior,
+                 topic_word_prior=fit.topic_word_prior, mean_change_tol=fit.mean_change_tol,
+                 max_doc_update_iter=fit.max_doc_update_iter, init_components=fit.components)
+        ot.n_batch_iter = int(fit.n_batch_iter)
+        return ot
+
+    def _current_table(self, lib, stream):
+        if self._table is None:
+            self._table = _table_for(self.num_topics, self.V, self._lam.device)
+            _exp_dirichlet(lib, stream, self._lam, self._table)
+        return self._table
+
+    def partial_fit(self, indptr, indices, counts, gamma0=None, return_iterations=False):
+        """sklearn's ``partial_fit`` of these documents (a CSR over the model's V words) -> self:
+        the minibatch walk in ``batch_size`` slices with doc_ratio = total_samples / slice size.
+        ``gamma0``: float64 [B x K] on the device instead of the host draw.
+        ``return_iterations``: ``self.iterations`` is the int32 [B] update counts of this call."""
+        K, V, dev = self.num_topics, self.V, self._lam.device
+        B = check_documents(indptr, indices, counts, dev)
+        if gamma0 is None:
+            g0 = torch.from_numpy(self._rs.gamma(100.0, 0.01, (B, K))).to(dev)
+        else:
+            g0 = _init_tensor(gamma0, "gamma0", (B, K), dev)
+        docs = _Documents(indptr, indices, counts, B, V, K)
+        iters = torch.empty(B, dtype=torch.int32, device=dev) if return_iterations else None
+        lib = _lib.load()
+        with torch.cuda.device(dev):
+            stream = _lib.stream(dev)
+            table = self._current_table(lib, stream)
+            self.n_batch_iter = _online_pass(lib, stream, docs, self._lam, table, g0, iters, self.doc_topic_prior,
+                                             self.topic_word_prior, self.mean_change_tol, self.max_doc_update_iter,
+                                             self.batch_size, self.learning_decay, self.learning_offset,
+                                             self.total_samples, self.n_batch_iter)
+        self.iterations = iters
+        self._work = (docs, g0)
+        return self
+
+    @property
+    def components(self):
+        """lambda [K x V] float64 (sklearn's ``components_``), updated in place by ``partial_fit``."""
+        return self._lam
+
+    @property
+    def topic_word_distribution(self):
+        """lambda over its row sums (topic_model.py:123-126)."""
+        return self._lam / self._lam.sum(dim=1, keepdim=True)
+
+    @property
+    def exp_topic_word(self):
+        """exp(E[log beta]) [K x V] float64 of the current lambda (sklearn's
+        ``exp_dirichlet_component_``): a transposed view of the table."""
+        with torch.cuda.device(self._lam.device):
+            table = self._current_table(_lib.load(), _lib.stream(self._lam.device))
+        return table[:, :self.num_topics].t()
+
+    def inferencer(self):
+        """``TopicInferencer.from_components`` of a copy of the current lambda: theta of any
+        documents under the model as it stands now."""
+        return TopicInferencer.from_components(self._lam.clone(), self.doc_topic_prior, self.mean_change_tol,
+                                               self.max_doc_update_iter)

@@ -1122,6 +1122,48 @@ int gcnk_lda_mstep_f64(const int32_t* wptr, const int32_t* pos, const int32_t* d
                        int64_t ldt, double eta, double* lambda, int64_t ldl, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * The topic model fitted ONLINE on the device (csrc/lda_estep.hip; an addition
+ * within ABI 13): sklearn's minibatch variational EM, learning_method='online'
+ * and partial_fit (_lda.py _em_step(batch_update=False)), which the reference's
+ * TopicModel offers as learning_method (topic_model.py:46,55,113).  A minibatch
+ * of documents [doc_lo, doc_hi) is three launches on one stream:
+ *   gcnk_lda_exp_dirichlet_f64   the table from the current lambda
+ *   gcnk_lda_estep_fit_f64       on the row range: indptr + doc_lo, B = doc_hi -
+ *       doc_lo, gamma0 and etheta advanced by doc_lo rows, the WHOLE ratio and
+ *       nnz (a ratio is stored at its absolute CSR position)
+ *   gcnk_lda_mstep_online_f64    for every word w and topic k, in place, every
+ *       line one correctly rounded float64 operation (no fma, no atomics):
+ *           S   = sum over w's entries whose document d is in [doc_lo, doc_hi),
+ *                 ASCENDING d, of etheta[d, k] * ratio[its entry] (the product
+ *                 rounded, then added: gcnk_lda_mstep_f64's chain, the same code)
+ *           ss  = S * table[w, k]
+ *           t   = doc_ratio * ss
+ *           u   = eta + t
+ *           v   = rho * u
+ *           a   = lambda[k * ldl + w] * (1.0 - rho)
+ *           lambda[k * ldl + w] = a + v
+ *       wptr / pos / doc are the word-major index of the WHOLE matrix, the one
+ *       gcnk_lda_mstep_f64 takes; etheta is [B x lde] with the minibatch's rows
+ *       filled.  A word's entries ascend in document, so the minibatch's are a
+ *       contiguous sub-range of [wptr[w], wptr[w + 1]) (clamped to [0, nnz]),
+ *       found on the device by a lower-bound search on doc for doc_lo and for
+ *       doc_hi: no index is built per minibatch.  A word the minibatch does not
+ *       hold is blended with S = 0.  rho = (learning_offset + n_batch_iter) ^
+ *       -learning_decay is the caller's (float64, on the host); 1.0 - rho is
+ *       formed from it once; rho = 1 gives a = +0.  doc_ratio = total_samples /
+ *       (doc_hi - doc_lo).
+ * GCNK_EARG: gcnk_lda_mstep_f64's (B < 1, K < 1, V < 1, a null pointer, a bad
+ * table, lde < K, ldl < V, nnz < 0), doc_lo < 0, doc_hi > B, doc_lo >= doc_hi,
+ * rho outside (0, 1] or not finite, doc_ratio not finite or <= 0.  GCNK_EUNSUP:
+ * K > 128, a table, nnz ratios or an etheta past 32-bit byte offsets.  Every
+ * refusal comes before any HIP call.
+ * ------------------------------------------------------------------------- */
+int gcnk_lda_mstep_online_f64(const int32_t* wptr, const int32_t* pos, const int32_t* doc, int64_t nnz, int32_t doc_lo,
+                              int32_t doc_hi, const double* ratio, const double* etheta, int64_t lde, int32_t B,
+                              int32_t V, int32_t K, const double* table, int64_t ldt, double eta, double rho,
+                              double doc_ratio, double* lambda, int64_t ldl, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Dropout keep-mask exactly as the reference's CPU th.dropout draws it
  * (HOST pointers; layer.py:185 -> ATen dropout -> empty_like(x).bernoulli_(p)
  * with p = 1 - dropout): torch's serial CPU bernoulli_ takes one 64-bit draw
