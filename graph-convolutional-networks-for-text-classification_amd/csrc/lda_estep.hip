@@ -50,6 +50,13 @@
 //                     the whole matrix's index (entries ascend in document), found by two lower-bound searches.
 // The M-step's loops run over [wptr[w], wptr[w + 1]) clamped to [0, nnz], nnz checked on the host; ratio and
 // etheta are read (and ratio written) through buffer resources, so a bad index reads zeros or writes nothing.
+//
+// The entry points, at the end of the file, are three families, each with its refusals and launch stated once:
+//     tables    gcnk_lda_exp_dirichlet_f64, gcnk_lda_table_from_exp_f64: check_table, then their own source check
+//     E-step    gcnk_lda_estep_f64 (transform), gcnk_lda_estep_fit_f64 (both fits): estep_args -- check_table, the
+//               document refusals, the common EStep fields -- then each one's own outputs; launch_estep<kFit>
+//     M-step    gcnk_lda_mstep_f64 (batch), gcnk_lda_mstep_online_f64 (online, partial_fit): mstep_args the same
+//               way, the online one then its minibatch, rho and doc_ratio; launch_mstep picks one or two topics a lane
 #include "gcnk_common.h"
 
 #pragma clang fp contract(off)
@@ -598,12 +605,10 @@ extern "C" int gcnk_lda_table_from_exp_f64(const double* exp_topic_word, int64_t
   return launch_check("lda_transpose_kernel");
 }
 
-extern "C" int gcnk_lda_estep_f64(const int32_t* indptr, const int32_t* indices, const void* counts,
-                                  int32_t counts_kind, int32_t B, int32_t V, int32_t K, const double* table,
-                                  int64_t ldt, double alpha, double tol, int32_t max_iter, double* theta, int64_t ldth,
-                                  double* gamma, int32_t* iters, float* x, int64_t ldx, float* a, int64_t lda,
-                                  double threshold, void* stream) {
-  const char* who = "gcnk_lda_estep_f64";
+// the refusals both E-step entry points share, then the kernel's common arguments (gamma and iters may be null)
+static int estep_args(const char* who, const int32_t* indptr, const int32_t* indices, const void* counts,
+                      int32_t counts_kind, int32_t B, int32_t V, int32_t K, const double* table, int64_t ldt,
+                      double alpha, double tol, int32_t max_iter, double* gamma, int64_t ldg, int32_t* iters, EStep& p) {
   const int rc = check_table(who, K, V, table, ldt);
   if (rc) return rc;
   if (B < 1 || !indptr || !indices || !counts) {
@@ -618,6 +623,43 @@ extern "C" int gcnk_lda_estep_f64(const int32_t* indptr, const int32_t* indices,
     set_error("%s: max_iter=%d is outside [0, %d]", who, max_iter, kMaxIter);
     return GCNK_EARG;
   }
+  p = EStep{};
+  p.indptr = indptr;
+  p.indices = indices;
+  p.counts = counts;
+  p.counts_kind = counts_kind;
+  p.B = B;
+  p.K = K;
+  p.table = table;
+  p.row_bytes = (uint32_t)(ldt * 8);
+  p.table_bytes = (uint32_t)((int64_t)V * ldt * 8);
+  p.alpha = alpha;
+  p.tol = tol;
+  p.max_iter = max_iter;
+  p.gamma = gamma;
+  p.ldth = ldg;
+  p.iters = iters;
+  return GCNK_OK;
+}
+
+// kDocs documents a workgroup, each wave with its own slice of the dynamic LDS
+template <bool kFit>
+static int launch_estep(const char* name, const EStep& p, void* stream) {
+  const int lds_bytes = kDocs * wave_doubles(p.K) * (int)sizeof(double);
+  const unsigned nblk = (unsigned)(((int64_t)p.B + kDocs - 1) / kDocs);
+  return launch_big_lds<lda_estep_kernel<kFit>>(name, dim3(nblk), dim3(64 * kDocs), (size_t)lds_bytes, stream, p);
+}
+
+extern "C" int gcnk_lda_estep_f64(const int32_t* indptr, const int32_t* indices, const void* counts,
+                                  int32_t counts_kind, int32_t B, int32_t V, int32_t K, const double* table,
+                                  int64_t ldt, double alpha, double tol, int32_t max_iter, double* theta, int64_t ldth,
+                                  double* gamma, int32_t* iters, float* x, int64_t ldx, float* a, int64_t lda,
+                                  double threshold, void* stream) {
+  const char* who = "gcnk_lda_estep_f64";
+  EStep p;
+  const int rc = estep_args(who, indptr, indices, counts, counts_kind, B, V, K, table, ldt, alpha, tol, max_iter, gamma,
+                            ldth, iters, p);
+  if (rc) return rc;
   if ((x == nullptr) != (a == nullptr)) {
     set_error("%s: x and a are given together or not at all", who);
     return GCNK_EARG;
@@ -631,32 +673,13 @@ extern "C" int gcnk_lda_estep_f64(const int32_t* indptr, const int32_t* indices,
               (long long)ldth, (long long)ldx, (long long)lda);
     return GCNK_EARG;
   }
-  EStep p{};
-  p.indptr = indptr;
-  p.indices = indices;
-  p.counts = counts;
-  p.counts_kind = counts_kind;
-  p.B = B;
-  p.K = K;
-  p.table = table;
-  p.row_bytes = (uint32_t)(ldt * 8);
-  p.table_bytes = (uint32_t)((int64_t)V * ldt * 8);
-  p.alpha = alpha;
-  p.tol = tol;
-  p.max_iter = max_iter;
   p.theta = theta;
-  p.gamma = gamma;
-  p.ldth = ldth;
-  p.iters = iters;
   p.x = x;
   p.ldx = ldx;
   p.a = a;
   p.lda = lda;
   p.threshold = threshold;
-  const int lds_bytes = kDocs * wave_doubles(K) * (int)sizeof(double);
-  const unsigned nblk = (unsigned)(((int64_t)B + kDocs - 1) / kDocs);
-  return launch_big_lds<lda_estep_kernel<false>>("lda_estep_kernel", dim3(nblk), dim3(64 * kDocs), (size_t)lds_bytes,
-                                                 stream, p);
+  return launch_estep<false>("lda_estep_kernel", p, stream);
 }
 
 extern "C" int32_t gcnk_lda_words_per_block(void) { return kWords; }
@@ -667,20 +690,10 @@ extern "C" int gcnk_lda_estep_fit_f64(const int32_t* indptr, const int32_t* indi
                                       int64_t ldg0, int64_t nnz, double* ratio, double* etheta, int64_t lde,
                                       double* gamma, int64_t ldg, int32_t* iters, void* stream) {
   const char* who = "gcnk_lda_estep_fit_f64";
-  const int rc = check_table(who, K, V, table, ldt);
+  EStep p;
+  const int rc = estep_args(who, indptr, indices, counts, counts_kind, B, V, K, table, ldt, alpha, tol, max_iter, gamma,
+                            ldg, iters, p);
   if (rc) return rc;
-  if (B < 1 || !indptr || !indices || !counts) {
-    set_error("%s: needs B >= 1 and non-null indptr, indices and counts (B=%d)", who, B);
-    return GCNK_EARG;
-  }
-  if (counts_kind < 0 || counts_kind > 2) {
-    set_error("%s: counts_kind %d is not 0 (float64), 1 (int32) or 2 (int64)", who, counts_kind);
-    return GCNK_EARG;
-  }
-  if (max_iter < 0 || max_iter > kMaxIter) {
-    set_error("%s: max_iter=%d is outside [0, %d]", who, max_iter, kMaxIter);
-    return GCNK_EARG;
-  }
   if (!gamma0 || !ratio || !etheta) {
     set_error("%s: gamma0, ratio and etheta must be non-null", who);
     return GCNK_EARG;
@@ -698,32 +711,13 @@ extern "C" int gcnk_lda_estep_fit_f64(const int32_t* indptr, const int32_t* indi
     set_error("%s: %lld ratios are past the 32-bit offsets of their buffer resource", who, (long long)nnz);
     return GCNK_EUNSUP;
   }
-  EStep p{};
-  p.indptr = indptr;
-  p.indices = indices;
-  p.counts = counts;
-  p.counts_kind = counts_kind;
-  p.B = B;
-  p.K = K;
-  p.table = table;
-  p.row_bytes = (uint32_t)(ldt * 8);
-  p.table_bytes = (uint32_t)((int64_t)V * ldt * 8);
-  p.alpha = alpha;
-  p.tol = tol;
-  p.max_iter = max_iter;
-  p.gamma = gamma;
-  p.ldth = ldg;
-  p.iters = iters;
   p.gamma0 = gamma0;
   p.ldg0 = ldg0;
   p.etheta = etheta;
   p.lde = lde;
   p.ratio = ratio;
   p.ratio_bytes = (uint32_t)(nnz * 8);
-  const int lds_bytes = kDocs * wave_doubles(K) * (int)sizeof(double);
-  const unsigned nblk = (unsigned)(((int64_t)B + kDocs - 1) / kDocs);
-  return launch_big_lds<lda_estep_kernel<true>>("lda_estep_fit_kernel", dim3(nblk), dim3(64 * kDocs), (size_t)lds_bytes,
-                                                stream, p);
+  return launch_estep<true>("lda_estep_fit_kernel", p, stream);
 }
 
 // the refusals both M-step entry points share, then the kernels' common arguments
@@ -769,6 +763,17 @@ static int mstep_args(const char* who, const int32_t* wptr, const int32_t* pos, 
   return GCNK_OK;
 }
 
+// kWords words a workgroup; K > 64 takes the instantiation with two topics a lane
+template <auto kTwoTopics, auto kOneTopic, typename P>
+static int launch_mstep(const char* name, const P& p, int32_t V, int32_t K, void* stream) {
+  const unsigned nblk = (unsigned)(((int64_t)V + kWords - 1) / kWords);
+  if (K > 64)
+    hipLaunchKernelGGL(kTwoTopics, dim3(nblk), dim3(64 * kWords), 0, (hipStream_t)stream, p);
+  else
+    hipLaunchKernelGGL(kOneTopic, dim3(nblk), dim3(64 * kWords), 0, (hipStream_t)stream, p);
+  return launch_check(name);
+}
+
 extern "C" int gcnk_lda_mstep_f64(const int32_t* wptr, const int32_t* pos, const int32_t* doc, int64_t nnz,
                                   const double* ratio, const double* etheta, int64_t lde, int32_t B, int32_t V,
                                   int32_t K, const double* table, int64_t ldt, double eta, double* lambda, int64_t ldl,
@@ -777,12 +782,7 @@ extern "C" int gcnk_lda_mstep_f64(const int32_t* wptr, const int32_t* pos, const
   const int rc = mstep_args("gcnk_lda_mstep_f64", wptr, pos, doc, nnz, ratio, etheta, lde, B, V, K, table, ldt, eta,
                             lambda, ldl, p);
   if (rc) return rc;
-  const unsigned nblk = (unsigned)(((int64_t)V + kWords - 1) / kWords);
-  if (K > 64)
-    hipLaunchKernelGGL(lda_mstep_kernel<true>, dim3(nblk), dim3(64 * kWords), 0, (hipStream_t)stream, p);
-  else
-    hipLaunchKernelGGL(lda_mstep_kernel<false>, dim3(nblk), dim3(64 * kWords), 0, (hipStream_t)stream, p);
-  return launch_check("lda_mstep_kernel");
+  return launch_mstep<lda_mstep_kernel<true>, lda_mstep_kernel<false>>("lda_mstep_kernel", p, V, K, stream);
 }
 
 extern "C" int gcnk_lda_mstep_online_f64(const int32_t* wptr, const int32_t* pos, const int32_t* doc, int64_t nnz,
@@ -810,10 +810,6 @@ extern "C" int gcnk_lda_mstep_online_f64(const int32_t* wptr, const int32_t* pos
   q.doc_hi = doc_hi;
   q.rho = rho;
   q.doc_ratio = doc_ratio;
-  const unsigned nblk = (unsigned)(((int64_t)V + kWords - 1) / kWords);
-  if (K > 64)
-    hipLaunchKernelGGL(lda_mstep_online_kernel<true>, dim3(nblk), dim3(64 * kWords), 0, (hipStream_t)stream, q);
-  else
-    hipLaunchKernelGGL(lda_mstep_online_kernel<false>, dim3(nblk), dim3(64 * kWords), 0, (hipStream_t)stream, q);
-  return launch_check("lda_mstep_online_kernel");
+  return launch_mstep<lda_mstep_online_kernel<true>, lda_mstep_online_kernel<false>>("lda_mstep_online_kernel", q, V, K,
+                                                                                      stream);
 }

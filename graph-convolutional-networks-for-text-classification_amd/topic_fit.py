@@ -56,7 +56,8 @@ import torch
 
 from . import _lib
 from .sparse import require_device
-from .topic_infer import _COUNTS, MAX_TOPICS, MAX_UPDATE_ITER, TopicInferencer, check_documents
+from .topic_infer import (_COUNTS, MAX_TOPICS, MAX_UPDATE_ITER, TopicInferencer, check_documents, kernel_documents,
+                          model_table)
 
 WORDS_PER_BLOCK = 4   # csrc/lda_estep.hip kWords: the M-step's waves (words) per workgroup
 
@@ -109,6 +110,29 @@ def _init_tensor(t, what, shape, dev):
     return t if t.is_contiguous() else t.contiguous()
 
 
+def _check_model(who, K, cap, **at_least_one):
+    """The refusals of a model's size: the topics two a lane, every named size (V, max_iter) at
+    least 1, the update cap within the kernel's."""
+    if not 1 <= K <= MAX_TOPICS:
+        raise RuntimeError(f"{who}: num_topics={K} is outside [1, {MAX_TOPICS}] (unsupported: two topics a lane)")
+    if min(at_least_one.values()) < 1:
+        raise RuntimeError(f"{who}: needs {' and '.join(f'{k} >= 1' for k in at_least_one)} "
+                           f"({' '.join(f'{k}={v}' for k, v in at_least_one.items())})")
+    if not 0 <= cap <= MAX_UPDATE_ITER:
+        raise RuntimeError(f"{who}: max_doc_update_iter={cap} is outside [0, {MAX_UPDATE_ITER}]")
+
+
+def _random_state(random_state):
+    """A numpy RandomState as it is, anything else as its seed."""
+    import numpy as np
+    return random_state if isinstance(random_state, np.random.RandomState) else np.random.RandomState(random_state)
+
+
+def _draw(rs, shape, dev):
+    """sklearn's initial draw, gamma(100, .01), made on the host and uploaded."""
+    return torch.from_numpy(rs.gamma(100.0, 0.01, shape)).to(dev)
+
+
 def _check_online(who, batch_size, learning_decay, learning_offset):
     """sklearn's own constraints on the online method's parameters -> (batch_size, decay, offset)."""
     bs, decay, offset = int(batch_size), float(learning_decay), float(learning_offset)
@@ -127,10 +151,6 @@ def _rho(offset, n, decay):
     return float(np.power(offset + n, -decay))
 
 
-def _table_for(K, V, dev):
-    return torch.zeros((V, (K + 1) // 2 * 2), dtype=torch.float64, device=dev)
-
-
 def _exp_dirichlet(lib, stream, lam, table):
     K, V = lam.shape
     _lib.check(lib.gcnk_lda_exp_dirichlet_f64(lam.data_ptr(), lam.stride(0), K, V, table.data_ptr(), table.stride(0),
@@ -138,41 +158,44 @@ def _exp_dirichlet(lib, stream, lam, table):
 
 
 class _Documents:
-    """A document batch as the online pass reads it: the CSR, its word-major index and the
+    """A document batch as the fit's launches read it: the CSR, its word-major index and the
     E-step's outputs (etheta [B x K], a ratio per stored nonzero)."""
 
-    __slots__ = ("indptr", "indices", "counts", "B", "nnz", "ix", "etheta", "ratio")
+    __slots__ = ("indptr", "indices", "counts", "B", "V", "K", "nnz", "ix", "etheta", "ratio")
 
     def __init__(self, indptr, indices, counts, B, V, K):
         dev = indptr.device
-        self.indptr, indices, counts = indptr.contiguous(), indices.contiguous(), counts.contiguous()
-        self.B, self.nnz = B, indices.numel()
-        self.ix = word_index(self.indptr, indices, V)
-        if self.nnz == 0:   # (no word at all: the entry points still want addresses)
-            indices = torch.zeros(1, dtype=torch.int32, device=dev)
-            counts = torch.zeros(1, dtype=counts.dtype, device=dev)
+        self.B, self.V, self.K, self.nnz = B, V, K, indices.numel()
+        self.indptr, self.indices, self.counts = kernel_documents(indptr, indices, counts)
+        self.ix = word_index(self.indptr, indices.contiguous(), V)
+        if self.nnz == 0:   # (kernel_documents' stand-ins, for the index too)
             self.ix.pos = self.ix.doc = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.indices, self.counts = indices, counts
         self.etheta = torch.empty((B, K), dtype=torch.float64, device=dev)
         self.ratio = torch.empty(max(self.nnz, 1), dtype=torch.float64, device=dev)
+
+
+def _estep_fit(lib, stream, docs, b0, b1, table, gamma0, iters, alpha, tol, cap):
+    """The fit E-step of rows [b0, b1) of ``docs``, from those rows of ``gamma0`` [B x K], into
+    ``docs.etheta``, ``docs.ratio`` and ``iters`` (int32 [B] or None).  A row range needs no copy:
+    indptr, gamma0, etheta and iters go in advanced by b0 rows (8-byte scalar accesses, so any
+    row offset is aligned) with the whole ratio array, where the kernel stores at absolute CSR
+    positions."""
+    _lib.check(lib.gcnk_lda_estep_fit_f64(
+        docs.indptr[b0:].data_ptr(), docs.indices.data_ptr(), docs.counts.data_ptr(), _COUNTS[docs.counts.dtype],
+        b1 - b0, docs.V, docs.K, table.data_ptr(), table.stride(0), alpha, tol, cap, gamma0[b0:].data_ptr(),
+        gamma0.stride(0), docs.nnz, docs.ratio.data_ptr(), docs.etheta[b0:].data_ptr(), docs.etheta.stride(0), None, 0,
+        None if iters is None else iters[b0:].data_ptr(), stream), "gcnk_lda_estep_fit_f64")
 
 
 def _online_pass(lib, stream, docs, lam, table, gamma0, iters, alpha, eta, tol, cap, bs, decay, offset, total, n):
     """One walk over ``docs`` in minibatches of ``bs``: fit E-step on the rows -> online M-step
     -> exp_dirichlet, the table being current on entry and on return.  ``gamma0`` [B x K] and
     ``iters`` (int32 [B] or None) are the walk's; ``n`` is sklearn's n_batch_iter_ on entry ->
-    on return.  A row range needs no copy: the E-step takes indptr, gamma0, etheta and iters
-    advanced by b0 rows (8-byte scalar accesses, so any row offset is aligned) with the whole
-    ratio array, where it stores at absolute CSR positions; the M-step takes the whole index."""
-    K, V = lam.shape
-    B, ix = docs.B, docs.ix
+    on return.  The M-step takes the whole index and the minibatch's row range."""
+    B, V, K, ix = docs.B, docs.V, docs.K, docs.ix
     for b0 in range(0, B, bs):
         b1 = min(b0 + bs, B)
-        _lib.check(lib.gcnk_lda_estep_fit_f64(
-            docs.indptr[b0:].data_ptr(), docs.indices.data_ptr(), docs.counts.data_ptr(), _COUNTS[docs.counts.dtype],
-            b1 - b0, V, K, table.data_ptr(), table.stride(0), alpha, tol, cap, gamma0[b0:].data_ptr(), gamma0.stride(0),
-            docs.nnz, docs.ratio.data_ptr(), docs.etheta[b0:].data_ptr(), docs.etheta.stride(0), None, 0,
-            None if iters is None else iters[b0:].data_ptr(), stream), "gcnk_lda_estep_fit_f64")
+        _estep_fit(lib, stream, docs, b0, b1, table, gamma0, iters, alpha, tol, cap)
         _lib.check(lib.gcnk_lda_mstep_online_f64(
             ix.wptr.data_ptr(), ix.pos.data_ptr(), ix.doc.data_ptr(), docs.nnz, b0, b1, docs.ratio.data_ptr(),
             docs.etheta.data_ptr(), docs.etheta.stride(0), B, V, K, table.data_ptr(), table.stride(0), eta,
@@ -200,12 +223,7 @@ def fit_topics(indptr, indices, counts, V, num_topics=50, max_iter=20, random_st
     learning_decay outside [0, 1], learning_offset < 1, and check_documents' refusals (float32
     counts, CPU tensors, dtypes)."""
     K, V, max_iter, cap = int(num_topics), int(V), int(max_iter), int(max_doc_update_iter)
-    if not 1 <= K <= MAX_TOPICS:
-        raise RuntimeError(f"fit_topics: num_topics={K} is outside [1, {MAX_TOPICS}] (unsupported: two topics a lane)")
-    if max_iter < 1 or V < 1:
-        raise RuntimeError(f"fit_topics: needs max_iter >= 1 and V >= 1 (max_iter={max_iter} V={V})")
-    if not 0 <= cap <= MAX_UPDATE_ITER:
-        raise RuntimeError(f"fit_topics: max_doc_update_iter={cap} is outside [0, {MAX_UPDATE_ITER}]")
+    _check_model("fit_topics", K, cap, max_iter=max_iter, V=V)
     if learning_method not in ("batch", "online"):
         raise RuntimeError(f"fit_topics: learning_method={learning_method!r} is neither 'batch' nor 'online'")
     online = learning_method == "online"
@@ -218,10 +236,9 @@ def fit_topics(indptr, indices, counts, V, num_topics=50, max_iter=20, random_st
     tol = float(mean_change_tol)
 
     if init is None:
-        import numpy as np
-        rs = random_state if isinstance(random_state, np.random.RandomState) else np.random.RandomState(random_state)
-        lam0 = torch.from_numpy(rs.gamma(100.0, 0.01, (K, V))).to(dev)
-        gamma0s = torch.from_numpy(rs.gamma(100.0, 0.01, (max_iter, B, K))).to(dev)
+        rs = _random_state(random_state)
+        lam0 = _draw(rs, (K, V), dev)
+        gamma0s = _draw(rs, (max_iter, B, K), dev)
     else:
         if not isinstance(init, (tuple, list)) or len(init) != 2:
             raise RuntimeError("init must be (lambda0 [K x V], gamma0s [max_iter x B x K])")
@@ -229,13 +246,10 @@ def fit_topics(indptr, indices, counts, V, num_topics=50, max_iter=20, random_st
         gamma0s = _init_tensor(init[1], "gamma0s", (max_iter, B, K), dev)
 
     docs = _Documents(indptr, indices, counts, B, V, K)
-    indptr, indices, counts, nnz, ix, etheta, ratio = (docs.indptr, docs.indices, docs.counts, docs.nnz, docs.ix,
-                                                       docs.etheta, docs.ratio)
-    table = _table_for(K, V, dev)
+    table = model_table(K, V, dev)
     iters = torch.empty((max_iter, B), dtype=torch.int32, device=dev) if return_iterations else None
 
     lib = _lib.load()
-    ldt = table.stride(0)
     with torch.cuda.device(dev):
         stream = _lib.stream(dev)
         if online:
@@ -247,18 +261,15 @@ def fit_topics(indptr, indices, counts, V, num_topics=50, max_iter=20, random_st
                                  alpha, eta, tol, cap, bs, decay, offset, B, n)
         else:
             lam = torch.empty((K, V), dtype=torch.float64, device=dev)
+            ix = docs.ix
             for it in range(max_iter):
                 _exp_dirichlet(lib, stream, lam0 if it == 0 else lam, table)
-                g0 = gamma0s[it]
-                _lib.check(lib.gcnk_lda_estep_fit_f64(
-                    indptr.data_ptr(), indices.data_ptr(), counts.data_ptr(), _COUNTS[counts.dtype], B, V, K,
-                    table.data_ptr(), ldt, alpha, tol, cap, g0.data_ptr(), g0.stride(0), nnz, ratio.data_ptr(),
-                    etheta.data_ptr(), etheta.stride(0), None, 0, None if iters is None else iters[it].data_ptr(),
-                    stream), "gcnk_lda_estep_fit_f64")
+                _estep_fit(lib, stream, docs, 0, B, table, gamma0s[it], None if iters is None else iters[it], alpha, tol,
+                           cap)
                 _lib.check(lib.gcnk_lda_mstep_f64(
-                    ix.wptr.data_ptr(), ix.pos.data_ptr(), ix.doc.data_ptr(), nnz, ratio.data_ptr(), etheta.data_ptr(),
-                    etheta.stride(0), B, V, K, table.data_ptr(), ldt, eta, lam.data_ptr(), lam.stride(0), stream),
-                    "gcnk_lda_mstep_f64")
+                    ix.wptr.data_ptr(), ix.pos.data_ptr(), ix.doc.data_ptr(), docs.nnz, docs.ratio.data_ptr(),
+                    docs.etheta.data_ptr(), docs.etheta.stride(0), B, V, K, table.data_ptr(), table.stride(0), eta,
+                    lam.data_ptr(), lam.stride(0), stream), "gcnk_lda_mstep_f64")
             _exp_dirichlet(lib, stream, lam, table)
             n = 1 + max_iter
 
@@ -289,14 +300,8 @@ class OnlineTopics:
     def __init__(self, V, num_topics=50, total_samples=1e6, batch_size=128, learning_decay=0.7, learning_offset=10.0,
                  random_state=42, doc_topic_prior=None, topic_word_prior=None, mean_change_tol=1e-3,
                  max_doc_update_iter=100, device="cuda", init_components=None):
-        import numpy as np
         K, V, cap = int(num_topics), int(V), int(max_doc_update_iter)
-        if not 1 <= K <= MAX_TOPICS:
-            raise RuntimeError(f"OnlineTopics: num_topics={K} is outside [1, {MAX_TOPICS}] (unsupported: two topics a lane)")
-        if V < 1:
-            raise RuntimeError(f"OnlineTopics: needs V >= 1 (V={V})")
-        if not 0 <= cap <= MAX_UPDATE_ITER:
-            raise RuntimeError(f"OnlineTopics: max_doc_update_iter={cap} is outside [0, {MAX_UPDATE_ITER}]")
+        _check_model("OnlineTopics", K, cap, V=V)
         self.batch_size, self.learning_decay, self.learning_offset = _check_online(
             "OnlineTopics", batch_size, learning_decay, learning_offset)
         self.total_samples = float(total_samples)
@@ -308,12 +313,12 @@ class OnlineTopics:
         self.mean_change_tol, self.max_doc_update_iter = float(mean_change_tol), cap
         self.n_batch_iter = 1
         self.iterations = None
-        self._rs = random_state if isinstance(random_state, np.random.RandomState) else np.random.RandomState(random_state)
+        self._rs = _random_state(random_state)
         if init_components is None:
             dev = torch.device(device)
             if dev.type != "cuda":
                 raise RuntimeError(f"OnlineTopics needs a ROCm GPU device, got {dev}")
-            self._lam = torch.from_numpy(self._rs.gamma(100.0, 0.01, (K, V))).to(dev)
+            self._lam = _draw(self._rs, (K, V), dev)
         else:
             require_device(init_components, "init_components")
             self._lam = _init_tensor(init_components, "init_components", (K, V), init_components.device).clone()
@@ -335,7 +340,7 @@ class OnlineTopics:
 
     def _current_table(self, lib, stream):
         if self._table is None:
-            self._table = _table_for(self.num_topics, self.V, self._lam.device)
+            self._table = model_table(self.num_topics, self.V, self._lam.device)
             _exp_dirichlet(lib, stream, self._lam, self._table)
         return self._table
 
@@ -347,7 +352,7 @@ class OnlineTopics:
         K, V, dev = self.num_topics, self.V, self._lam.device
         B = check_documents(indptr, indices, counts, dev)
         if gamma0 is None:
-            g0 = torch.from_numpy(self._rs.gamma(100.0, 0.01, (B, K))).to(dev)
+            g0 = _draw(self._rs, (B, K), dev)
         else:
             g0 = _init_tensor(gamma0, "gamma0", (B, K), dev)
         docs = _Documents(indptr, indices, counts, B, V, K)

@@ -71,6 +71,21 @@ def check_documents(indptr, indices, counts, device=None):
     return B
 
 
+def model_table(K, V, device):
+    """The zeroed [V x even(K)] float64 table the kernels read: a word's K values are one row of 16-byte pairs."""
+    return torch.zeros((V, (K + 1) // 2 * 2), dtype=torch.float64, device=device)
+
+
+def kernel_documents(indptr, indices, counts):
+    """-> contiguous (indptr, indices, counts) as the entry points take them.  With no word at all,
+    indices and counts are one-element stand-ins: the entry points still want addresses."""
+    indptr, indices, counts = indptr.contiguous(), indices.contiguous(), counts.contiguous()
+    if indices.numel() == 0:
+        indices = torch.zeros(1, dtype=torch.int32, device=indptr.device)
+        counts = torch.zeros(1, dtype=counts.dtype, device=indptr.device)
+    return indptr, indices, counts
+
+
 class TopicInferencer:
     """theta of unseen documents under a fitted LDA model.
 
@@ -122,7 +137,7 @@ class TopicInferencer:
         K, V = src.shape
         tb = _Table()
         tb.K, tb.V, tb.pinned = K, V, False
-        tb.t = torch.zeros((V, (K + 1) // 2 * 2), dtype=torch.float64, device=src.device)
+        tb.t = model_table(K, V, src.device)
         lib = _lib.load()
         name = "gcnk_lda_exp_dirichlet_f64" if self._lambda else "gcnk_lda_table_from_exp_f64"
         with torch.cuda.device(src.device):
@@ -140,10 +155,7 @@ class TopicInferencer:
         tb = self._table()
         dev = tb.t.device
         B = check_documents(indptr, indices, counts, dev)
-        indptr, indices, counts = indptr.contiguous(), indices.contiguous(), counts.contiguous()
-        if indices.numel() == 0:   # (no word at all: the entry point still wants two addresses)
-            indices = torch.zeros(1, dtype=torch.int32, device=dev)
-            counts = torch.zeros(1, dtype=counts.dtype, device=dev)
+        indptr, indices, counts = kernel_documents(indptr, indices, counts)
         K = tb.K
         out = {}
         if theta:

@@ -9,7 +9,7 @@ Stored: the document-term matrix the reference's CountVectorizer gives (indptr /
 int64, V), the reference's components_ (lambda, [8 x V] float64) and its row-normalised
 topic_word_distribution, doc_topic_prior_, topic_word_prior_, mean_change_tol, max_doc_update_iter,
 random_state; lambda0 and the three gamma0 draws of RandomState(42) in sklearn's order; the update counts
-of tests/lda_fit_ref.py's restatement per EM iteration (int32 [3 x 200]) and its smallest stop margin; and
+of tests/lda_ref.py's restatement per EM iteration (int32 [3 x 200]) and its smallest stop margin; and
 two measured distances of the restatement's lambda (max relative):
   d_ref   to the reference's components_;
   d_perm  to the restatement run with every document's words randomly permuted (a pure reorder of sums).
@@ -31,7 +31,7 @@ def main():
     sys.path.insert(0, REF)
     sys.path.insert(0, os.path.dirname(HERE))
     import numpy as np
-    import lda_fit_ref
+    import lda_ref as lda_fit_ref
     quiet = io.StringIO()
     with contextlib.redirect_stdout(quiet), contextlib.redirect_stderr(quiet):
         import topic_model

@@ -14,7 +14,7 @@ own vectoriser is asserted to give the same matrix).  Three runs, keys prefixed 
                              random_state=42).fit(X)   (minibatches 64, 64, 64, 8)
   c  sklearn's partial_fit   (..., total_samples=1000, batch_size=64): partial_fit(X); partial_fit(X[:70])
 
-For each: components_ [8 x V] float64 and n_batch_iter_; the update counts of tests/lda_online_ref.py's
+For each: components_ [8 x V] float64 and n_batch_iter_; the update counts of tests/lda_ref.py's
 restatement (int32 [3 x 200] for a and b, [270] for c: the two calls one after the other) and its smallest stop
 margin; and two measured distances of the restatement's lambda (max relative):
   d_ref   to components_;
@@ -44,15 +44,15 @@ def main():
     import scipy.sparse as sp
     from sklearn.decomposition import LatentDirichletAllocation
     import lda_cases
-    import lda_fit_ref
-    import lda_online_ref as ref
+    import lda_ref as lda_fit_ref
+    import lda_ref as ref
     quiet = io.StringIO()
     with contextlib.redirect_stdout(quiet), contextlib.redirect_stderr(quiet):
         import topic_model
         docs = topic_model.load_documents_from_file(os.path.join(REF, "data", "text_dataset", "clean_corpus", "R8.txt"))
         tm = topic_model.TopicModel(num_topics=NTOPIC, max_iter=MAX_ITER, random_state=SEED, learning_method="online")
         tm.fit(docs[:NFIT])
-    z = lda_fit_ref.load_golden()
+    z = lda_fit_ref.load_fit_golden()
     X = tm.vectorizer.transform(docs[:NFIT]).tocsr()
     indptr, indices, counts = z["indptr"], z["indices"], z["counts"]
     assert X.has_sorted_indices and np.array_equal(X.indptr, indptr) and np.array_equal(X.indices, indices)

@@ -61,6 +61,13 @@ def _case(name, K, V, lengths, seed, counts="several", sort=True, alpha=None, to
                 indptr=indptr, indices=indices, counts=data)
 
 
+def csr_of(has):
+    """bool [B x V], which document holds which word -> (indptr, indices) int32, a document's words ascending."""
+    indptr = np.concatenate([[0], np.cumsum(has.sum(1))]).astype(np.int32)
+    indices = np.concatenate([np.flatnonzero(r) for r in has]).astype(np.int32) if has.any() else np.zeros(0, np.int32)
+    return indptr, indices
+
+
 @functools.lru_cache(maxsize=None)
 def table():
     """name -> case, in a fixed order."""

@@ -1,5 +1,5 @@
 """The case tables of the LDA fit's two launches (csrc/lda_estep.hip: the fit E-step and the M-step): seeded
-synthetic inputs at the smallest shapes where the kernels can go wrong, with tests/lda_fit_ref.py's result
+synthetic inputs at the smallest shapes where the kernels can go wrong, with tests/lda_ref.py's result
 for each, computed once.
 
 Fit E-step (lda_cases.py's models and documents, plus a gamma0 ~ Gamma(100, .01) draw per document):
@@ -22,7 +22,7 @@ import functools
 import numpy as np
 
 import lda_cases
-import lda_fit_ref
+import lda_ref
 
 KS = lda_cases.KS
 LENGTHS = (0, 1, 63, 64, 65, 199)
@@ -59,10 +59,10 @@ ESTEP_NAMES = tuple(estep_table())
 
 @functools.lru_cache(maxsize=None)
 def estep_reference(name):
-    """lda_fit_ref.estep_fit of the case: (gamma, etheta, ratio, iters, margin); computed once, read-only."""
+    """lda_ref.estep of the case: (gamma, etheta, ratio, iters, margin); computed once, read-only."""
     c = estep_table()[name]
-    out = lda_fit_ref.estep_fit(c["indptr"], c["indices"], c["counts"], c["beta"], c["gamma0"], c["alpha"], c["tol"],
-                                c["max_iter"])
+    out = lda_ref.estep(c["indptr"], c["indices"], c["counts"], c["beta"], c["gamma0"], c["alpha"], c["tol"],
+                        c["max_iter"])
     for a in out:
         a.setflags(write=False)
     return out
@@ -89,8 +89,7 @@ def _mstep_case(name, K, B, V, seed, holders=None, density=0.3, empty=()):
     for w, n in (holders or {}).items():
         has[:, w] = np.arange(B) < n
     has[list(empty), :] = False
-    indptr = np.concatenate([[0], np.cumsum(has.sum(1))]).astype(np.int32)
-    indices = np.concatenate([np.flatnonzero(r) for r in has]).astype(np.int32) if has.any() else np.zeros(0, np.int32)
+    indptr, indices = lda_cases.csr_of(has)
     return dict(name=name, K=K, B=B, V=V, indptr=indptr, indices=indices, eta=1.0 / K,
                 etheta=rng.uniform(1e-3, 1.0, (B, K)), ratio=rng.gamma(2.0, 3.0, indices.size),
                 beta=rng.gamma(0.3, 1.0, (K, V)) + 1e-3)
@@ -119,7 +118,7 @@ MSTEP_NAMES = tuple(mstep_table())
 @functools.lru_cache(maxsize=None)
 def mstep_reference(name):
     c = mstep_table()[name]
-    lam = lda_fit_ref.mstep(c["indptr"], c["indices"], c["ratio"], c["etheta"], c["beta"], c["eta"])
+    lam = lda_ref.mstep(c["indptr"], c["indices"], c["ratio"], c["etheta"], c["beta"], c["eta"])
     lam.setflags(write=False)
     return lam
 
@@ -127,10 +126,10 @@ def mstep_reference(name):
 @functools.lru_cache(maxsize=None)
 def golden_fit():
     """The restatement's fit of the R8 fixture from its stored draws: (lambda, iterations, margin)."""
-    z = lda_fit_ref.load_golden()
-    lam, iters, margin = lda_fit_ref.fit(z["indptr"], z["indices"], z["counts"], z["lambda0"], z["gamma0"],
-                                         float(z["doc_topic_prior_"]), float(z["topic_word_prior_"]),
-                                         float(z["mean_change_tol"]), int(z["max_doc_update_iter"]))
+    z = lda_ref.load_fit_golden()
+    lam, iters, margin = lda_ref.fit(z["indptr"], z["indices"], z["counts"], z["lambda0"], z["gamma0"],
+                                     float(z["doc_topic_prior_"]), float(z["topic_word_prior_"]),
+                                     float(z["mean_change_tol"]), int(z["max_doc_update_iter"]))
     lam.setflags(write=False)
     iters.setflags(write=False)
     return lam, iters, margin

@@ -1,5 +1,5 @@
 """The case table of the online M-step (csrc/lda_estep.hip, gcnk_lda_mstep_online_f64): seeded synthetic inputs at
-the smallest shapes where the kernel can go wrong, with tests/lda_online_ref.py's serial loop for each, computed
+the smallest shapes where the kernel can go wrong, with tests/lda_ref.py's serial loop for each, computed
 once.  etheta, ratio, beta and lambda are seeded positive numbers: the launch is checked on identical inputs, bit
 for bit.  The etheta rows of the documents OUTSIDE [doc_lo, doc_hi) are NaN: a search that is off by one entry on
 either side poisons a sum instead of moving it a little.
@@ -21,8 +21,9 @@ import itertools
 
 import numpy as np
 
+import lda_cases
 import lda_fit_cases
-import lda_online_ref
+import lda_ref
 
 KS = (1, 50, 64, 65, 128)
 IN_RANGE = tuple(n for n in lda_fit_cases.CHAINS if n not in (47, 48, 49, 79, 80, 81))
@@ -36,8 +37,7 @@ def _case(name, K, has, doc_lo, doc_hi, rho, doc_ratio, seed, pad=0):
     """has: bool [B x V], which document holds which word."""
     rng = np.random.default_rng(seed)
     B, V = has.shape
-    indptr = np.concatenate([[0], np.cumsum(has.sum(1))]).astype(np.int32)
-    indices = np.concatenate([np.flatnonzero(r) for r in has]).astype(np.int32) if has.any() else np.zeros(0, np.int32)
+    indptr, indices = lda_cases.csr_of(has)
     etheta = rng.uniform(1e-3, 1.0, (B, K))
     etheta[:doc_lo] = np.nan
     etheta[doc_hi:] = np.nan
@@ -98,9 +98,9 @@ NAMES = tuple(table())
 
 @functools.lru_cache(maxsize=None)
 def reference(name):
-    """lda_online_ref.mstep_online of the case: the new lambda [K x V]; computed once, read-only."""
+    """lda_ref.mstep_online of the case: the new lambda [K x V]; computed once, read-only."""
     c = table()[name]
-    lam = lda_online_ref.mstep_online(c["indptr"], c["indices"], c["ratio"], c["etheta"], c["beta"], c["lam"], c["eta"],
-                                      c["rho"], c["doc_ratio"], c["doc_lo"], c["doc_hi"])
+    lam = lda_ref.mstep_online(c["indptr"], c["indices"], c["ratio"], c["etheta"], c["beta"], c["lam"], c["eta"], c["rho"],
+                               c["doc_ratio"], c["doc_lo"], c["doc_hi"])
     lam.setflags(write=False)
     return lam

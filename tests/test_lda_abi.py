@@ -1,8 +1,5 @@
 """gcnk_lda_* without a GPU: declared, exported and bound within ABI 13, and every refusal -- of the entry
 points and of the Python layer -- before any HIP call, with its reason in gcnk_last_error."""
-import os
-import re
-
 import numpy as np
 import pytest
 import torch
@@ -10,38 +7,22 @@ import torch
 import gcn_amd
 from graph_convolutional_networks_for_text_classification_amd import TopicInferencer, _lib, doc_term, topic_infer
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from lda_abi import PTR, assert_declared_exported_bound, call, header, kernels_source
+
 NAMES = {"gcnk_lda_max_topics": 0, "gcnk_lda_tile_words": 0, "gcnk_lda_docs_per_block": 0,
          "gcnk_lda_exp_dirichlet_f64": 7, "gcnk_lda_table_from_exp_f64": 7, "gcnk_lda_estep_f64": 22}
-PTR = 0x10000   # an aligned address that no refused call dereferences
 ESTEP = "gcnk_lda_estep_f64"
 
 
-def _estep(indptr=PTR, indices=PTR, counts=PTR, kind=0, B=8, V=100, K=16, table=PTR, ldt=None, alpha=0.1, tol=1e-3,
-           max_iter=100, theta=PTR, ldth=None, gamma=None, iters=None, x=None, ldx=None, a=None, lda=None, thr=0.02):
-    lib = _lib.load()
-    kp = (K + 1) // 2 * 2
-    rc = lib.gcnk_lda_estep_f64(indptr, indices, counts, kind, B, V, K, table, kp if ldt is None else ldt, alpha, tol,
-                                max_iter, theta, K if ldth is None else ldth, gamma, iters, x,
-                                K if ldx is None else ldx, a, K if lda is None else lda, thr, None)
-    return rc, lib.gcnk_last_error().decode()
+def _estep(**kw):
+    return call(ESTEP, **kw)
 
 
 def test_symbols_declared_exported_and_bound():
-    with open(os.path.join(ROOT, "include", "gcnk.h")) as f:
-        text = f.read()
-    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    lib = _lib.load()
-    for name, nargs in NAMES.items():
-        assert re.search(r"\b" + name + r"\s*\(", src), name
-        assert name in _lib.SIGNATURES and len(_lib.SIGNATURES[name][1]) == nargs
-        assert name in _lib.NEWER_THAN_SOME_VARIANTS
-        fn = getattr(lib, name)
-        assert fn.argtypes == _lib.SIGNATURES[name][1] and fn.restype is _lib.SIGNATURES[name][0]
-    assert lib.gcnk_abi_version() == _lib.ABI_VERSION == 13
+    assert_declared_exported_bound(NAMES)
+    text = header()[0]
     assert "topic_model.py:133-164" in text and "gcnk_lda_" in text.split("#define GCNK_ABI_VERSION")[0]
-    with open(os.path.join(ROOT, "graph-convolutional-networks-for-text-classification_amd", "csrc", "Makefile")) as f:
-        assert "lda_estep.hip" in f.read()
+    assert ESTEP in kernels_source()
 
 
 def test_constants_and_public_names():
@@ -72,15 +53,11 @@ def test_unsupported_sizes_are_refused_before_any_hip_call():
 
 @pytest.mark.parametrize("fn", ["gcnk_lda_exp_dirichlet_f64", "gcnk_lda_table_from_exp_f64"])
 def test_table_builders_refuse(fn):
-    lib = _lib.load()
-    f = getattr(lib, fn)
-    good = dict(src=PTR, ld=100, K=16, V=100, table=PTR, ldt=16)
     for kw, want in ((dict(src=None), _lib.EARG), (dict(ld=99), _lib.EARG), (dict(K=0), _lib.EARG),
                      (dict(K=129, ldt=130), _lib.EUNSUP), (dict(V=0), _lib.EARG), (dict(table=None), _lib.EARG),
                      (dict(ldt=15), _lib.EARG), (dict(ldt=17), _lib.EARG), (dict(table=PTR + 8), _lib.EARG)):
-        a = dict(good, **kw)
-        assert f(a["src"], a["ld"], a["K"], a["V"], a["table"], a["ldt"], None) == want, kw
-        assert fn in lib.gcnk_last_error().decode()
+        rc, msg = call(fn, **kw)
+        assert rc == want and fn in msg, kw
 
 
 def test_python_refusals_that_need_no_device():

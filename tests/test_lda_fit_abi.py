@@ -1,58 +1,31 @@
 """The LDA fit's entry points without a GPU: gcnk_lda_estep_fit_f64 and gcnk_lda_mstep_f64 declared, exported
 and bound within ABI 13, every refusal of both before any HIP call with its reason in gcnk_last_error, and
 the public names."""
-import os
-import re
-
 import pytest
 import torch
 
 import gcn_amd
 from graph_convolutional_networks_for_text_classification_amd import TopicFit, _lib, fit_topics, topic_fit, topic_infer
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from lda_abi import PTR, assert_declared_exported_bound, call, header, kernels_source
+
 NAMES = {"gcnk_lda_words_per_block": 0, "gcnk_lda_estep_fit_f64": 22, "gcnk_lda_mstep_f64": 16}
-PTR = 0x10000   # an aligned address that no refused call dereferences
 ESTEP, MSTEP = "gcnk_lda_estep_fit_f64", "gcnk_lda_mstep_f64"
 
 
-def _estep(indptr=PTR, indices=PTR, counts=PTR, kind=0, B=8, V=100, K=16, table=PTR, ldt=None, alpha=0.1, tol=1e-3,
-           max_iter=100, gamma0=PTR, ldg0=None, nnz=50, ratio=PTR, etheta=PTR, lde=None, gamma=None, ldg=0, iters=None):
-    lib = _lib.load()
-    kp = (K + 1) // 2 * 2
-    rc = lib.gcnk_lda_estep_fit_f64(indptr, indices, counts, kind, B, V, K, table, kp if ldt is None else ldt, alpha,
-                                    tol, max_iter, gamma0, K if ldg0 is None else ldg0, nnz, ratio, etheta,
-                                    K if lde is None else lde, gamma, ldg, iters, None)
-    return rc, lib.gcnk_last_error().decode()
+def _estep(**kw):
+    return call(ESTEP, **kw)
 
 
-def _mstep(wptr=PTR, pos=PTR, doc=PTR, nnz=50, ratio=PTR, etheta=PTR, lde=None, B=8, V=100, K=16, table=PTR, ldt=None,
-           eta=0.1, lam=PTR, ldl=None):
-    lib = _lib.load()
-    kp = (K + 1) // 2 * 2
-    rc = lib.gcnk_lda_mstep_f64(wptr, pos, doc, nnz, ratio, etheta, K if lde is None else lde, B, V, K, table,
-                                kp if ldt is None else ldt, eta, lam, V if ldl is None else ldl, None)
-    return rc, lib.gcnk_last_error().decode()
+def _mstep(**kw):
+    return call(MSTEP, **kw)
 
 
 def test_symbols_declared_exported_and_bound():
-    with open(os.path.join(ROOT, "include", "gcnk.h")) as f:
-        text = f.read()
-    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    lib = _lib.load()
-    for name, nargs in NAMES.items():
-        assert re.search(r"\b" + name + r"\s*\(", src), name
-        assert name in _lib.SIGNATURES and len(_lib.SIGNATURES[name][1]) == nargs
-        assert name in _lib.NEWER_THAN_SOME_VARIANTS
-        fn = getattr(lib, name)
-        assert fn.argtypes == _lib.SIGNATURES[name][1] and fn.restype is _lib.SIGNATURES[name][0]
+    assert_declared_exported_bound(NAMES)
     assert len(_lib.SIGNATURES["gcnk_lda_estep_f64"][1]) == 22   # the transform's entry point keeps its signature
-    assert lib.gcnk_abi_version() == _lib.ABI_VERSION == 13
-    assert "topic_model.py:74-131" in text
-    with open(os.path.join(ROOT, "graph-convolutional-networks-for-text-classification_amd", "csrc", "Makefile")) as f:
-        assert "lda_estep.hip" in f.read()
-    with open(os.path.join(ROOT, "graph-convolutional-networks-for-text-classification_amd", "csrc", "lda_estep.hip")) as f:
-        kernels = f.read()
+    assert "topic_model.py:74-131" in header()[0]
+    kernels = kernels_source()
     assert MSTEP in kernels and ESTEP in kernels
 
 

@@ -1,18 +1,18 @@
-"""The batch-EM restatement (tests/lda_fit_ref.py) pinned on the CPU to the reference's own fit of 200 R8
+"""The batch-EM restatement (tests/lda_ref.py) pinned on the CPU to the reference's own fit of 200 R8
 documents (tests/golden/lda_fit_r8_small.npz), and the conditions that make the GPU tests' demands fair:
 every document far from the stop rule's edge in every EM iteration, and sklearn's random stream reproduced."""
 import numpy as np
 import pytest
 
 import lda_fit_cases
-import lda_fit_ref
+import lda_ref
 
 MIN_MARGIN = lda_fit_cases.MIN_MARGIN
 
 
 @pytest.fixture(scope="module")
 def golden():
-    return lda_fit_ref.load_golden()
+    return lda_ref.load_fit_golden()
 
 
 def test_fixture_holds_what_the_generator_documents(golden):
@@ -35,7 +35,7 @@ def test_fixture_holds_what_the_generator_documents(golden):
 def test_restatement_against_the_reference_lambda(golden):
     z = golden
     lam, iters, margin = lda_fit_cases.golden_fit()
-    d_ref = lda_fit_ref.max_rel(lam, z["components_"])
+    d_ref = lda_ref.max_rel(lam, z["components_"])
     print(f"max relative |lambda_restatement - lambda_reference| = {d_ref:.3e} (stored {float(z['d_ref']):.3e}); "
           f"d_perm stored {float(z['d_perm']):.3e}; smallest stop margin {margin:.3e}")
     assert d_ref == float(z["d_ref"]) and d_ref < 1e-12
@@ -55,20 +55,20 @@ def test_no_document_stops_near_the_tolerance(golden):
 
 def test_a_reorder_of_every_documents_words_moves_lambda_by_d_perm(golden):
     z = golden
-    pi, pc = lda_fit_ref.permuted(z["indptr"], z["indices"], z["counts"])
+    pi, pc = lda_ref.permuted(z["indptr"], z["indices"], z["counts"])
     assert not np.array_equal(pi, z["indices"])
-    lam_p, iters_p, _ = lda_fit_ref.fit(z["indptr"], pi, pc, z["lambda0"], z["gamma0"], float(z["doc_topic_prior_"]),
+    lam_p, iters_p, _ = lda_ref.fit(z["indptr"], pi, pc, z["lambda0"], z["gamma0"], float(z["doc_topic_prior_"]),
                                         float(z["topic_word_prior_"]), float(z["mean_change_tol"]),
                                         int(z["max_doc_update_iter"]))
     lam, iters, _ = lda_fit_cases.golden_fit()
     assert np.array_equal(iters_p, iters)
-    assert lda_fit_ref.max_rel(lam, lam_p) == float(z["d_perm"]) < 1e-12
+    assert lda_ref.max_rel(lam, lam_p) == float(z["d_perm"]) < 1e-12
 
 
 def test_random_state_reproduces_the_stored_draws(golden):
     z = golden
     K, V = z["lambda0"].shape
-    lam0, g0s = lda_fit_ref.draws(int(z["random_state"]), K, V, 200, 3)
+    lam0, g0s = lda_ref.draws(int(z["random_state"]), K, V, 200, 3)
     assert np.array_equal(lam0, z["lambda0"]) and np.array_equal(g0s, z["gamma0"])
 
 
@@ -92,7 +92,7 @@ def test_restatement_against_sklearn(golden):
     lda = LatentDirichletAllocation(n_components=K, random_state=int(z["random_state"]), max_iter=3,
                                     learning_method="batch").fit(X)
     lam = lda_fit_cases.golden_fit()[0]
-    assert lda_fit_ref.max_rel(lam, lda.components_) < 1e-11
+    assert lda_ref.max_rel(lam, lda.components_) < 1e-11
 
 
 @pytest.mark.parametrize("name", lda_fit_cases.ESTEP_NAMES)
@@ -129,7 +129,7 @@ def test_case_tables_cover_what_they_say():
 
 
 def test_mstep_restatement_is_the_outer_product_accumulate():
-    """lda_fit_ref.mstep against sklearn's own statement: sstats[:, ids] += np.outer(etheta_d, r_d), document
+    """lda_ref.mstep against sklearn's own statement: sstats[:, ids] += np.outer(etheta_d, r_d), document
     by document, then eta + sstats * beta."""
     c = lda_fit_cases.mstep_table()["K16"]
     S = np.zeros((c["K"], c["V"]))

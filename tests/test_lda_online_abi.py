@@ -2,8 +2,6 @@
 ABI 13, every refusal before any HIP call with its reason in gcnk_last_error, the public names, and the Python
 refusals of the online method."""
 import math
-import os
-import re
 
 import pytest
 import torch
@@ -11,37 +9,20 @@ import torch
 import gcn_amd
 from graph_convolutional_networks_for_text_classification_amd import OnlineTopics, TopicFit, _lib, fit_topics, topic_fit
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from lda_abi import PTR, assert_declared_exported_bound, call, header, kernels_source
+
 ONLINE = "gcnk_lda_mstep_online_f64"
 NARGS = 20      # the declaration in include/gcnk.h, counted: 19 operands and the stream
-PTR = 0x10000   # an aligned address that no refused call dereferences
 
 
-def _online(wptr=PTR, pos=PTR, doc=PTR, nnz=50, doc_lo=2, doc_hi=6, ratio=PTR, etheta=PTR, lde=None, B=8, V=100, K=16,
-            table=PTR, ldt=None, eta=0.1, rho=0.5, doc_ratio=4.0, lam=PTR, ldl=None):
-    lib = _lib.load()
-    kp = (K + 1) // 2 * 2
-    rc = lib.gcnk_lda_mstep_online_f64(wptr, pos, doc, nnz, doc_lo, doc_hi, ratio, etheta, K if lde is None else lde, B, V,
-                                       K, table, kp if ldt is None else ldt, eta, rho, doc_ratio, lam,
-                                       V if ldl is None else ldl, None)
-    return rc, lib.gcnk_last_error().decode()
+def _online(**kw):
+    return call(ONLINE, **kw)
 
 
 def test_symbol_declared_exported_and_bound():
-    with open(os.path.join(ROOT, "include", "gcnk.h")) as f:
-        text = f.read()
-    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    decl = re.search(r"\b" + ONLINE + r"\s*\(([^)]*)\)", src)
-    assert decl and len(decl.group(1).split(",")) == NARGS
-    assert ONLINE in _lib.SIGNATURES and len(_lib.SIGNATURES[ONLINE][1]) == NARGS
-    assert ONLINE in _lib.NEWER_THAN_SOME_VARIANTS
-    lib = _lib.load()
-    fn = getattr(lib, ONLINE)
-    assert fn.argtypes == _lib.SIGNATURES[ONLINE][1] and fn.restype is _lib.SIGNATURES[ONLINE][0]
-    assert lib.gcnk_abi_version() == _lib.ABI_VERSION == 13
-    assert "_em_step(batch_update=False)" in text
-    with open(os.path.join(ROOT, "graph-convolutional-networks-for-text-classification_amd", "csrc", "lda_estep.hip")) as f:
-        kernels = f.read()
+    assert_declared_exported_bound({ONLINE: NARGS})
+    assert "_em_step(batch_update=False)" in header()[0]
+    kernels = kernels_source()
     assert ONLINE in kernels
     # one summation chain, which both M-step kernels instantiate
     assert kernels.count("void mstep_chain(") == 1 and kernels.count("mstep_chain<kTwo>(") == 2

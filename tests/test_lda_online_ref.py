@@ -1,4 +1,4 @@
-"""The online-EM restatement (tests/lda_online_ref.py) pinned on the CPU to the reference's own online fit of 200
+"""The online-EM restatement (tests/lda_ref.py) pinned on the CPU to the reference's own online fit of 200
 R8 documents and to sklearn's online fit and partial_fit (tests/golden/lda_online_r8_small.npz), and the
 conditions that make the GPU tests' demands fair: every document far from the stop rule's edge in every
 minibatch, sklearn's random stream reproduced slice by slice, and the case table holding what it says."""
@@ -8,9 +8,8 @@ import numpy as np
 import pytest
 
 import lda_fit_cases
-import lda_fit_ref
+import lda_ref
 import lda_online_cases
-import lda_online_ref
 
 MIN_MARGIN = lda_fit_cases.MIN_MARGIN
 RUNS = {"a": 128, "b": 64}     # fit runs: key -> batch_size
@@ -18,23 +17,23 @@ RUNS = {"a": 128, "b": 64}     # fit runs: key -> batch_size
 
 @pytest.fixture(scope="module")
 def golden():
-    return lda_fit_ref.load_golden(), lda_online_ref.load_golden()
+    return lda_ref.load_fit_golden(), lda_ref.load_online_golden()
 
 
 @functools.lru_cache(maxsize=None)
 def _restated(key):
     """The restatement's run of fixture run `key`: (lambda, iterations, margin, n_batch_iter)."""
-    z, o = lda_fit_ref.load_golden(), lda_online_ref.load_golden()
+    z, o = lda_ref.load_fit_golden(), lda_ref.load_online_golden()
     alpha, eta = float(z["doc_topic_prior_"]), float(z["topic_word_prior_"])
     tol, cap = float(z["mean_change_tol"]), int(z["max_doc_update_iter"])
     docs = (z["indptr"], z["indices"], z["counts"])
     if key in RUNS:
-        return lda_online_ref.fit_online(*docs, z["lambda0"], z["gamma0"], alpha, eta, RUNS[key], 0.7, 10.0, tol, cap)
+        return lda_ref.fit_online(*docs, z["lambda0"], z["gamma0"], alpha, eta, RUNS[key], 0.7, 10.0, tol, cap)
     total, bs, second = int(o["c_total_samples"]), int(o["c_batch_size"]), int(o["c_second"])
     hi = int(z["indptr"][second])
-    lam, i1, m1, n = lda_online_ref.partial_fit(*docs, z["lambda0"], o["c_gamma0"][:200], alpha, eta, total, 1, bs, 0.7,
+    lam, i1, m1, n = lda_ref.partial_fit(*docs, z["lambda0"], o["c_gamma0"][:200], alpha, eta, total, 1, bs, 0.7,
                                                 10.0, tol, cap)
-    lam, i2, m2, n = lda_online_ref.partial_fit(z["indptr"][:second + 1], z["indices"][:hi], z["counts"][:hi], lam,
+    lam, i2, m2, n = lda_ref.partial_fit(z["indptr"][:second + 1], z["indices"][:hi], z["counts"][:hi], lam,
                                                 o["c_gamma0"][200:], alpha, eta, total, n, bs, 0.7, 10.0, tol, cap)
     return lam, np.concatenate([i1, i2]), min(m1, m2), n
 
@@ -60,7 +59,7 @@ def test_fixture_holds_what_the_generator_documents(golden):
 def test_restatement_against_the_recorded_components(golden, key):
     z, o = golden
     lam, iters, margin, n = _restated(key)
-    d_ref = lda_fit_ref.max_rel(lam, o[f"{key}_components_"])
+    d_ref = lda_ref.max_rel(lam, o[f"{key}_components_"])
     print(f"{key}: max relative |lambda_restatement - components_| = {d_ref:.3e} (stored {float(o[f'{key}_d_ref']):.3e}); "
           f"d_perm stored {float(o[f'{key}_d_perm']):.3e}; smallest stop margin {margin:.3e}; n_batch_iter_ {n}")
     assert d_ref == float(o[f"{key}_d_ref"])
@@ -80,7 +79,7 @@ def test_restatement_against_sklearn(golden):
     lda = LatentDirichletAllocation(n_components=K, random_state=int(z["random_state"]), max_iter=3,
                                     learning_method="online", batch_size=64).fit(X)
     lam, _, _, n = _restated("b")
-    assert lda_fit_ref.max_rel(lam, lda.components_) < 1e-11 and n == lda.n_batch_iter_
+    assert lda_ref.max_rel(lam, lda.components_) < 1e-11 and n == lda.n_batch_iter_
 
 
 def test_gamma0_slices_are_sklearns_stream(golden):
@@ -92,22 +91,22 @@ def test_gamma0_slices_are_sklearns_stream(golden):
         rs = np.random.RandomState(int(z["random_state"]))
         assert np.array_equal(rs.gamma(100.0, 0.01, (K, V)), z["lambda0"])
         for it in range(3):
-            for b0, b1 in lda_online_ref.batches(200, bs):
+            for b0, b1 in lda_ref.batches(200, bs):
                 assert np.array_equal(rs.gamma(100.0, 0.01, (b1 - b0, K)), z["gamma0"][it, b0:b1])
     rs = np.random.RandomState(int(z["random_state"]))
     rs.gamma(100.0, 0.01, (K, V))
     for n, off in ((200, 0), (70, 200)):
-        for b0, b1 in lda_online_ref.batches(n, 64):
+        for b0, b1 in lda_ref.batches(n, 64):
             assert np.array_equal(rs.gamma(100.0, 0.01, (b1 - b0, K)), o["c_gamma0"][off + b0:off + b1])
-    assert lda_online_ref.batches(200, 64) == [(0, 64), (64, 128), (128, 192), (192, 200)]
-    assert lda_online_ref.batches(200, 200) == [(0, 200)] and lda_online_ref.batches(3, 7) == [(0, 3)]
+    assert lda_ref.batches(200, 64) == [(0, 64), (64, 128), (128, 192), (192, 200)]
+    assert lda_ref.batches(200, 200) == [(0, 200)] and lda_ref.batches(3, 7) == [(0, 3)]
 
 
 @pytest.mark.parametrize("name", ["K16", "K65", "chains-K50", "empty-documents", "empty-corpus"])
 def test_rho_one_in_one_minibatch_is_the_batch_mstep_bit_for_bit(name):
     c = lda_fit_cases.mstep_table()[name]
     lam = np.random.default_rng(11).gamma(100.0, 0.01, (c["K"], c["V"]))
-    got = lda_online_ref.mstep_online(c["indptr"], c["indices"], c["ratio"], c["etheta"], c["beta"], lam, c["eta"], 1.0, 1.0,
+    got = lda_ref.mstep_online(c["indptr"], c["indices"], c["ratio"], c["etheta"], c["beta"], lam, c["eta"], 1.0, 1.0,
                                       0, c["B"])
     want = lda_fit_cases.mstep_reference(name)
     assert np.array_equal(got.view(np.int64), want.view(np.int64))
@@ -115,7 +114,7 @@ def test_rho_one_in_one_minibatch_is_the_batch_mstep_bit_for_bit(name):
 
 @pytest.mark.parametrize("name", ["range-start", "rho2-ratio1", "empty-documents"])
 def test_mstep_restatement_is_sklearns_dense_update(name):
-    """lda_online_ref.mstep_online against sklearn's own statement on dense arrays: sstats[:, ids] +=
+    """lda_ref.mstep_online against sklearn's own statement on dense arrays: sstats[:, ids] +=
     np.outer(etheta_d, r_d) over the minibatch's documents, sstats *= beta, components *= 1 - rho,
     components += rho * (eta + doc_ratio * sstats)."""
     c = lda_online_cases.table()[name]

@@ -1,5 +1,5 @@
 """fit_topics on the GPU (csrc/lda_estep.hip: the fit E-step, the M-step and their loop) against the float64
-numpy restatement tests/lda_fit_ref.py, itself pinned on the CPU (test_lda_fit_ref.py) to the reference's
+numpy restatement tests/lda_ref.py, itself pinned on the CPU (test_lda_ref.py) to the reference's
 fit and to sklearn.  Expected values never come from the code under test.
 
   fit E-step  update counts EQUAL on every document; gamma, etheta and ratio within lda_fit_cases.bound; a
@@ -14,53 +14,13 @@ import pytest
 import torch
 
 import gcn_amd  # noqa: F401
-from graph_convolutional_networks_for_text_classification_amd import TopicInferencer, _lib, fit_topics, topic_fit
+from graph_convolutional_networks_for_text_classification_amd import TopicInferencer, fit_topics
 
 import lda_fit_cases
-import lda_fit_ref
+import lda_ref
+from lda_gpu import DEV, bits as _bits, dev as _dev, estep_fit as _estep_fit, mstep as _mstep
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int64 if t.dtype == torch.float64 else torch.int32)
-
-
-def _table(beta):
-    """exp(E[log beta]) [K x V] as the kernels read it: transposed, rows padded to an even length."""
-    K, V = beta.shape
-    t = torch.zeros((V, (K + 1) // 2 * 2), dtype=torch.float64, device=DEV)
-    t[:, :K] = _dev(beta).t()
-    return t
-
-
-def _estep_fit(c, indptr=None, indices=None, counts=None, gamma0=None):
-    """gcnk_lda_estep_fit_f64 alone on case c (or on the batch given) -> gamma, etheta, ratio, iters."""
-    indptr = c["indptr"] if indptr is None else indptr
-    indices = c["indices"] if indices is None else indices
-    counts = c["counts"] if counts is None else counts
-    gamma0 = c["gamma0"] if gamma0 is None else gamma0
-    B, K, V, nnz = len(indptr) - 1, c["K"], c["V"], len(indices)
-    table = _table(c["beta"])
-    ip, g0 = _dev(indptr), _dev(gamma0)
-    ix = _dev(indices) if nnz else torch.zeros(1, dtype=torch.int32, device=DEV)
-    ct = _dev(counts) if nnz else torch.zeros(1, dtype=torch.float64, device=DEV)
-    gamma = torch.full((B, K), -1.0, dtype=torch.float64, device=DEV)
-    etheta = torch.full((B, K), -1.0, dtype=torch.float64, device=DEV)
-    ratio = torch.full((max(nnz, 1) + 2,), -1.0, dtype=torch.float64, device=DEV)   # (two guard entries)
-    iters = torch.full((B,), -1, dtype=torch.int32, device=DEV)
-    rc = _lib.load().gcnk_lda_estep_fit_f64(ip.data_ptr(), ix.data_ptr(), ct.data_ptr(), 0, B, V, K, table.data_ptr(),
-                                            table.stride(0), c["alpha"], c["tol"], c["max_iter"], g0.data_ptr(), K, nnz,
-                                            ratio.data_ptr(), etheta.data_ptr(), K, gamma.data_ptr(), K,
-                                            iters.data_ptr(), _lib.stream(torch.device(DEV)))
-    _lib.check(rc, "gcnk_lda_estep_fit_f64")
-    assert float(ratio[nnz:].max()) == -1.0 == float(ratio[nnz:].min())   # nothing stored past the nnz ratios
-    return gamma, etheta, ratio[:nnz], iters
 
 
 _worst = {"estep": 0.0}
@@ -111,21 +71,6 @@ def test_a_documents_fit_outputs_do_not_depend_on_the_batch(name):
         assert torch.equal(_bits(got[2]), _bits(whole[2][ents])) and torch.equal(got[3], whole[3][rows]), order
 
 
-def _mstep(c):
-    B, K, V, nnz = c["B"], c["K"], c["V"], len(c["indices"])
-    ix = topic_fit.word_index(_dev(c["indptr"]), _dev(c["indices"]), V)
-    if nnz == 0:
-        ix.pos = ix.doc = torch.zeros(1, dtype=torch.int32, device=DEV)
-    table, etheta = _table(c["beta"]), _dev(c["etheta"])
-    ratio = _dev(c["ratio"]) if nnz else torch.zeros(1, dtype=torch.float64, device=DEV)
-    lam = torch.full((K, V), -1.0, dtype=torch.float64, device=DEV)
-    rc = _lib.load().gcnk_lda_mstep_f64(ix.wptr.data_ptr(), ix.pos.data_ptr(), ix.doc.data_ptr(), nnz, ratio.data_ptr(),
-                                        etheta.data_ptr(), K, B, V, K, table.data_ptr(), table.stride(0), c["eta"],
-                                        lam.data_ptr(), V, _lib.stream(torch.device(DEV)))
-    _lib.check(rc, "gcnk_lda_mstep_f64")
-    return lam, ix
-
-
 @pytest.mark.parametrize("name", lda_fit_cases.MSTEP_NAMES)
 def test_mstep_is_bit_for_bit_the_serial_loop(name):
     c = lda_fit_cases.mstep_table()[name]
@@ -148,7 +93,7 @@ def test_mstep_is_bit_for_bit_the_serial_loop(name):
 
 @pytest.fixture(scope="module")
 def golden():
-    return lda_fit_ref.load_golden()
+    return lda_ref.load_fit_golden()
 
 
 def _golden_fit(z, init=True, **kw):
@@ -175,8 +120,8 @@ def test_whole_fit_against_the_reference(golden, fitted):
     assert differ.size == 0, f"(EM iteration, document) {differ.tolist()} ran {its[its != z['iterations']]} updates"
     lam = fit.components.cpu().numpy()
     bound = 16.0 * max(float(z["d_ref"]), float(z["d_perm"]))
-    d = lda_fit_ref.max_rel(lam, z["components_"])
-    d_rest = lda_fit_ref.max_rel(lam, lda_fit_cases.golden_fit()[0])
+    d = lda_ref.max_rel(lam, z["components_"])
+    d_rest = lda_ref.max_rel(lam, lda_fit_cases.golden_fit()[0])
     print(f"whole fit: max relative |lambda - reference components_| = {d:.3e} = {d / bound:.4f} of 16 max(d_ref, d_perm) "
           f"= {bound:.3e}; to the restatement {d_rest:.3e}")
     assert d <= bound
@@ -184,10 +129,10 @@ def test_whole_fit_against_the_reference(golden, fitted):
     assert np.abs(tw.sum(1) - 1).max() <= 1e-12
     # lambda_kw / sum_w lambda_kw: the numerator within `bound`, the sum of V positive terms within `bound` and
     # its own V roundings in whatever order, one division
-    assert lda_fit_ref.max_rel(tw, z["topic_word_distribution"]) <= 2 * bound + (V + 1) * 2.0 ** -52
+    assert lda_ref.max_rel(tw, z["topic_word_distribution"]) <= 2 * bound + (V + 1) * 2.0 ** -52
     # the last table is exp_dirichlet of the fitted lambda
-    want = lda_fit_ref.exp_dirichlet(lam)
-    assert lda_fit_ref.max_rel(fit.exp_topic_word.cpu().numpy(), want) <= 8 * 2.0 ** -52 + V * 2.0 ** -53
+    want = lda_ref.exp_dirichlet(lam)
+    assert lda_ref.max_rel(fit.exp_topic_word.cpu().numpy(), want) <= 8 * 2.0 ** -52 + V * 2.0 ** -53
 
 
 def test_host_draw_second_run_and_replay_are_bit_for_bit(golden, fitted):
@@ -231,8 +176,8 @@ def test_fit_of_documents_without_a_word_is_the_prior():
     ct = torch.zeros(0, dtype=torch.float64, device=DEV)
     fit = fit_topics(ip, ix, ct, V, num_topics=K, max_iter=2, random_state=3, topic_word_prior=0.3, return_iterations=True)
     assert torch.equal(fit.components, torch.full((K, V), 0.3, dtype=torch.float64, device=DEV))
-    lam0, g0s = lda_fit_ref.draws(3, K, V, B, 2)
-    lam, iters, _ = lda_fit_ref.fit(np.zeros(B + 1, np.int32), np.zeros(0, np.int32), np.zeros(0), lam0, g0s, 1.0 / K, 0.3)
+    lam0, g0s = lda_ref.draws(3, K, V, B, 2)
+    lam, iters, _ = lda_ref.fit(np.zeros(B + 1, np.int32), np.zeros(0, np.int32), np.zeros(0), lam0, g0s, 1.0 / K, 0.3)
     assert np.all(lam == 0.3) and np.array_equal(fit.iterations.cpu().numpy(), iters)
     assert float((fit.topic_word_distribution.sum(1) - 1).abs().max()) <= 1e-12
 

@@ -1,6 +1,6 @@
 """The online topic-model fit on the GPU (csrc/lda_estep.hip: gcnk_lda_mstep_online_f64, and the minibatch loop
 of fit_topics(learning_method="online") and OnlineTopics.partial_fit) against the float64 numpy restatement
-tests/lda_online_ref.py, itself pinned on the CPU (test_lda_online_ref.py) to the reference's online fit and to
+tests/lda_ref.py, itself pinned on the CPU (test_lda_ref.py) to the reference's online fit and to
 sklearn.  Expected values never come from the code under test.
 
   online M-step  on the restatement's own inputs, lambda BIT FOR BIT the serial loop's: every operation is a
@@ -20,47 +20,11 @@ import gcn_amd  # noqa: F401
 from graph_convolutional_networks_for_text_classification_amd import (OnlineTopics, TopicInferencer, _lib, fit_topics,
                                                                       topic_fit)
 
-import lda_fit_ref
 import lda_online_cases
-import lda_online_ref
+import lda_ref
+from lda_gpu import DEV, GUARD, bits as _bits, dev as _dev, mstep_online as _mstep_online
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-GUARD = -1.0
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int64 if t.dtype == torch.float64 else torch.int32)
-
-
-def _table(beta):
-    """exp(E[log beta]) [K x V] as the kernels read it: transposed, rows padded to an even length."""
-    K, V = beta.shape
-    t = torch.zeros((V, (K + 1) // 2 * 2), dtype=torch.float64, device=DEV)
-    t[:, :K] = _dev(beta).t()
-    return t
-
-
-def _mstep_online(c):
-    """gcnk_lda_mstep_online_f64 alone on case c -> lambda [K x (V + pad)], the guard columns included."""
-    B, K, V, nnz = c["B"], c["K"], c["V"], len(c["indices"])
-    ix = topic_fit.word_index(_dev(c["indptr"]), _dev(c["indices"]), V)
-    if nnz == 0:
-        ix.pos = ix.doc = torch.zeros(1, dtype=torch.int32, device=DEV)
-    table, etheta = _table(c["beta"]), _dev(c["etheta"])
-    ratio = _dev(c["ratio"]) if nnz else torch.zeros(1, dtype=torch.float64, device=DEV)
-    lam = torch.full((K, V + c["pad"]), GUARD, dtype=torch.float64, device=DEV)
-    lam[:, :V] = _dev(c["lam"])
-    rc = _lib.load().gcnk_lda_mstep_online_f64(
-        ix.wptr.data_ptr(), ix.pos.data_ptr(), ix.doc.data_ptr(), nnz, c["doc_lo"], c["doc_hi"], ratio.data_ptr(),
-        etheta.data_ptr(), K, B, V, K, table.data_ptr(), table.stride(0), c["eta"], c["rho"], c["doc_ratio"],
-        lam.data_ptr(), lam.stride(0), _lib.stream(torch.device(DEV)))
-    _lib.check(rc, "gcnk_lda_mstep_online_f64")
-    return lam
 
 
 @pytest.mark.parametrize("name", lda_online_cases.NAMES)
@@ -80,7 +44,7 @@ def test_online_mstep_is_bit_for_bit_the_serial_loop(name):
 
 @pytest.fixture(scope="module")
 def golden():
-    return lda_fit_ref.load_golden(), lda_online_ref.load_golden()
+    return lda_ref.load_fit_golden(), lda_ref.load_online_golden()
 
 
 @pytest.fixture(scope="module")
@@ -130,7 +94,7 @@ def test_whole_online_fit_against_the_reference(golden, fitted, key):
     assert fit.n_batch_iter == int(o[f"{key}_n_batch_iter_"]) and fit.n_iter == 3
     lam = fit.components.cpu().numpy()
     bound = 16.0 * max(float(o[f"{key}_d_ref"]), float(o[f"{key}_d_perm"]))
-    d = lda_fit_ref.max_rel(lam, want)
+    d = lda_ref.max_rel(lam, want)
     print(f"online fit {key}: max relative |lambda - recorded components_| = {d:.3e} = {d / bound:.4f} of "
           f"16 max(d_ref, d_perm) = {bound:.3e}")
     assert d <= bound
@@ -139,9 +103,9 @@ def test_whole_online_fit_against_the_reference(golden, fitted, key):
     # test_whole_fit_against_the_reference's two bounds: lambda_kw / sum_w lambda_kw, the numerator within `bound`,
     # the sum of V positive terms within `bound` and its own V roundings in whatever order, one division;
     want_tw = o["a_topic_word_distribution"] if key == "a" else want / want.sum(axis=1, keepdims=True)
-    assert lda_fit_ref.max_rel(tw, want_tw) <= 2 * bound + (V + 1) * 2.0 ** -52
+    assert lda_ref.max_rel(tw, want_tw) <= 2 * bound + (V + 1) * 2.0 ** -52
     # and the last table is exp_dirichlet of the fitted lambda
-    assert lda_fit_ref.max_rel(fit.exp_topic_word.cpu().numpy(), lda_fit_ref.exp_dirichlet(lam)) <= 8 * 2.0 ** -52 + V * 2.0 ** -53
+    assert lda_ref.max_rel(fit.exp_topic_word.cpu().numpy(), lda_ref.exp_dirichlet(lam)) <= 8 * 2.0 ** -52 + V * 2.0 ** -53
 
 
 def _online_topics(z, o, **kw):
@@ -169,12 +133,12 @@ def test_two_partial_fit_calls_against_sklearn(golden, docs):
     assert np.array_equal(np.concatenate(its), o["c_iterations"])
     lam = ot.components.cpu().numpy()
     bound = 16.0 * max(float(o["c_d_ref"]), float(o["c_d_perm"]))
-    d = lda_fit_ref.max_rel(lam, o["c_components_"])
+    d = lda_ref.max_rel(lam, o["c_components_"])
     print(f"two partial_fit calls: max relative |lambda - sklearn's components_| = {d:.3e} = {d / bound:.4f} of "
           f"16 max(d_ref, d_perm) = {bound:.3e}")
     assert d <= bound
     V = int(z["V"])
-    assert lda_fit_ref.max_rel(ot.exp_topic_word.cpu().numpy(), lda_fit_ref.exp_dirichlet(lam)) <= 8 * 2.0 ** -52 + V * 2.0 ** -53
+    assert lda_ref.max_rel(ot.exp_topic_word.cpu().numpy(), lda_ref.exp_dirichlet(lam)) <= 8 * 2.0 ** -52 + V * 2.0 ** -53
     assert float((ot.topic_word_distribution.sum(1) - 1).abs().max()) <= 1e-12
     # the host draws: lambda0, then a (B, K) gamma0 per call from the same RandomState
     drawn = _online_topics(z, o, device=DEV)
@@ -270,7 +234,7 @@ def test_a_minibatch_does_not_depend_on_the_rows_outside_it(golden, docs):
     z = golden[0]
     assert docs[2].dtype == torch.int64 and z["components_"].shape[0] % 2 == 0
     lam0, g0 = _dev(z["lambda0"]), _dev(z["gamma0"][0])
-    rho, doc_ratio = lda_online_ref.rho_of(10.0, 1, 0.7), 200.0 / 64
+    rho, doc_ratio = lda_ref.rho_of(10.0, 1, 0.7), 200.0 / 64
     inside, etheta, ratio = _one_minibatch(*docs, 64, 128, lam0, g0, z, rho, doc_ratio)
     lo, hi = int(z["indptr"][64]), int(z["indptr"][128])
     assert not torch.isnan(etheta[64:128]).any() and torch.isnan(etheta[:64]).all() and torch.isnan(etheta[128:]).all()
@@ -295,18 +259,18 @@ def test_online_fit_of_documents_without_a_word_is_the_blend_of_lambda0_and_the_
     ct = torch.zeros(0, dtype=torch.float64, device=DEV)
     fit = fit_topics(ip, ix, ct, V, num_topics=K, max_iter=2, random_state=3, topic_word_prior=eta, return_iterations=True,
                      learning_method="online", batch_size=2)
-    lam0, g0s = lda_fit_ref.draws(3, K, V, B, 2)
+    lam0, g0s = lda_ref.draws(3, K, V, B, 2)
     lam, n = lam0.copy(), 1
     for _ in range(2):
         for b0, b1 in ((0, 2), (2, 3)):
             rho = np.float64(np.power(10.0 + n, -0.7))
-            beta = lda_fit_ref.exp_dirichlet(lam)
+            beta = lda_ref.exp_dirichlet(lam)
             v = rho * (np.float64(eta) + np.float64(3.0 / (b1 - b0)) * (np.zeros((K, V)) * beta))
             lam = lam * (np.float64(1.0) - rho) + v
             n += 1
     assert fit.n_batch_iter == n == 5
     assert np.array_equal(fit.components.cpu().numpy().view(np.int64), lam.view(np.int64))
-    want, iters, _, _ = lda_online_ref.fit_online(np.zeros(B + 1, np.int32), np.zeros(0, np.int32), np.zeros(0), lam0, g0s,
+    want, iters, _, _ = lda_ref.fit_online(np.zeros(B + 1, np.int32), np.zeros(0, np.int32), np.zeros(0), lam0, g0s,
                                                   1.0 / K, eta, batch_size=2)
     assert np.array_equal(want.view(np.int64), lam.view(np.int64))
     assert np.array_equal(fit.iterations.cpu().numpy(), iters)

@@ -14,14 +14,10 @@ from graph_convolutional_networks_for_text_classification_amd import (GCN, Docum
 
 import lda_cases
 import lda_ref
+from lda_gpu import DEV, bits as _bits, dev as _dev
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 T, W = lda_cases.T, lda_cases.W
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 def _docs(c, dtype=np.float64):
@@ -30,10 +26,6 @@ def _docs(c, dtype=np.float64):
 
 def _inferencer(c):
     return TopicInferencer(_dev(c["beta"]), c["alpha"], c["tol"], c["max_iter"])
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int64 if t.dtype == torch.float64 else torch.int32)
 
 
 def _compare(what, theta, iters, ref, extra=0.0):
