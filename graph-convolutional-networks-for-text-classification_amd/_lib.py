@@ -1,5 +1,10 @@
 """ctypes binding of libgcnk.so (the C-ABI declared in include/gcnk.h).
 
+The header is the only statement of the ABI: every entry point's signature,
+every struct and every ``GCNK_*`` constant is read from it when this module is
+imported (``parse_header``), so a new entry point is declared there,
+implemented, and bound.  What the reader cannot take whole it refuses.
+
 The shared library is built in-tree by ``__graft_entry__.build()`` (or
 ``make -C <package>/csrc``).  There is no fallback: if the library is missing
 or fails to load, every op raises ``RuntimeError`` — the hot path never
@@ -7,6 +12,7 @@ silently runs anywhere but the HIP kernels.
 """
 import ctypes
 import os
+import re
 import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -31,53 +37,94 @@ def _resolve_lib():
 
 
 LIB_PATH = _resolve_lib()
-ABI_VERSION = 13
 
-# C-ABI return codes (gcnk.h)
-OK, EARG, EUNSUP, EHIP = 0, -1, -2, -3
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "gcnk.h")
 
-# SpMM epilogues (gcnk.h GCNK_EPI_*)
-EPI_NONE, EPI_BIAS, EPI_BIAS_RELU, EPI_BIAS_RELU_DROP, EPI_BIAS_RELU_HASH = 0, 1, 2, 3, 4
-# GEMM epilogues (gcnk.h GCNK_GEMM_EPI_*)
-GEMM_EPI_NONE, GEMM_EPI_BIAS, GEMM_EPI_BIAS_RELU, GEMM_EPI_MASK_POS = 0, 1, 2, 5
-# gcnk_gemm_route's families and flags (gcnk.h GCNK_GEMM_ROUTE_*)
-(GEMM_ROUTE_NARROW, GEMM_ROUTE_SKINNY, GEMM_ROUTE_SHORTK, GEMM_ROUTE_SMALLM, GEMM_ROUTE_TILED_N16,
- GEMM_ROUTE_TILED) = 1, 2, 3, 4, 5, 6
-GEMM_ROUTE_SPLIT, GEMM_ROUTE_PTR_FETCH = 1, 2
-# gcnk_spmm_route's aligned16 mask (gcnk.h GCNK_SPMM_ALIGNED_*)
-SPMM_ALIGNED_B, SPMM_ALIGNED_C, SPMM_ALIGNED_BIAS, SPMM_ALIGNED_WORKSPACE, SPMM_ALIGNED_ALL = 1, 2, 4, 8, 15
-
-_vp, _i32, _i64, _u64, _f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float
-_f64 = ctypes.c_double
-# gcnk_adam_f32 (gcnk.h GCNK_ADAM_*)
-ADAM_MAX_TENSORS, ADAM_CHUNK, ADAM_ZERO_GRAD, ADAM_HOLD_STEP = 8, 2048, 1, 2
+# ---- The binding is read from include/gcnk.h, once, at import: entry points, structs and constants are stated
+# there and nowhere else.
+_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint32_t": ctypes.c_uint32,
+            "uint64_t": ctypes.c_uint64, "float": ctypes.c_float, "double": ctypes.c_double}
+_POINTEES = ("void", "char", "uint8_t")   # what a pointer may point to besides a scalar and a struct
+_DEFINE = re.compile(r"^[ \t]*#[ \t]*define[ \t]+GCNK_(\w+)[ \t]+(\S.*?)[ \t]*$", re.M)   # (not function-like)
+_STRUCT = re.compile(r"typedef\s+struct\s+\w+\s*\{([^{}]*)\}\s*(\w+)\s*;\s*")
+_FUNCTION = re.compile(r"([\w\s*]+?)\b(gcnk_\w+)\s*\(([^()]*)\)\s*;\s*")
+_DECLARATOR = re.compile(r"(.*?[\s*])((?:\w+(?:\[\d+\])?\s*,\s*)*\w+(?:\[\d+\])?)", re.S)
 
 
-class AdamTensor(ctypes.Structure):
-    """gcnk.h gcnk_adam_tensor"""
-    _fields_ = [("p", _vp), ("g", _vp), ("m", _vp), ("v", _vp), ("numel", _i64)]
+def _ctype(spelling, structs, decl):
+    """The ctypes class of a C type as the header spells it: a pointer is c_void_p (``const char*``: c_char_p), a
+    scalar its ctypes namesake, an earlier struct that struct.  ``decl``: the declaration, for the error."""
+    words = spelling.replace("*", " * ").split()
+    base = [w for w in words if w not in ("const", "*")]
+    if len(base) != 1 or not (base[0] in _SCALARS or base[0] in structs or ("*" in words and base[0] in _POINTEES)):
+        raise RuntimeError(f"gcnk.h: unknown type '{' '.join(spelling.split())}' in '{decl}'")
+    if "*" in words:
+        return ctypes.c_char_p if base[0] == "char" and "const" in words else ctypes.c_void_p
+    return _SCALARS.get(base[0]) or structs[base[0]]
 
 
-class EpochState(ctypes.Structure):
-    """gcnk.h gcnk_epoch_state (32 bytes on the device)"""
-    _fields_ = [("epoch", _i32), ("stopped", _i32), ("stop_epoch", _i32), ("counter", _i32), ("best", _f64),
-                ("arrivals", _i32), ("reserved", _i32)]
+def _declared(decl, structs, member):
+    """[(name, ctypes class)] of a struct's member declaration (``T a, b``, ``T a[16]``) or of a function's parameter
+    (one name, no array)."""
+    decl = " ".join(decl.split())
+    m = _DECLARATOR.fullmatch(decl)
+    if not m or ("*" in m.group(1) and "," in m.group(2)) or ("[" in m.group(2) and not member):
+        raise RuntimeError(f"gcnk.h: cannot read the declaration '{decl}'")
+    ctype = _ctype(m.group(1), structs, decl)
+    names = [d.strip().rstrip("]").partition("[") for d in m.group(2).split(",")]
+    return [(name, ctype * int(dim) if dim else ctype) for name, _, dim in names]
 
 
-# gcnk_epoch_tail_f32's stop reasons (gcnk.h GCNK_EPOCH_STOP_*)
-EPOCH_STOP_PATIENCE, EPOCH_STOP_MAX_EPOCH = 1, 2
-# gcnk_keep_best_f32 (gcnk.h GCNK_KEEP_*)
-KEEP_MAX_TENSORS, KEEP_CHUNK, KEEP_HOLD_STATE = 8, 8192, 1
+def parse_header(text):
+    """(signatures, structs, constants) of a header in include/gcnk.h's form: {entry point: (restype, [argtypes])},
+    {typedef'd struct: its ctypes.Structure} and {NAME: value} for every ``#define GCNK_<NAME> <integer>``.  Besides
+    comments and preprocessor lines the text is one ``extern "C" { ... }`` of function declarations and struct
+    typedefs; anything else raises RuntimeError naming it, because an entry point left unbound would be called with
+    ctypes' default conversions (a pointer passed as a 32-bit int)."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    constants = {}
+    for name, value in _DEFINE.findall(text):
+        try:
+            constants[name] = int(value[1:-1] if value[0] + value[-1] == "()" else value, 0)
+        except ValueError:   # (an expression, or another macro's name)
+            raise RuntimeError(f"gcnk.h: GCNK_{name} is defined as '{value}', not as an integer") from None
+    code = "\n".join(line for line in text.splitlines() if not line.lstrip().startswith("#"))
+    block = re.fullmatch(r'\s*extern\s+"C"\s*\{\s*(.*)\}\s*', code, re.S)
+    if not block:
+        raise RuntimeError('gcnk.h: expected one extern "C" { ... } block and nothing outside it')
+    body, pos, signatures, structs = block.group(1), 0, {}, {}
+    while pos < len(body):
+        s = _STRUCT.match(body, pos)
+        f = None if s else _FUNCTION.match(body, pos)
+        if s:
+            fields = [fld for d in s.group(1).split(";") if d.strip() for fld in _declared(d, structs, True)]
+            structs[s.group(2)] = type(s.group(2), (ctypes.Structure,), {"_fields_": fields})
+        elif f:
+            params = [] if f.group(3).strip() == "void" else f.group(3).split(",")
+            signatures[f.group(2)] = (_ctype(f.group(1), structs, f.group(2)),
+                                      [_declared(p, structs, False)[0][1] for p in params])
+        else:
+            stmt = " ".join(body[pos:body.find(";", pos) + 1 or None].split())
+            raise RuntimeError(f"gcnk.h: neither a function declaration nor a struct typedef: '{stmt[:200]}'")
+        pos = (s or f).end()   # (each pattern takes the white space behind its statement)
+    return signatures, structs, constants
 
 
-class KeepTensor(ctypes.Structure):
-    """gcnk.h gcnk_keep_tensor"""
-    _fields_ = [("src", _vp), ("dst", _vp), ("numel", _i64)]
+def read_header(path=HEADER_PATH):
+    if not os.path.exists(path):
+        raise RuntimeError(f"gcnk.h not found at {path}: libgcnk.so is bound from the header it was built with "
+                           "(include/gcnk.h of the source tree). There is no hand-written fallback.")
+    with open(path) as f:
+        return parse_header(f.read())
 
 
-class KeepState(ctypes.Structure):
-    """gcnk.h gcnk_keep_state (16 bytes on the device)"""
-    _fields_ = [("seen", _i32), ("best", _i32), ("arrivals", _i32), ("copies", _i32)]
+# name -> (restype, argtypes) of every entry point; C name -> ctypes.Structure; GCNK_<NAME> -> value
+SIGNATURES, STRUCTS, CONSTANTS = read_header()
+if set(CONSTANTS) & set(globals()):
+    raise RuntimeError(f"gcnk.h: GCNK_{sorted(set(CONSTANTS) & set(globals()))[0]} would replace a name of {__name__}")
+globals().update(CONSTANTS)   # GCNK_OK is _lib.OK, GCNK_EPI_BIAS_RELU _lib.EPI_BIAS_RELU, ..., GCNK_ABI_VERSION too
+AdamTensor, EpochState = STRUCTS["gcnk_adam_tensor"], STRUCTS["gcnk_epoch_state"]
+KeepTensor, KeepState = STRUCTS["gcnk_keep_tensor"], STRUCTS["gcnk_keep_state"]
 
 
 class LaunchTables:
@@ -107,203 +154,6 @@ def epoch_row_words(nclass):
     """gcnk.h GCNK_EPOCH_ROW_WORDS: train_loss | val_loss | TP | FP | FN | correct"""
     return 3 * nclass + 3
 
-
-# the nine epilogue arguments of the entry points that end in the SpMM's fused epilogue:
-# bias, epilogue, drop_mask, ldm, drop_scale, keep_prob, seed, offset, rng_base
-_EPI_ARGS = [_vp, _i32, _vp, _i64, _f32, _f32, _u64, _u64, _vp]
-
-# name -> (restype, argtypes); every symbol include/gcnk.h declares
-SIGNATURES = {
-    "gcnk_abi_version": (ctypes.c_int, []),
-    "gcnk_debug_set_stamps": (ctypes.c_int, [_vp]),
-    "gcnk_last_error": (ctypes.c_char_p, []),
-    "gcnk_spmm_groups": (_i32, [_i32, _i32]),
-    "gcnk_spmm_default_ipc": (_i32, [_i32, _i64, _i32, _i32]),
-    # rowptr, colind, M, K, nnz, ipc, groups, dense_threshold, stream
-    "gcnk_spmm_plan_bytes": (_i64, [_vp, _vp, _i32, _i32, _i64, _i32, _i32, _f32, _vp]),
-    # rowptr, colind, val, M, K, nnz, ipc, groups, dense_threshold, plan, plan_bytes, stream
-    "gcnk_spmm_plan_build": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _i64, _i32, _i32, _f32, _vp, _i64, _vp]),
-    "gcnk_spmm_plan_bytes_host": (_i64, [_vp, _vp, _i32, _i32, _i64, _i32, _i32, _f32]),
-    "gcnk_spmm_plan_build_host": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _i64, _i32, _i32, _f32, _vp, _i64]),
-    "gcnk_spmm_plan_query": (ctypes.c_int, [_vp, _vp, _vp]),
-    "gcnk_spmm_workspace_bytes": (_i64, [_vp, _i32]),
-    "gcnk_spmm_counter_bytes": (_i64, [_vp]),
-    "gcnk_spmm_csr_f32": (ctypes.c_int, [
-        _vp, _vp,                 # plan (device), plan header (host, 16 words)
-        _vp, _i64, _i32,          # B, ldb, F
-        _vp, _i64,                # C, ldc
-        *_EPI_ARGS,
-        _vp, _i64,                # workspace, workspace_bytes
-        _vp, _i64,                # counters, counter_bytes
-        _i32, _vp,                # lanes_hint, stream
-    ]),
-    "gcnk_spmm_csr_f32_part": (ctypes.c_int, [
-        _vp, _vp,                 # plan (device), plan header (host, 16 words)
-        _vp, _i64, _i32,          # B, ldb, F
-        _vp, _i64,                # C, ldc
-        *_EPI_ARGS,
-        _vp, _i64,                # workspace, workspace_bytes
-        _vp, _i64,                # counters, counter_bytes
-        _i32, _i32, _vp,          # lanes_hint, part, stream
-    ]),
-    "gcnk_spmm_proj_f32": (ctypes.c_int, [
-        _vp, _vp,                 # plan, plan header
-        _vp, _i64, _i32,          # B, ldb, F
-        _vp, _i64,                # C (nullable), ldc
-        *_EPI_ARGS,
-        _vp, _i64, _i32, _vp, _i64,  # W, ldw, P, C2, ldc2
-        _vp, _i64,                # workspace, workspace_bytes
-        _vp, _i64,                # counters, counter_bytes
-        _i32, _vp,                # lanes_hint, stream
-    ]),
-    # plan header (host), F, ldb, ldc, aligned16 mask, lanes_hint, P, part, out16
-    "gcnk_spmm_route": (ctypes.c_int, [_vp, _i32, _i64, _i64, _i32, _i32, _i32, _i32, _vp]),
-    "gcnk_gemm_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32]),
-    "gcnk_gemm_f32": (ctypes.c_int, [
-        _i32, _i32, _i32, _i32, _i32,   # transA, transB, M, N, K
-        _vp, _i64, _vp, _i64,           # A, lda, B, ldb
-        _vp, _i64,                      # C, ldc
-        _vp, _i32, _vp, _i64, _f32,     # bias, epilogue, R, ldr, scale
-        _i32, _vp, _i64, _vp,           # split_k, workspace, workspace_bytes, stream
-    ]),
-    # transA, transB, M, N, K, lda, ldb, a_aligned16, b_aligned16, split_k, out4
-    "gcnk_gemm_route": (ctypes.c_int, [_i32, _i32, _i32, _i32, _i32, _i64, _i64, _i32, _i32, _i32, _vp]),
-    "gcnk_colsum_workspace_bytes": (_i64, [_i32, _i32]),
-    "gcnk_colsum_f32": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _i64, _vp]),
-    "gcnk_gcn_bwd2_workspace_bytes": (_i64, [_i32, _i32, _i32]),
-    "gcnk_gcn_bwd2_f32": (ctypes.c_int, [
-        _vp, _i64, _vp, _i64, _vp, _i64,   # H, ldh, gS, ldgs, W, ldw
-        _vp, _i64, _i32, _i32, _i32, _f32,  # G, ldg, M, N, P, scale
-        _vp, _i64, _vp, _vp, _vp,          # gZ1, ldz, gW, gb1, gb2
-        _vp, _i64, _vp]),                  # workspace, bytes, stream
-    # M, N, P, ldh, ldz, h_align, z_align, ldgs, has_g, ldg, ldw, w_aligned16, out9
-    "gcnk_gcn_bwd2_route": (ctypes.c_int, [_i32, _i32, _i32, _i64, _i64, _i32, _i32, _i64, _i32, _i64, _i64, _i32, _vp]),
-    "gcnk_stream_copy_f32": (ctypes.c_int, [_vp, _vp, _i64, _vp]),
-    "gcnk_debug_poison_lds": (ctypes.c_int, [ctypes.c_uint32, _vp]),
-    "gcnk_hubfactor_lds_bytes": (_i64, [_i32, _i32, _i32, _i32, _i32]),
-    "gcnk_hubfactor_gc1_f32": (ctypes.c_int, [
-        _i32, _i32, _i32, _i32, _i32,     # M, F, Kc, nhub, P
-        _vp, _i64, _vp, _i64, _i32,       # U, ldu, W, ldw, k0
-        _vp, _i64, _vp, _i32,             # S, lds, rec, rec_words
-        *_EPI_ARGS,
-        _vp, _i64, _vp, _i64, _vp, _i64,  # W2, ldw2, H, ldh, C2, ldc2
-        _vp]),                            # stream
-    # F, Kc, nhub, rec_words, P, ldu, u_aligned16, out6
-    "gcnk_hubfactor_gc1_route": (ctypes.c_int, [_i32, _i32, _i32, _i32, _i32, _i64, _i32, _vp]),
-    "gcnk_hubfactor_gc2_f32": (ctypes.c_int, [
-        _i32, _i32, _i32, _vp, _i32,      # M, H, P, rec, rec_words
-        _vp, _vp, _vp, _vp, _vp, _vp,     # diag, pre, hub_ids (host), hub_rp (host), hub_ci, hub_val
-        _vp, _i64, _vp, _vp, _i64,        # S2, lds2, b2, out, ldo
-        _vp]),                            # stream
-    "gcnk_score_docs_f32": (ctypes.c_int, [
-        _i32, _i32, _i32, _i32, _i32, _i32,   # B, F, Kc, H, P, k0
-        _vp, _i64, _vp, _i64,             # x, ldx, a, lda
-        _vp, _i64, _vp, _i64,             # W1, ldw1, S_T, lds
-        _vp, _i64, _vp, _i64,             # W2, ldw2, S2_T, lds2
-        _vp, _vp, _vp,                    # dh (float64), b1, b2
-        _vp, _i64, _vp, _vp]),            # out, ldo, labels (int32), stream
-    # F, Kc, H, P, out8
-    "gcnk_score_docs_route": (ctypes.c_int, [_i32, _i32, _i32, _i32, _vp]),
-    # rowptr, colind, val, M, hub_index, perm, diag, pre, stream
-    "gcnk_factor_diag_f32": (ctypes.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
-    "gcnk_dense_gc1_f32": (ctypes.c_int, [
-        _i32, _i32, _i32, _i32,           # M, K, F, P
-        _vp, _i64, _vp, _i64,             # AX, ldax, W1, ldw1
-        *_EPI_ARGS,
-        _vp, _i64, _vp, _i64, _vp, _i64,  # W2, ldw2, H, ldh, C2, ldc2
-        _vp]),                            # stream
-    "gcnk_aggregate_f32": (ctypes.c_int, [_vp, _vp, _vp, _i32, _vp, _i64, _i32, _vp, _i64, _i32, _vp]),
-    # record (host struct gcnk_gcn_fwd), W1, b1, W2, b2, out, ldo, H1, ldh, epilogue, mask, ldm, scale,
-    # keep_prob, seed, offset, rng_base, stream
-    "gcnk_gcn_forward_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _f32,
-                                            _f32, _u64, _u64, _vp, _vp]),
-    "gcnk_gcn_fwd_layout": (_i32, [_vp, _i32]),
-    "gcnk_factor_u_f32": (ctypes.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _i64, _i32, _vp, _i64, _i32, _vp]),
-    "gcnk_factor_records": (ctypes.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp]),
-    "gcnk_factor_analyze_workspace_bytes": (_i64, [_i32, _i32]),
-    # rowptr, colind, M, hmin, x_rowptr, x_colind, x_val, x_dense, ldx, K, max_hubs, info, hubs, cnt (host),
-    # workspace, bytes, stream
-    "gcnk_factor_analyze": (ctypes.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp,
-                                           _vp, _i64, _vp]),
-    "gcnk_factor_xl_f32": (ctypes.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _i64, _i32, _vp]),
-    "gcnk_csr_gather_rows": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
-    "gcnk_dense_gather_rows_f32": (ctypes.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _i64, _vp]),
-    "gcnk_gcn_backward_f32": (ctypes.c_int, [_vp, _vp, _vp, _i64, _vp, _f32, _vp, _vp, _vp, _vp, _vp]),
-    "gcnk_class_stats": (ctypes.c_int, [_vp, _i64, _vp, _vp, _i64, _i32, _vp, _vp]),
-    # idx, n, M, counts, stream
-    "gcnk_ce_row_counts": (ctypes.c_int, [_vp, _i64, _i32, _vp, _vp]),
-    "gcnk_ce_workspace_bytes": (_i64, [_i32, _i32]),
-    # logits, ld, M, P, target, counts, n, loss, lse, workspace, workspace_bytes, stream
-    "gcnk_ce_forward_f32": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
-    # logits, ld, M, P, target, counts, n, lse, grad_out, dlogits, ldd, stream
-    "gcnk_ce_backward_f32": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
-    # tensor table (host, AdamTensor[ntensors]), ntensors, lr, beta1, beta2, eps, weight_decay, state, flags, stream
-    "gcnk_adam_f32": (ctypes.c_int, [_vp, _i32, _f64, _f64, _f64, _f64, _f64, _vp, _i32, _vp]),
-    # gcnk_adam_f32's arguments, then gate before stream
-    "gcnk_adam_gated_f32": (ctypes.c_int, [_vp, _i32, _f64, _f64, _f64, _f64, _f64, _vp, _i32, _vp, _vp]),
-    "gcnk_epoch_tail_workspace_bytes": (_i64, [_i32, _i32]),
-    # logits, ld, M, P, target, counts, n, train_loss, state, history, max_epoch, patience, delta, workspace,
-    # workspace_bytes, stream
-    "gcnk_epoch_tail_f32": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _f64,
-                                           _vp, _i64, _vp]),
-    # tensor table (host, KeepTensor[ntensors]), ntensors, epoch_state, state, flags, stream
-    "gcnk_keep_best_f32": (ctypes.c_int, [_vp, _i32, _vp, _vp, _i32, _vp]),
-    "gcnk_edgelist_size": (ctypes.c_int, [ctypes.c_char_p, _vp, _vp]),
-    "gcnk_edgelist_csr": (ctypes.c_int, [ctypes.c_char_p, _i64, _i64, _vp, _vp, _vp]),
-    "gcnk_csr_to_dense": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp]),
-    "gcnk_bernoulli_mt19937": (ctypes.c_int, [_vp, _vp, _vp, _i64, ctypes.c_double, _vp, _i32]),
-    "gcnk_bernoulli_mt19937_start": (ctypes.c_int, [_vp, _vp, _vp, _i64, ctypes.c_double, _vp, _vp]),
-    "gcnk_bernoulli_mt19937_wait": (ctypes.c_int, [_vp]),
-    "gcnk_sym_normalize_workspace_bytes": (_i64, [_i32, _i64]),
-    "gcnk_sym_normalize": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
-    "gcnk_topic_graph_chunk": (_i32, []),
-    "gcnk_topic_graph_max_topics": (_i32, []),
-    "gcnk_topic_graph_nnz_bound": (_i64, [_i32, _i32, _i32]),       # D, K, has_sim
-    "gcnk_topic_graph_workspace_bytes": (_i64, [_i32, _i32]),       # D, K
-    "gcnk_topic_graph_build": (ctypes.c_int, [
-        _vp, _i32, _i64, _vp, _i32, _i64,   # theta, theta_f32, ldt, sim (nullable), sim_f32, lds
-        _i32, _i32, _f64, _f64,             # D, K, doc_topic_threshold, topic_topic_threshold
-        _vp, _vp, _vp, _i64, _vp,           # rowptr, colind, val, capacity, edges (nullable, int32[2])
-        _vp, _i64, _vp]),                   # workspace, workspace_bytes, stream
-    # emb, emb_f32, lde, K, dim, sim (float64), lds, stream
-    "gcnk_topic_cosine_f64": (ctypes.c_int, [_vp, _i32, _i64, _i32, _i32, _vp, _i64, _vp]),
-    "gcnk_lda_max_topics": (_i32, []),
-    "gcnk_lda_tile_words": (_i32, []),
-    "gcnk_lda_docs_per_block": (_i32, []),
-    # components / exp_topic_word (float64 [K x V]), its row stride, K, V, table, ldt, stream
-    "gcnk_lda_exp_dirichlet_f64": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _i64, _vp]),
-    "gcnk_lda_table_from_exp_f64": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _i64, _vp]),
-    "gcnk_lda_estep_f64": (ctypes.c_int, [
-        _vp, _vp, _vp, _i32,                # indptr, indices, counts, counts_kind (0 f64, 1 i32, 2 i64)
-        _i32, _i32, _i32, _vp, _i64,        # B, V, K, table, ldt
-        _f64, _f64, _i32,                   # alpha, tol, max_iter
-        _vp, _i64, _vp, _vp,                # theta, ldth, gamma, iters (int32[B]); each nullable
-        _vp, _i64, _vp, _i64, _f64,         # x, ldx, a, lda (nullable together), threshold
-        _vp]),                              # stream
-    "gcnk_lda_words_per_block": (_i32, []),
-    "gcnk_lda_estep_fit_f64": (ctypes.c_int, [
-        _vp, _vp, _vp, _i32,                # indptr, indices, counts, counts_kind
-        _i32, _i32, _i32, _vp, _i64,        # B, V, K, table, ldt
-        _f64, _f64, _i32,                   # alpha, tol, max_iter
-        _vp, _i64, _i64, _vp,               # gamma0, ldg0, nnz, ratio (float64[nnz])
-        _vp, _i64, _vp, _i64, _vp,          # etheta, lde, gamma, ldg, iters (the last two pointers nullable)
-        _vp]),                              # stream
-    "gcnk_lda_mstep_f64": (ctypes.c_int, [
-        _vp, _vp, _vp, _i64,                # wptr, pos, doc, nnz
-        _vp, _vp, _i64,                     # ratio, etheta, lde
-        _i32, _i32, _i32, _vp, _i64,        # B, V, K, table, ldt
-        _f64, _vp, _i64, _vp]),             # eta, lambda, ldl, stream
-    "gcnk_lda_mstep_online_f64": (ctypes.c_int, [
-        _vp, _vp, _vp, _i64, _i32, _i32,    # wptr, pos, doc, nnz, doc_lo, doc_hi
-        _vp, _vp, _i64,                     # ratio, etheta, lde
-        _i32, _i32, _i32, _vp, _i64,        # B, V, K, table, ldt
-        _f64, _f64, _f64,                   # eta, rho, doc_ratio
-        _vp, _i64, _vp]),                   # lambda (in place), ldl, stream
-    "gcnk_csr_transpose_workspace_bytes": (_i64, [_i32, _i32, _i64]),
-    "gcnk_coo_to_csr_workspace_bytes": (_i64, [_i64, _i32, _i32]),
-    "gcnk_coo_to_csr": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
-    "gcnk_csr_transpose": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
-}
 
 # added within ABI 13 (gc2 from the hub factor, the backward's and the factored gc1's route reports): absent from
 # variants of an older tree

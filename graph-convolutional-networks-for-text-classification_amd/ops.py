@@ -210,7 +210,8 @@ def spmm_proj(a, B, W, bias=None, epilogue=_lib.EPI_NONE, mask=None, scale=1.0, 
 # The two-layer forward's four schedules (include/gcnk.h GCNK_FWD_*) and the
 # range of gc1's fused kernels: rows of F floats as float4s in one column tile;
 # dense-AX and factored project onto <= FUSED_MAX_P classes, factored stages in LDS.
-FWD_FACTORED, FWD_SPMM_PROJ, FWD_SPMM_GEMM, FWD_DENSE_AX = 1, 2, 3, 4
+FWD_FACTORED, FWD_SPMM_PROJ, FWD_SPMM_GEMM, FWD_DENSE_AX = (_lib.FWD_FACTORED, _lib.FWD_SPMM_PROJ, _lib.FWD_SPMM_GEMM,
+                                                           _lib.FWD_DENSE_AX)
 FUSED_MAX_F, FUSED_MAX_P, FACTOR_LDS_BUDGET = 256, 32, 160 * 1024
 
 

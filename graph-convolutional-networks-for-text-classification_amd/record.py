@@ -28,44 +28,15 @@ from .sparse import CSR
 _c = ctypes
 
 
-class PlanRef(_c.Structure):
-    """gcnk_plan_ref (include/gcnk.h)."""
-    _fields_ = [("plan", _c.c_void_p), ("hdr", _c.c_int32 * 16), ("workspace", _c.c_void_p),
-                ("workspace_bytes", _c.c_int64), ("counters", _c.c_void_p), ("counter_bytes", _c.c_int64),
-                ("lanes_hint", _c.c_int32), ("pad_", _c.c_int32)]
-
-
-class GcnFwd(_c.Structure):
-    """gcnk_gcn_fwd (include/gcnk.h)."""
-    _fields_ = [("kind", _c.c_int32), ("M", _c.c_int32), ("F", _c.c_int32), ("P", _c.c_int32),
-                ("x_rows", _c.c_int32), ("x_cols", _c.c_int32), ("x", PlanRef),
-                ("x_dense", _c.c_void_p), ("ldx", _c.c_int64), ("x_split_k", _c.c_int32), ("pad0_", _c.c_int32),
-                ("gemm_ws", _c.c_void_p), ("gemm_ws_bytes", _c.c_int64), ("s1", _c.c_void_p), ("lds1", _c.c_int64),
-                ("Kc", _c.c_int32), ("nhub", _c.c_int32), ("k0", _c.c_int32), ("rec_words", _c.c_int32),
-                ("U", _c.c_void_p), ("ldu", _c.c_int64), ("rec", _c.c_void_p),
-                ("aF", PlanRef), ("aP", PlanRef), ("s2", _c.c_void_p), ("lds2", _c.c_int64),
-                ("h1_tmp", _c.c_void_p), ("ld_h1_tmp", _c.c_int64),
-                ("gc2_diag", _c.c_void_p), ("gc2_pre", _c.c_void_p), ("gc2_hub_ids", _c.c_void_p),
-                ("gc2_hub_rp", _c.c_void_p), ("gc2_hub_ci", _c.c_void_p), ("gc2_hub_val", _c.c_void_p)]
-
-
-class GcnBwd(_c.Structure):
-    """gcnk_gcn_bwd (include/gcnk.h)."""
-    _fields_ = [("M", _c.c_int32), ("F", _c.c_int32), ("P", _c.c_int32), ("x_rows", _c.c_int32),
-                ("x_cols", _c.c_int32), ("x_split_k", _c.c_int32), ("flags", _c.c_int32), ("pad1_", _c.c_int32),
-                ("aTP", PlanRef), ("aTF", PlanRef),
-                ("xT", PlanRef), ("x_dense", _c.c_void_p), ("ldx", _c.c_int64), ("gemm_ws", _c.c_void_p),
-                ("gemm_ws_bytes", _c.c_int64), ("gS2", _c.c_void_p), ("gZ1", _c.c_void_p), ("gS1", _c.c_void_p),
-                ("bwd2_ws", _c.c_void_p), ("bwd2_ws_bytes", _c.c_int64)]
-
-
+# gcnk_plan_ref, gcnk_gcn_fwd, gcnk_gcn_bwd as _lib reads them from include/gcnk.h
+PlanRef, GcnFwd, GcnBwd = (_lib.STRUCTS[name] for name in ("gcnk_plan_ref", "gcnk_gcn_fwd", "gcnk_gcn_bwd"))
 FACTORED, SPMM_PROJ, SPMM_GEMM, DENSE_AX = ops.FWD_FACTORED, ops.FWD_SPMM_PROJ, ops.FWD_SPMM_GEMM, ops.FWD_DENSE_AX
 KIND_NAMES = {FACTORED: "factored", SPMM_PROJ: "spmm+proj", SPMM_GEMM: "spmm+gemm", DENSE_AX: "dense-ax"}
-BWD_AX_DIRECT = 1
+BWD_AX_DIRECT = _lib.BWD_AX_DIRECT
 
 
 def layout_ok():
-    """The ctypes mirrors match the library's struct layout (gcnk_gcn_fwd_layout)."""
+    """The structs read from the header match the library's own layout (gcnk_gcn_fwd_layout)."""
     buf = (_c.c_int64 * 16)()
     n = _lib.load().gcnk_gcn_fwd_layout(buf, 16)
     want = [_c.sizeof(PlanRef), _c.sizeof(GcnFwd), GcnFwd.x.offset, GcnFwd.U.offset, GcnFwd.aF.offset,

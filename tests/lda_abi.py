@@ -2,13 +2,14 @@
 one row per gcnk_lda_* entry point, and the declared / exported / bound check they share.  No GPU: every call made
 through here is refused before any HIP call, so PTR is never dereferenced."""
 import os
-import re
 
 import gcn_amd  # noqa: F401
 from graph_convolutional_networks_for_text_classification_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "graph-convolutional-networks-for-text-classification_amd", "csrc")
+import abi_bound
+from abi_bound import header  # noqa: F401  (the three files take it from here)
+
+CSRC = os.path.join(abi_bound.ROOT, "graph-convolutional-networks-for-text-classification_amd", "csrc")
 PTR = 0x10000   # an aligned address that no refused call dereferences
 
 
@@ -55,13 +56,6 @@ def call(name, **kw):
     return rc, lib.gcnk_last_error().decode()
 
 
-def header():
-    """include/gcnk.h -> (its text, the text without comments)."""
-    with open(os.path.join(ROOT, "include", "gcnk.h")) as f:
-        text = f.read()
-    return text, re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-
-
 def kernels_source():
     with open(os.path.join(CSRC, "Makefile")) as f:
         assert "lda_estep.hip" in f.read()
@@ -70,15 +64,7 @@ def kernels_source():
 
 
 def assert_declared_exported_bound(names):
-    """names: entry point -> its argument count, the stream included."""
-    src = header()[1]
-    lib = _lib.load()
+    """names: entry point -> its argument count, the stream included (abi_bound's check, and ENTRY's rows agree)."""
+    abi_bound.assert_declared_exported_bound(names)
     for name, nargs in names.items():
-        decl = re.search(r"\b" + name + r"\s*\(([^)]*)\)", src)
-        assert decl and (nargs == 0 or len(decl.group(1).split(",")) == nargs), name
-        assert name in _lib.SIGNATURES and len(_lib.SIGNATURES[name][1]) == nargs
-        assert name in _lib.NEWER_THAN_SOME_VARIANTS
-        fn = getattr(lib, name)
-        assert fn.argtypes == _lib.SIGNATURES[name][1] and fn.restype is _lib.SIGNATURES[name][0]
         assert name not in ENTRY or len(ENTRY[name]) + 1 == nargs
-    assert lib.gcnk_abi_version() == _lib.ABI_VERSION == 13

@@ -12,6 +12,7 @@ import gcn_amd  # noqa: F401
 from graph_convolutional_networks_for_text_classification_amd import _lib
 
 import score_ref
+from abi_bound import assert_declared_exported_bound, header
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAME = "gcnk_score_docs_f32"
@@ -30,13 +31,8 @@ def _call(B=40, F=200, Kc=50, H=50, P=8, k0=0, x=PTR, ldx=None, a=PTR, lda=None,
 
 
 def test_symbol_declared_exported_and_bound():
-    with open(os.path.join(ROOT, "include", "gcnk.h")) as f:
-        src = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
-    assert re.search(r"\bint\s+" + NAME + r"\s*\(", src)
-    assert NAME in _lib.SIGNATURES and len(_lib.SIGNATURES[NAME][1]) == 25
-    fn = getattr(_lib.load(), NAME)
-    assert fn.argtypes == _lib.SIGNATURES[NAME][1] and fn.restype is ctypes.c_int
-    assert _lib.load().gcnk_abi_version() == 13
+    assert re.search(r"\bint\s+" + NAME + r"\s*\(", header()[1])
+    assert_declared_exported_bound({NAME: 25}, restype=ctypes.c_int)
 
 
 @pytest.mark.parametrize("kw", [dict(H=129), dict(Kc=129), dict(P=33), dict(F=6), dict(F=260), dict(x=PTR + 4),

@@ -3,7 +3,6 @@ every refusal before any HIP call with its reason in gcnk_last_error, and the de
 kernels implement (tests/topic_graph_ref.py) pinned to the reference's own A-hat of R8."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
@@ -12,6 +11,7 @@ import gcn_amd
 from graph_convolutional_networks_for_text_classification_amd import _lib, factor, topic_graph
 
 import topic_graph_ref as ref
+from abi_bound import assert_declared_exported_bound, header
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = {"gcnk_topic_graph_chunk": 0, "gcnk_topic_graph_max_topics": 0, "gcnk_topic_graph_nnz_bound": 3,
@@ -32,16 +32,8 @@ def _build(theta=PTR, theta_f32=0, ldt=None, sim=PTR, sim_f32=0, lds=None, D=300
 
 
 def test_symbols_declared_exported_and_bound():
-    with open(os.path.join(ROOT, "include", "gcnk.h")) as f:
-        text = f.read()
-    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    lib = _lib.load()
-    for name, nargs in NAMES.items():
-        assert re.search(r"\b" + name + r"\s*\(", src), name
-        assert name in _lib.SIGNATURES and len(_lib.SIGNATURES[name][1]) == nargs
-        fn = getattr(lib, name)
-        assert fn.argtypes == _lib.SIGNATURES[name][1] and fn.restype is _lib.SIGNATURES[name][0]
-    assert lib.gcnk_abi_version() == _lib.ABI_VERSION == 13
+    assert_declared_exported_bound(NAMES)
+    text = header()[0]
     assert "build_graph.py:99-133" in text and "gcnk_topic_graph_" in text.split("#define GCNK_ABI_VERSION")[0]
     with open(os.path.join(ROOT, "graph-convolutional-networks-for-text-classification_amd", "csrc", "Makefile")) as f:
         assert "topic_graph.hip" in f.read()
