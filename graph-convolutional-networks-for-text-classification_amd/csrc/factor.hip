@@ -56,6 +56,7 @@ struct FactorArgs {
   int32_t u_lds;                        // 1: the block's U rows staged in LDS by 16-B DMA (ldu % 4 == 0, aligned)
   float* H; int64_t ldh;                // nullable
   float* C2; int64_t ldc2;              // [M x P]
+  uint32_t c2_bytes;                    // C2's span (below kBufOob: stored through a buffer resource)
   Epi epi;
 };
 
@@ -309,18 +310,24 @@ hubfactor_gc1_kernel(FactorArgs a) {
   const int4 orow = *reinterpret_cast<const int4*>(s_rec + kHubRecRow + 16 * strip + (lane >> 4) * 4);
   __syncthreads();
   if (quarter == 0) {
+    // through a buffer resource over C2: a row id of -1 (past M) and a column past P are sent past it, so the
+    // four stores sit behind no branch or 64-bit multiply.  Plain stores: gc2 gathers S2 right away, and
+    // write-through or nontemporal ones made this kernel slower ("What each launch leaves
+    // at its seam")
+    const __amdgpu_buffer_rsrc_t rc2 = buffer_rsrc(a.C2, a.c2_bytes);
     const int rid[4] = {orow.x, orow.y, orow.z, orow.w};
+    uint32_t roff[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) roff[r] = rid[r] >= 0 ? (uint32_t)rid[r] * (4u * (uint32_t)a.ldc2) : kBufOob;
 #pragma unroll
     for (int t = 0; t < NP; ++t) {
 #pragma unroll
       for (int qq = 0; qq < 3; ++qq)
         pc[t] += *reinterpret_cast<const f32x4*>(s_red + (((t * 3 + qq) * 2 + strip) * 64 + lane) * 4);
       const int p = 16 * t + (lane & 15);
+      const uint32_t poff = p < a.P ? 4u * (uint32_t)p : kBufOob;
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int64_t row = rid[r];
-        if (row >= 0 && p < a.P) a.C2[row * a.ldc2 + p] = pc[t][r];
-      }
+      for (int r = 0; r < 4; ++r) buf_store_f32(pc[t][r], rc2, roff[r] + poff);
     }
   }
   stamp(a.epi, 3);
@@ -432,9 +439,11 @@ extern "C" int gcnk_hubfactor_gc1_f32(int32_t M, int32_t F, int32_t Kc, int32_t 
     set_error("gcnk_hubfactor_gc1_f32: leading dimension too small");
     return GCNK_EARG;
   }
+  const int64_t c2_bytes = 4 * ((int64_t)(M - 1) * ldc2 + P);
   if (bad == 3 || ldw != F || lds != F || ldw2 != P || !aligned16(W) || !aligned16(S) || (H && !aligned16(H)) ||
-      (H && ldh % 4) || (bias && !aligned16(bias))) {
-    set_error("gcnk_hubfactor_gc1_f32: unsupported shape (F=%d %% 4, F <= 256, Kc <= 128, P <= 32, 16-B rows)", F);
+      (H && ldh % 4) || (bias && !aligned16(bias)) || c2_bytes >= (int64_t)kBufOob) {
+    set_error("gcnk_hubfactor_gc1_f32: unsupported shape (F=%d %% 4, F <= 256, Kc <= 128, P <= 32, 16-B rows, "
+              "S2 below 2 GiB)", F);
     return GCNK_EUNSUP;
   }
   FactorArgs a;
@@ -451,6 +460,7 @@ extern "C" int gcnk_hubfactor_gc1_f32(int32_t M, int32_t F, int32_t Kc, int32_t 
   a.U = U; a.ldu = ldu; a.W = W; a.ldw = ldw; a.k0 = k0;
   a.S = S; a.lds = lds; a.rec = rec; a.rec_words = rec_words;
   a.W2 = W2; a.ldw2 = ldw2; a.H = H; a.ldh = ldh; a.C2 = C2; a.ldc2 = ldc2;
+  a.c2_bytes = (uint32_t)c2_bytes;
   const int64_t nblk = hub_blocks(M);
   const int ks = rt.ks, ntq = rt.ntq, np = rt.np;
   const int64_t lds_l = rt.lds_launch;

@@ -26,6 +26,10 @@
 //
 // Out-of-range lanes go through buffer resources sized to the operands (loads
 // return 0, stores are dropped); no global partials, counters or atomics.
+// The output rows are stored write-through (sc1): nothing in this launch reads
+// them, and plain stores left them as dirty lines in the XCD L2s for the
+// end-of-kernel write-back (2.94-2.97 against 2.99-3.01 us replayed; nontemporal
+// stores 3.33-3.35: DESIGN section 5, "What each launch leaves at its seam").
 #include "hub_block.h"
 
 #include <algorithm>
@@ -180,7 +184,7 @@ __global__ void __launch_bounds__(kThreads) factored_spmm_row_kernel(Gc2Args a) 
 #pragma unroll
       for (int q = 1; q < kCollect; ++q) t += p[q];
       t += bv;
-      buf_store_f32x4(t, r_out, (uint32_t)row * a.ldo4 + 16u * c);
+      buf_store_f32x4<kBufSc1>(t, r_out, (uint32_t)row * a.ldo4 + 16u * c);
     }
     stamp2(a, 3);
     return;
@@ -242,7 +246,7 @@ __global__ void __launch_bounds__(kThreads) factored_spmm_row_kernel(Gc2Args a) 
   doc_chain<P4>(acc, s_items, s_hub, a.H * P, c, jm, je);
   stamp2(a, 2);
   acc += bv;
-  buf_store_f32x4(acc, r_out, doc ? (uint32_t)rid * a.ldo4 + 16u * c : kBufOob);
+  buf_store_f32x4<kBufSc1>(acc, r_out, doc ? (uint32_t)rid * a.ldo4 + 16u * c : kBufOob);
   stamp2(a, 3);
 }
 

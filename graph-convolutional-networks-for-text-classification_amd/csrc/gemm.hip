@@ -507,19 +507,24 @@ gemm_smallm_wk_kernel(int32_t M, int32_t N, int32_t K, const float* __restrict__
   }
   __syncthreads();
   // the eight waves' tiles summed in wave order; thread e owns (tile e / 64, lane e % 64)
-  float* out = slab + (int64_t)blockIdx.x * M * N;
+  // Stored write-through (sc1) through a buffer resource over this slab (a row past M lies past it, a column
+  // past N is sent there; M N 4 B fit 32 bits under the route's bound on ldb): the slabs are read once, by
+  // the reduce launch on other XCDs, and plain stores left their 1.2 MB (R8) as dirty lines in this XCD's L2
+  // for the end-of-kernel write-back ("What each launch leaves at its seam").
+  const __amdgpu_buffer_rsrc_t ro = buffer_rsrc(slab + (int64_t)blockIdx.x * M * N, M * N * 4);
   for (int e = tid; e < RT * NTG * 64; e += 512) {
     const int ti = e / 64, l = e % 64;
     f32x4 v = s_acc[0][ti][l];
 #pragma unroll
     for (int ww = 1; ww < kW; ++ww) v += s_acc[ww][ti][l];
     const int t = ti / NTG, u = ti % NTG;
-    const int64_t n = n0 + 16 * u + (l & 15);
+    const int n = (int)n0 + 16 * u + (l & 15);
+    const uint32_t noff = n < N ? 4u * (uint32_t)n : kBufOob;
     // C/D map: reg jj -> row 4 (l >> 4) + jj of the tile, column l & 15
 #pragma unroll
     for (int jj = 0; jj < 4; ++jj) {
-      const int64_t m = 16 * t + 4 * (l >> 4) + jj;
-      if (m < M && n < N) out[m * N + n] = v[jj];
+      const int m = 16 * t + 4 * (l >> 4) + jj;
+      buf_store_f32<kBufSc1>(v[jj], ro, 4u * (uint32_t)(m * N) + noff);
     }
   }
 }
