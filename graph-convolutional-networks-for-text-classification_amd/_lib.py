@@ -4,6 +4,9 @@ The header is the only statement of the ABI: every entry point's signature,
 every struct and every ``GCNK_*`` constant is read from it when this module is
 imported (``parse_header``), so a new entry point is declared there,
 implemented, and bound.  What the reader cannot take whole it refuses.
+include/gcnk_lda_bound.h, which gcnk.h includes, declares the topic model's
+bound, score and perplexity in the same form and is read the same way
+(``LDA_BOUND_SIGNATURES``).
 
 The shared library is built in-tree by ``__graft_entry__.build()`` (or
 ``make -C <package>/csrc``).  There is no fallback: if the library is missing
@@ -39,6 +42,8 @@ def _resolve_lib():
 LIB_PATH = _resolve_lib()
 
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "gcnk.h")
+# the topic model's bound, score and perplexity: a header of its own in gcnk.h's form, which gcnk.h includes
+LDA_BOUND_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "gcnk_lda_bound.h")
 
 # ---- The binding is read from include/gcnk.h, once, at import: entry points, structs and constants are stated
 # there and nowhere else.
@@ -123,6 +128,10 @@ SIGNATURES, STRUCTS, CONSTANTS = read_header()
 if set(CONSTANTS) & set(globals()):
     raise RuntimeError(f"gcnk.h: GCNK_{sorted(set(CONSTANTS) & set(globals()))[0]} would replace a name of {__name__}")
 globals().update(CONSTANTS)   # GCNK_OK is _lib.OK, GCNK_EPI_BIAS_RELU _lib.EPI_BIAS_RELU, ..., GCNK_ABI_VERSION too
+# name -> (restype, argtypes) of gcnk_lda_bound.h's entry points, read the same way (it holds nothing else)
+LDA_BOUND_SIGNATURES, _structs, _constants = read_header(LDA_BOUND_HEADER_PATH)
+if _structs or _constants or set(LDA_BOUND_SIGNATURES) & set(SIGNATURES):
+    raise RuntimeError("gcnk_lda_bound.h: expected function declarations alone, none of them gcnk.h's own")
 AdamTensor, EpochState = STRUCTS["gcnk_adam_tensor"], STRUCTS["gcnk_epoch_state"]
 KeepTensor, KeepState = STRUCTS["gcnk_keep_tensor"], STRUCTS["gcnk_keep_state"]
 
@@ -164,7 +173,8 @@ NEWER_THAN_SOME_VARIANTS = ("gcnk_hubfactor_gc2_f32", "gcnk_factor_diag_f32", "g
                             "gcnk_topic_graph_build", "gcnk_topic_cosine_f64", "gcnk_lda_max_topics",
                             "gcnk_lda_tile_words", "gcnk_lda_docs_per_block", "gcnk_lda_exp_dirichlet_f64",
                             "gcnk_lda_table_from_exp_f64", "gcnk_lda_estep_f64", "gcnk_lda_words_per_block",
-                            "gcnk_lda_estep_fit_f64", "gcnk_lda_mstep_f64", "gcnk_lda_mstep_online_f64")
+                            "gcnk_lda_estep_fit_f64", "gcnk_lda_mstep_f64", "gcnk_lda_mstep_online_f64",
+                            *LDA_BOUND_SIGNATURES)
 
 _lock = threading.Lock()
 _lib = None
@@ -187,7 +197,7 @@ def load():
                 f"libgcnk.so not found at {LIB_PATH}: build it with __graft_entry__.build() "
                 "or `make -C <package>/csrc` (hipcc --offload-arch=gfx950). There is no CPU fallback.")
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in (*SIGNATURES.items(), *LDA_BOUND_SIGNATURES.items()):
             fn = getattr(lib, name, None)
             if fn is None:
                 # an experiment variant built from an older csrc (an A/B's parent library)

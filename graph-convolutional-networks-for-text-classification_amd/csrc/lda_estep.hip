@@ -51,7 +51,15 @@
 // The M-step's loops run over [wptr[w], wptr[w + 1]) clamped to [0, nnz], nnz checked on the host; ratio and
 // etheta are read (and ratio written) through buffer resources, so a bad index reads zeros or writes nothing.
 //
-// The entry points, at the end of the file, are three families, each with its refusals and launch stated once:
+// How good a model is (sklearn's _approx_bound, score, perplexity, bound_ and evaluate_every) is three more launches,
+// stated above their kernels under "The variational bound": the documents' terms (one wave per document, this
+// file's staging and LDS layout, a logsumexp that shifts theta's side only and reads the same table), the topics'
+// terms (a workgroup per topic, the table builder's serial row sum) and one workgroup that sums both and the counts.
+// Every sum has a fixed order: no atomics, no workspace, no host synchronisation.
+//
+// The entry points, at the end of the file, are four families, each with its refusals and launch stated once:
+//     bound     gcnk_lda_bound_docs_f64 (check_table, check_documents), gcnk_lda_bound_topics_f64,
+//               gcnk_lda_bound_finish_f64 (check_topics); declared in include/gcnk_lda_bound.h
 //     tables    gcnk_lda_exp_dirichlet_f64, gcnk_lda_table_from_exp_f64: check_table, then their own source check
 //     E-step    gcnk_lda_estep_f64 (transform), gcnk_lda_estep_fit_f64 (both fits): estep_args -- check_table, the
 //               document refusals, the common EStep fields -- then each one's own outputs; launch_estep<kFit>
@@ -134,10 +142,11 @@ struct EStep {
   uint32_t ratio_bytes;
 };
 
-__device__ __forceinline__ double count_at(const EStep& p, int64_t i) {
-  if (p.counts_kind == 0) return static_cast<const double*>(p.counts)[i];
-  if (p.counts_kind == 1) return (double)static_cast<const int32_t*>(p.counts)[i];
-  return (double)static_cast<const int64_t*>(p.counts)[i];
+// a stored count as float64: counts_kind 0 float64, 1 int32, 2 int64 (widened exactly)
+__device__ __forceinline__ double count_at(const void* counts, int32_t counts_kind, int64_t i) {
+  if (counts_kind == 0) return static_cast<const double*>(counts)[i];
+  if (counts_kind == 1) return (double)static_cast<const int32_t*>(counts)[i];
+  return (double)static_cast<const int64_t*>(counts)[i];
 }
 
 // tile[w * Ks + k] = table[id_w, k] for the m words whose ids the lanes hold (lane w: word w)
@@ -195,7 +204,7 @@ lda_estep_kernel(EStep p) {
   auto load_words = [&](int c) {
     const int32_t w = c * kTile + lane;
     id = w < n ? p.indices[b + w] : 0;
-    cnt = w < n ? count_at(p, b + w) : 0.0;
+    cnt = w < n ? count_at(p.counts, p.counts_kind, b + w) : 0.0;
   };
 
   double g0 = 1.0, g1 = 1.0;
@@ -345,14 +354,9 @@ lda_estep_kernel(EStep p) {
   }
 }
 
-// A workgroup per topic: exp(psi(lambda_kw) - psi(sum_w lambda_kw)) into column k of the table.  Every wave
-// takes the row sum for itself, serially and ascending in w: 64 values a load, added one after the other
-// (a lane past the row's end holds +0, which leaves the sum as it is).
-__global__ void __launch_bounds__(256)
-lda_exp_dirichlet_kernel(const double* __restrict__ lam, int64_t ldc, int32_t V, double* __restrict__ table,
-                         int64_t ldt) {
-  const int k = blockIdx.x, lane = threadIdx.x & 63;
-  const double* row = lam + (int64_t)k * ldc;
+// sum_w row[w], serially and ascending in w, in every lane of the wave: 64 values a load, added one after the
+// other (a lane past the row's end holds +0, which leaves the sum as it is)
+__device__ __forceinline__ double row_sum_serial(const double* __restrict__ row, int32_t V, int lane) {
   double s = 0.0;
   for (int32_t base = 0; base < V; base += 4 * 64) {
     double v[4];
@@ -365,7 +369,17 @@ lda_exp_dirichlet_kernel(const double* __restrict__ lam, int64_t ldc, int32_t V,
       for (int j = 0; j < 64; ++j) s += readlane_f64(v[u], j);
     }
   }
-  const double psi_row = psi(s);
+  return s;
+}
+
+// A workgroup per topic: exp(psi(lambda_kw) - psi(sum_w lambda_kw)) into column k of the table.  Every wave
+// takes the row sum for itself (row_sum_serial).
+__global__ void __launch_bounds__(256)
+lda_exp_dirichlet_kernel(const double* __restrict__ lam, int64_t ldc, int32_t V, double* __restrict__ table,
+                         int64_t ldt) {
+  const int k = blockIdx.x, lane = threadIdx.x & 63;
+  const double* row = lam + (int64_t)k * ldc;
+  const double psi_row = psi(row_sum_serial(row, V, lane));
   for (int32_t w = threadIdx.x; w < V; w += 256) table[(int64_t)w * ldt + k] = exp(psi(row[w]) - psi_row);
 }
 
@@ -542,6 +556,194 @@ lda_mstep_online_kernel(MStepOnline q) {
   if (on1) blend(k1, s1);
 }
 
+// ---- The variational bound (sklearn's _approx_bound, score, perplexity): three launches, no atomics, no workspace.
+
+// v of the wave's 64 lanes summed in one fixed tree: lanes 2i and 2i + 1, then those sums in pairs, and so on
+// (partners lane ^ 1, 2, 4, 8, 16, 32).  Both partners add the same two numbers, so every lane holds the total.
+template <typename T>
+__device__ __forceinline__ T wave_tree_sum(T v) {
+#pragma unroll
+  for (int s = 1; s < 64; s <<= 1) v += __shfl_xor(v, s, 64);
+  return v;
+}
+
+// v of the workgroup's threads: wave_tree_sum in every wave, then the waves' sums one after the other in
+// ascending wave order; every thread holds the total.  `waves`: LDS for one value a wave.
+template <typename T>
+__device__ __forceinline__ T block_tree_sum(T v, T* waves) {
+  const int nwave = (int)(blockDim.x >> 6);
+  v = wave_tree_sum(v);
+  if ((threadIdx.x & 63) == 0) waves[threadIdx.x >> 6] = v;
+  __syncthreads();
+  T s = waves[0];
+  for (int q = 1; q < nwave; ++q) s += waves[q];
+  __syncthreads();   // (the caller may hand `waves` to the next sum)
+  return s;
+}
+
+struct BoundDocs {
+  const int32_t* indptr;
+  const int32_t* indices;
+  const void* counts;
+  int32_t counts_kind;
+  int32_t B, K;
+  const double* table;
+  uint32_t row_bytes, table_bytes;
+  const double* gamma;
+  int64_t ldg;
+  double alpha;
+  double* doc_bound;
+};
+
+// One wave per document, the E-step's geometry and LDS layout.  With l_k = psi(gamma_k) - psi(sum_k gamma_k),
+// m = max_k l_k and e_k = exp(l_k - m):
+//     words = sum_w c_w (m + log(sum_k e_k table[id_w, k]))     (logsumexp_k(l_k + E[log beta_kw]), theta's side shifted)
+//     s1 = sum_k (alpha - gamma_k) l_k      s2 = sum_k (lgamma(gamma_k) - lgamma(alpha))
+//     s3 = lgamma(alpha K) - lgamma(sum_k gamma_k)
+//     doc_bound = ((words + s1) + s2) + s3
+// Orders: every sum over k ascends, in-lane from LDS (the dot product by fma, as the E-step's phi).  The words go
+// in stored order in tiles of kTile: lane = word, the tile's 64 terms (+0 past the document's end) by
+// wave_tree_sum, the tiles' sums added one after the other.  Nothing depends on B, d or the launch.
+__global__ void __launch_bounds__(64 * kDocs)
+lda_bound_docs_kernel(BoundDocs p) {
+  extern __shared__ double lds[];
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int32_t d = (int32_t)blockIdx.x * kDocs + wv;
+  if (d >= p.B) return;
+  const int K = p.K, Ks = tile_stride(K), Kr = topics_even(K);
+  double* tile = lds + (size_t)wv * wave_doubles(K);
+  double* et = tile + kTile * Ks;   // l_k, then e_k
+  double* gm = et + Kr;             // gamma_k, then s2's addends
+  double* df = gm + Kr;             // s1's addends
+  const int64_t b = p.indptr[d];
+  const int64_t e = p.indptr[d + 1];
+  const int32_t n = e > b ? (int32_t)(e - b) : 0;
+  const int nchunk = (n + kTile - 1) / kTile;
+  const __amdgpu_buffer_rsrc_t table = buffer_rsrc(p.table, p.table_bytes);
+
+  const int k0 = lane, k1 = lane + 64;
+  const bool on0 = k0 < K, on1 = k1 < K;
+  const int r0 = on0 ? k0 : K - 1, r1 = on1 ? k1 : K - 1;
+  const double g0 = p.gamma[(int64_t)d * p.ldg + r0], g1 = p.gamma[(int64_t)d * p.ldg + r1];
+  if (on0) gm[k0] = g0;
+  if (on1) gm[k1] = g1;
+  wave_sync();
+  double total = 0.0;
+  for (int k = 0; k < K; ++k) total += gm[k];
+  const double psi_total = psi(total);
+  const double l0 = psi(g0) - psi_total, l1 = psi(g1) - psi_total;
+  if (on0) {
+    et[k0] = l0;
+    df[k0] = (p.alpha - g0) * l0;
+  }
+  if (on1) {
+    et[k1] = l1;
+    df[k1] = (p.alpha - g1) * l1;
+  }
+  wave_sync();
+  double mx = et[0], s1 = 0.0;
+  for (int k = 0; k < K; ++k) {
+    mx = fmax(mx, et[k]);
+    s1 += df[k];
+  }
+  wave_sync();   // (et and gm are rewritten)
+  const double lg_alpha = lgamma(p.alpha);
+  if (on0) {
+    et[k0] = exp(l0 - mx);
+    gm[k0] = lgamma(g0) - lg_alpha;
+  }
+  if (on1) {
+    et[k1] = exp(l1 - mx);
+    gm[k1] = lgamma(g1) - lg_alpha;
+  }
+  wave_sync();
+  double s2 = 0.0;
+  for (int k = 0; k < K; ++k) s2 += gm[k];
+  const double s3 = lgamma(p.alpha * (double)K) - lgamma(total);
+
+  double words = 0.0;
+  for (int c = 0; c < nchunk; ++c) {
+    const int m = min(kTile, n - c * kTile);
+    const int32_t w = c * kTile + lane;
+    const int32_t id = w < n ? p.indices[b + w] : 0;
+    const double cnt = w < n ? count_at(p.counts, p.counts_kind, b + w) : 0.0;
+    stage_words(table, p.row_bytes, K, Ks, id, m, lane, tile);
+    wave_sync();
+    const double* mine = tile + lane * Ks;   // (a lane past the chunk's end computes on stale LDS and adds +0)
+    double dot = 0.0;
+    for (int k = 0; k < K; ++k) dot = fma(et[k], mine[k], dot);
+    const double term = cnt * (mx + log(dot));
+    words += wave_tree_sum(lane < m ? term : 0.0);
+    wave_sync();   // (the next chunk rewrites tile)
+  }
+  if (lane == 0) p.doc_bound[d] = ((words + s1) + s2) + s3;
+}
+
+constexpr int kTopicThreads = 256;    // the topic term's chunk: addend w belongs to thread w mod 256
+constexpr int kFinishThreads = 1024;
+
+// A workgroup per topic.  With L = sum_w lambda_kw (row_sum_serial, as the table's builder takes it):
+//     s1 = sum_w (eta - lambda_kw) (psi(lambda_kw) - psi(L))      s2 = sum_w (lgamma(lambda_kw) - lgamma(eta))
+//     topic_bound = (s1 + s2) + (lgamma(eta V) - lgamma(L))
+// Order of s1 and s2: thread t adds the words t, t + 256, ... in ascending order, then block_tree_sum.
+__global__ void __launch_bounds__(kTopicThreads)
+lda_bound_topics_kernel(const double* __restrict__ lam, int64_t ldl, int32_t V, double eta,
+                        double* __restrict__ topic_bound) {
+  __shared__ double waves[kTopicThreads / 64];
+  const int k = blockIdx.x, lane = threadIdx.x & 63;
+  const double* row = lam + (int64_t)k * ldl;
+  const double L = row_sum_serial(row, V, lane);
+  const double psi_row = psi(L), lg_eta = lgamma(eta);
+  double a1 = 0.0, a2 = 0.0;
+  for (int32_t w = threadIdx.x; w < V; w += kTopicThreads) {
+    const double x = row[w];
+    a1 += (eta - x) * (psi(x) - psi_row);
+    a2 += lgamma(x) - lg_eta;
+  }
+  const double s1 = block_tree_sum(a1, waves);
+  const double s2 = block_tree_sum(a2, waves);
+  if (threadIdx.x == 0) topic_bound[k] = (s1 + s2) + (lgamma(eta * (double)V) - lgamma(L));
+}
+
+// One workgroup: out[0] = bound = doc_ratio * sum_d doc_bound[d] + sum_k topic_bound[k], out[1] = the word count
+// sum of counts[indptr[0] .. indptr[B]), out[2] = perplexity = exp(-(bound / (count * doc_ratio))).  Every sum:
+// thread t adds the elements t, t + 1024, ... in ascending order, then block_tree_sum; integer counts in int64.
+__global__ void __launch_bounds__(kFinishThreads)
+lda_bound_finish_kernel(const double* __restrict__ doc_bound, int32_t B, const double* __restrict__ topic_bound,
+                        int32_t K, const int32_t* __restrict__ indptr, const void* __restrict__ counts,
+                        int32_t counts_kind, double doc_ratio, double* __restrict__ out) {
+  __shared__ double waves[kFinishThreads / 64];
+  __shared__ long long iwaves[kFinishThreads / 64];
+  const int t = threadIdx.x;
+  double a = 0.0;
+  for (int32_t d = t; d < B; d += kFinishThreads) a += doc_bound[d];
+  const double docs = block_tree_sum(a, waves);
+  double q = 0.0;
+  for (int32_t k = t; k < K; k += kFinishThreads) q += topic_bound[k];
+  const double topics = block_tree_sum(q, waves);
+  const int64_t lo = indptr[0], hi = indptr[B];
+  double count;
+  if (counts_kind == 0) {
+    double c = 0.0;
+    for (int64_t i = lo + t; i < hi; i += kFinishThreads) c += static_cast<const double*>(counts)[i];
+    count = block_tree_sum(c, waves);
+  } else {
+    long long c = 0;
+    for (int64_t i = lo + t; i < hi; i += kFinishThreads)
+      c += counts_kind == 1 ? (long long)static_cast<const int32_t*>(counts)[i]
+                            : (long long)static_cast<const int64_t*>(counts)[i];
+    count = (double)block_tree_sum(c, iwaves);
+  }
+  if (t != 0) return;
+  const double scaled = doc_ratio * docs;
+  const double bound = scaled + topics;
+  const double per_word = bound / (count * doc_ratio);
+  out[0] = bound;
+  out[1] = count;
+  out[2] = exp(-1.0 * per_word);
+}
+
 // K in range, the table's rows 16-byte accesses, every byte offset into it below kBufOob
 int check_table(const char* who, int32_t K, int32_t V, const void* table, int64_t ldt) {
   if (K < 1 || V < 1) {
@@ -561,6 +763,23 @@ int check_table(const char* who, int32_t K, int32_t V, const void* table, int64_
     set_error("%s: a table of %lld bytes is past the 32-bit offsets of its buffer resource (V=%d ldt=%lld)", who,
               (long long)((int64_t)V * ldt * 8), V, (long long)ldt);
     return GCNK_EUNSUP;
+  }
+  return GCNK_OK;
+}
+
+// (NaN and +inf fail)
+bool finite_positive(double x) { return x > 0.0 && x <= 1.7976931348623157e308; }
+
+// a document batch: B >= 1, its three arrays, a count kind the kernels widen
+int check_documents(const char* who, const int32_t* indptr, const int32_t* indices, const void* counts,
+                    int32_t counts_kind, int32_t B) {
+  if (B < 1 || !indptr || !indices || !counts) {
+    set_error("%s: needs B >= 1 and non-null indptr, indices and counts (B=%d)", who, B);
+    return GCNK_EARG;
+  }
+  if (counts_kind < 0 || counts_kind > 2) {
+    set_error("%s: counts_kind %d is not 0 (float64), 1 (int32) or 2 (int64)", who, counts_kind);
+    return GCNK_EARG;
   }
   return GCNK_OK;
 }
@@ -611,14 +830,8 @@ static int estep_args(const char* who, const int32_t* indptr, const int32_t* ind
                       double alpha, double tol, int32_t max_iter, double* gamma, int64_t ldg, int32_t* iters, EStep& p) {
   const int rc = check_table(who, K, V, table, ldt);
   if (rc) return rc;
-  if (B < 1 || !indptr || !indices || !counts) {
-    set_error("%s: needs B >= 1 and non-null indptr, indices and counts (B=%d)", who, B);
-    return GCNK_EARG;
-  }
-  if (counts_kind < 0 || counts_kind > 2) {
-    set_error("%s: counts_kind %d is not 0 (float64), 1 (int32) or 2 (int64)", who, counts_kind);
-    return GCNK_EARG;
-  }
+  const int rd = check_documents(who, indptr, indices, counts, counts_kind, B);
+  if (rd) return rd;
   if (max_iter < 0 || max_iter > kMaxIter) {
     set_error("%s: max_iter=%d is outside [0, %d]", who, max_iter, kMaxIter);
     return GCNK_EARG;
@@ -802,7 +1015,7 @@ extern "C" int gcnk_lda_mstep_online_f64(const int32_t* wptr, const int32_t* pos
     set_error("%s: rho=%g is outside (0, 1]", who, rho);
     return GCNK_EARG;
   }
-  if (!(doc_ratio > 0.0 && doc_ratio <= 1.7976931348623157e308)) {   // (NaN and +inf fail)
+  if (!finite_positive(doc_ratio)) {
     set_error("%s: doc_ratio=%g is not a finite positive number", who, doc_ratio);
     return GCNK_EARG;
   }
@@ -812,4 +1025,90 @@ extern "C" int gcnk_lda_mstep_online_f64(const int32_t* wptr, const int32_t* pos
   q.doc_ratio = doc_ratio;
   return launch_mstep<lda_mstep_online_kernel<true>, lda_mstep_online_kernel<false>>("lda_mstep_online_kernel", q, V, K,
                                                                                       stream);
+}
+
+// ---- the variational bound's entry points
+extern "C" int32_t gcnk_lda_bound_topic_chunk(void) { return kTopicThreads; }
+
+extern "C" int gcnk_lda_bound_docs_f64(const int32_t* indptr, const int32_t* indices, const void* counts,
+                                       int32_t counts_kind, int32_t B, int32_t V, int32_t K, const double* table,
+                                       int64_t ldt, const double* gamma, int64_t ldg, double alpha, double* doc_bound,
+                                       void* stream) {
+  const char* who = "gcnk_lda_bound_docs_f64";
+  const int rc = check_table(who, K, V, table, ldt);
+  if (rc) return rc;
+  const int rd = check_documents(who, indptr, indices, counts, counts_kind, B);
+  if (rd) return rd;
+  if (!gamma || !doc_bound || ldg < K) {
+    set_error("%s: gamma and doc_bound must be non-null and ldg >= K (ldg=%lld K=%d)", who, (long long)ldg, K);
+    return GCNK_EARG;
+  }
+  BoundDocs p{};
+  p.indptr = indptr;
+  p.indices = indices;
+  p.counts = counts;
+  p.counts_kind = counts_kind;
+  p.B = B;
+  p.K = K;
+  p.table = table;
+  p.row_bytes = (uint32_t)(ldt * 8);
+  p.table_bytes = (uint32_t)((int64_t)V * ldt * 8);
+  p.gamma = gamma;
+  p.ldg = ldg;
+  p.alpha = alpha;
+  p.doc_bound = doc_bound;
+  const int lds_bytes = kDocs * wave_doubles(K) * (int)sizeof(double);
+  const unsigned nblk = (unsigned)(((int64_t)B + kDocs - 1) / kDocs);
+  return launch_big_lds<lda_bound_docs_kernel>("lda_bound_docs_kernel", dim3(nblk), dim3(64 * kDocs), (size_t)lds_bytes,
+                                               stream, p);
+}
+
+// K within the kernels' topics: GCNK_EARG below 1, GCNK_EUNSUP above kMaxTopics
+static int check_topics(const char* who, int32_t K) {
+  if (K < 1) {
+    set_error("%s: needs K >= 1 (K=%d)", who, K);
+    return GCNK_EARG;
+  }
+  if (K > kMaxTopics) {
+    set_error("%s: K=%d topics, the kernels take at most %d", who, K, kMaxTopics);
+    return GCNK_EUNSUP;
+  }
+  return GCNK_OK;
+}
+
+extern "C" int gcnk_lda_bound_topics_f64(const double* lambda, int64_t ldl, int32_t K, int32_t V, double eta,
+                                         double* topic_bound, void* stream) {
+  const char* who = "gcnk_lda_bound_topics_f64";
+  const int rc = check_topics(who, K);
+  if (rc) return rc;
+  if (V < 1 || !lambda || !topic_bound || ldl < V) {
+    set_error("%s: needs V >= 1, non-null lambda and topic_bound and ldl >= V (V=%d ldl=%lld)", who, V, (long long)ldl);
+    return GCNK_EARG;
+  }
+  hipLaunchKernelGGL(lda_bound_topics_kernel, dim3((unsigned)K), dim3(kTopicThreads), 0, (hipStream_t)stream, lambda, ldl,
+                     V, eta, topic_bound);
+  return launch_check("lda_bound_topics_kernel");
+}
+
+extern "C" int gcnk_lda_bound_finish_f64(const double* doc_bound, int32_t B, const double* topic_bound, int32_t K,
+                                         const int32_t* indptr, const void* counts, int32_t counts_kind,
+                                         double doc_ratio, double* out, void* stream) {
+  const char* who = "gcnk_lda_bound_finish_f64";
+  const int rc = check_topics(who, K);
+  if (rc) return rc;
+  if (B < 1 || !doc_bound || !topic_bound || !indptr || !counts || !out) {
+    set_error("%s: needs B >= 1 and non-null doc_bound, topic_bound, indptr, counts and out (B=%d)", who, B);
+    return GCNK_EARG;
+  }
+  if (counts_kind < 0 || counts_kind > 2) {
+    set_error("%s: counts_kind %d is not 0 (float64), 1 (int32) or 2 (int64)", who, counts_kind);
+    return GCNK_EARG;
+  }
+  if (!finite_positive(doc_ratio)) {
+    set_error("%s: doc_ratio=%g is not a finite positive number", who, doc_ratio);
+    return GCNK_EARG;
+  }
+  hipLaunchKernelGGL(lda_bound_finish_kernel, dim3(1), dim3(kFinishThreads), 0, (hipStream_t)stream, doc_bound, B,
+                     topic_bound, K, indptr, counts, counts_kind, doc_ratio, out);
+  return launch_check("lda_bound_finish_kernel");
 }

@@ -45,19 +45,29 @@ are uploaded before the first launch.  ``init=(lambda0, gamma0s)`` takes float64
 device tensors of those shapes instead and draws nothing.  ``OnlineTopics`` keeps
 its RandomState and draws a (B, K) gamma0 per ``partial_fit``.
 
+``evaluate_every`` / ``perp_tol`` / ``bound_`` are sklearn's too (topic_bound.py has
+the bound itself, with ``score`` and ``perplexity``).  ``compute_bound=True`` closes
+the fit as sklearn does, with an E-step from gamma = 1 and the training perplexity
+of the fitted lambda: ``fit.bound`` is sklearn's ``bound_``, a 0-dim device tensor,
+and still nothing synchronises.  ``evaluate_every=n > 0`` evaluates that perplexity
+after every n-th EM iteration, READS IT ON THE HOST (one scalar: the only
+synchronisation, in this mode alone) and stops by sklearn's rule -- the change
+since the last evaluation below ``perp_tol``, tested before the iteration is
+counted: ``fit.n_iter`` is sklearn's ``n_iter_``, ``fit.perplexities`` the values.
+``fit.scorer()`` / ``OnlineTopics.scorer()`` give the ``TopicBound`` of the model
+for held-out documents.
+
 Still not restated, out of scope (sklearn features the reference never uses):
-``bound_`` and the extra E-step and perplexity sklearn computes for it after the
-loop (so also ``score`` and ``perplexity``), ``evaluate_every > 0``, ``n_jobs``
-slicing of the documents, float32 input; the online method shuffles nothing, as
-sklearn's does not.  A document's word ids must be distinct (a CSR row of a
-document-term matrix); a word id outside [0, V) is the caller's error.
+``n_jobs`` slicing of the documents, float32 input; the online method shuffles
+nothing, as sklearn's does not.  A document's word ids must be distinct (a CSR row
+of a document-term matrix); a word id outside [0, V) is the caller's error.
 """
 import torch
 
-from . import _lib
+from . import _lib, topic_bound
 from .sparse import require_device
 from .topic_infer import (_COUNTS, MAX_TOPICS, MAX_UPDATE_ITER, TopicInferencer, check_documents, kernel_documents,
-                          model_table)
+                          model_table, run_estep)
 
 WORDS_PER_BLOCK = 4   # csrc/lda_estep.hip kWords: the M-step's waves (words) per workgroup
 
@@ -85,10 +95,13 @@ def word_index(indptr, indices, V):
 class TopicFit:
     """What ``fit_topics`` returns; every tensor is on the documents' device.  ``n_batch_iter``
     is sklearn's ``n_batch_iter_`` after the call: 1 + the M-steps run (EM iterations for
-    'batch', minibatches for 'online')."""
+    'batch', minibatches for 'online'); ``n_iter`` its ``n_iter_``.  ``bound``: sklearn's
+    ``bound_``, the training perplexity of the fitted lambda as a 0-dim float64 device tensor
+    (None unless asked for); ``perplexities``: the values ``evaluate_every`` read, host floats."""
 
     __slots__ = ("components", "topic_word_distribution", "iterations", "doc_topic_prior", "topic_word_prior",
-                 "mean_change_tol", "max_doc_update_iter", "n_iter", "n_batch_iter", "_table", "_work")
+                 "mean_change_tol", "max_doc_update_iter", "n_iter", "n_batch_iter", "bound", "perplexities", "_table",
+                 "_work")
 
     @property
     def exp_topic_word(self):
@@ -101,6 +114,12 @@ class TopicFit:
         tolerance and update cap: theta of any documents under this model."""
         return TopicInferencer.from_components(self.components, self.doc_topic_prior, self.mean_change_tol,
                                                self.max_doc_update_iter)
+
+    def scorer(self):
+        """``TopicBound`` of the fitted lambda with the fit's priors, tolerance and update cap:
+        score and perplexity of any documents under this model."""
+        return topic_bound.TopicBound(self.components, self.doc_topic_prior, self.topic_word_prior,
+                                      self.mean_change_tol, self.max_doc_update_iter)
 
 
 def _init_tensor(t, what, shape, dev):
@@ -206,10 +225,20 @@ def _online_pass(lib, stream, docs, lam, table, gamma0, iters, alpha, eta, tol, 
     return n
 
 
+def _training_perplexity(docs, lam, table, alpha, eta, tol, cap):
+    """sklearn's perplexity of the fit's own documents under ``lam``, whose ``table`` is current:
+    the E-step from gamma = 1 (``_e_step(random_init=False)``), then the bound's three launches
+    -> float64 [3] on the device (bound, word count, perplexity)."""
+    held = (docs.indptr, docs.indices, docs.counts, docs.B)
+    gamma = run_estep(table, docs.K, docs.V, *held, alpha, tol, cap, gamma=True)["gamma"]
+    doc_bound = topic_bound.doc_terms(table, docs.K, docs.V, *held, gamma, alpha)
+    return topic_bound.finish(doc_bound, topic_bound.topic_terms(lam, eta), docs.indptr, docs.counts, 1.0)
+
+
 def fit_topics(indptr, indices, counts, V, num_topics=50, max_iter=20, random_state=42, doc_topic_prior=None,
                topic_word_prior=None, mean_change_tol=1e-3, max_doc_update_iter=100, init=None,
                return_iterations=False, learning_method="batch", batch_size=128, learning_decay=0.7,
-               learning_offset=10.0):
+               learning_offset=10.0, evaluate_every=0, perp_tol=0.1, compute_bound=False):
     """sklearn's LDA fit of the documents (a CSR over V words, as ``doc_term`` gives it)
     -> TopicFit.  ``doc_topic_prior`` / ``topic_word_prior`` default to 1 / num_topics as
     sklearn's do.  ``init``: (lambda0 [K x V], gamma0s [max_iter x B x K]) float64 on the
@@ -217,11 +246,15 @@ def fit_topics(indptr, indices, counts, V, num_topics=50, max_iter=20, random_st
     int32 [max_iter x B] count of updates every document ran in every EM iteration.
     ``learning_method``: 'batch' or 'online'; ``batch_size``, ``learning_decay`` and
     ``learning_offset`` are the online method's (sklearn's names and defaults) and are not
-    looked at for 'batch'.
+    looked at for 'batch'.  ``evaluate_every`` / ``perp_tol`` (sklearn's; <= 0: never) and
+    ``compute_bound``: see the module docstring; with their defaults the launches are the
+    fit's alone.  A fit that ``evaluate_every`` stops early leaves the rows of
+    ``fit.iterations`` past ``n_batch_iter`` unwritten.
     RuntimeError, never a fallback: more than 128 topics, max_iter < 1, V < 1, an update cap
     outside [0, 10000], a bad ``init``, an unknown ``learning_method``, batch_size < 1,
-    learning_decay outside [0, 1], learning_offset < 1, and check_documents' refusals (float32
-    counts, CPU tensors, dtypes)."""
+    learning_decay outside [0, 1], learning_offset < 1, ``evaluate_every > 0`` with a
+    ``perp_tol`` that is negative or NaN or inside a stream capture (it reads the device), and
+    check_documents' refusals (float32 counts, CPU tensors, dtypes)."""
     K, V, max_iter, cap = int(num_topics), int(V), int(max_iter), int(max_doc_update_iter)
     _check_model("fit_topics", K, cap, max_iter=max_iter, V=V)
     if learning_method not in ("batch", "online"):
@@ -229,8 +262,14 @@ def fit_topics(indptr, indices, counts, V, num_topics=50, max_iter=20, random_st
     online = learning_method == "online"
     if online:
         bs, decay, offset = _check_online("fit_topics", batch_size, learning_decay, learning_offset)
+    every, perp_tol = max(int(evaluate_every), 0), float(perp_tol)
+    if every and not perp_tol >= 0.0:
+        raise RuntimeError(f"fit_topics: perp_tol={perp_tol} must be at least 0")
     B = check_documents(indptr, indices, counts, getattr(indptr, "device", None))
     dev = indptr.device
+    if every and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("fit_topics: evaluate_every > 0 reads a perplexity on the host after an EM iteration, "
+                           "which a stream capture cannot do (capture with evaluate_every=0)")
     alpha = 1.0 / K if doc_topic_prior is None else float(doc_topic_prior)
     eta = 1.0 / K if topic_word_prior is None else float(topic_word_prior)
     tol = float(mean_change_tol)
@@ -249,6 +288,19 @@ def fit_topics(indptr, indices, counts, V, num_topics=50, max_iter=20, random_st
     table = model_table(K, V, dev)
     iters = torch.empty((max_iter, B), dtype=torch.int32, device=dev) if return_iterations else None
 
+    perplexities, last, n_iter = [], None, 0
+
+    def converged():
+        """sklearn's check after an EM iteration (lam's table is current): the training
+        perplexity, read on the host, within perp_tol of the last one read."""
+        nonlocal last
+        p = float(_training_perplexity(docs, lam, table, alpha, eta, tol, cap)[2])
+        perplexities.append(p)
+        if last and abs(last - p) < perp_tol:
+            return True
+        last = p
+        return False
+
     lib = _lib.load()
     with torch.cuda.device(dev):
         stream = _lib.stream(dev)
@@ -259,9 +311,13 @@ def fit_topics(indptr, indices, counts, V, num_topics=50, max_iter=20, random_st
             for it in range(max_iter):
                 n = _online_pass(lib, stream, docs, lam, table, gamma0s[it], None if iters is None else iters[it],
                                  alpha, eta, tol, cap, bs, decay, offset, B, n)
+                if every and (it + 1) % every == 0 and converged():
+                    break
+                n_iter += 1
         else:
             lam = torch.empty((K, V), dtype=torch.float64, device=dev)
             ix = docs.ix
+            n = 1
             for it in range(max_iter):
                 _exp_dirichlet(lib, stream, lam0 if it == 0 else lam, table)
                 _estep_fit(lib, stream, docs, 0, B, table, gamma0s[it], None if iters is None else iters[it], alpha, tol,
@@ -270,16 +326,23 @@ def fit_topics(indptr, indices, counts, V, num_topics=50, max_iter=20, random_st
                     ix.wptr.data_ptr(), ix.pos.data_ptr(), ix.doc.data_ptr(), docs.nnz, docs.ratio.data_ptr(),
                     docs.etheta.data_ptr(), docs.etheta.stride(0), B, V, K, table.data_ptr(), table.stride(0), eta,
                     lam.data_ptr(), lam.stride(0), stream), "gcnk_lda_mstep_f64")
+                n += 1
+                if every and (it + 1) % every == 0:
+                    _exp_dirichlet(lib, stream, lam, table)   # (the next iteration makes the same table again)
+                    if converged():
+                        break
+                n_iter += 1
             _exp_dirichlet(lib, stream, lam, table)
-            n = 1 + max_iter
+        bound = _training_perplexity(docs, lam, table, alpha, eta, tol, cap)[2] if compute_bound or every else None
 
     fit = TopicFit()
     fit.components = lam
     fit.topic_word_distribution = lam / lam.sum(dim=1, keepdim=True)
     fit.iterations = iters
     fit.doc_topic_prior, fit.topic_word_prior = alpha, eta
-    fit.mean_change_tol, fit.max_doc_update_iter, fit.n_iter = tol, cap, max_iter
+    fit.mean_change_tol, fit.max_doc_update_iter, fit.n_iter = tol, cap, n_iter
     fit.n_batch_iter = n
+    fit.bound, fit.perplexities = bound, perplexities
     fit._table = table
     # (a captured call's launches keep reading these through raw pointers: held as long as the result is)
     fit._work = (docs, lam0, gamma0s)
@@ -392,3 +455,9 @@ class OnlineTopics:
         documents under the model as it stands now."""
         return TopicInferencer.from_components(self._lam.clone(), self.doc_topic_prior, self.mean_change_tol,
                                                self.max_doc_update_iter)
+
+    def scorer(self):
+        """``TopicBound`` of a copy of the current lambda: score and perplexity of any documents
+        under the model as it stands now (so whether a ``partial_fit`` made it better)."""
+        return topic_bound.TopicBound(self._lam.clone(), self.doc_topic_prior, self.topic_word_prior,
+                                      self.mean_change_tol, self.max_doc_update_iter)

@@ -86,6 +86,34 @@ def kernel_documents(indptr, indices, counts):
     return indptr, indices, counts
 
 
+def run_estep(table, K, V, indptr, indices, counts, B, alpha, tol, cap, theta=False, gamma=False, iters=False,
+              operands=None):
+    """gcnk_lda_estep_f64 of checked documents (``kernel_documents``' arrays) under ``table`` (``model_table``'s
+    form, current for the model) -> {name: tensor} of the outputs asked for; ``operands``: the threshold of x, a."""
+    dev = table.device
+    out = {}
+    if theta:
+        out["theta"] = torch.empty((B, K), dtype=torch.float64, device=dev)
+    if gamma:
+        out["gamma"] = torch.empty((B, K), dtype=torch.float64, device=dev)
+    if iters:
+        out["iters"] = torch.empty(B, dtype=torch.int32, device=dev)
+    threshold = 0.0
+    if operands is not None:
+        threshold = float(operands)
+        for k in ("x", "a"):   # rows 16-byte aligned: what DocumentScorer takes without a copy
+            out[k] = torch.empty((B, (K + 3) // 4 * 4), dtype=torch.float32, device=dev)[:, :K]
+    ptr = lambda k: out[k].data_ptr() if k in out else None   # noqa: E731
+    ld = lambda k: out[k].stride(0) if k in out else 0        # noqa: E731
+    with torch.cuda.device(dev):
+        rc = _lib.load().gcnk_lda_estep_f64(
+            indptr.data_ptr(), indices.data_ptr(), counts.data_ptr(), _COUNTS[counts.dtype], B, V, K,
+            table.data_ptr(), table.stride(0), alpha, tol, cap, ptr("theta"), K, ptr("gamma"), ptr("iters"), ptr("x"),
+            ld("x"), ptr("a"), ld("a"), threshold, _lib.stream(dev))
+    _lib.check(rc, "gcnk_lda_estep_f64")   # (no fallback: a shape the kernel refuses is an error)
+    return out
+
+
 class TopicInferencer:
     """theta of unseen documents under a fitted LDA model.
 
@@ -151,34 +179,11 @@ class TopicInferencer:
         tb = self._table()
         return tb.t[:, :tb.K].t()
 
-    def _run(self, indptr, indices, counts, theta=False, gamma=False, iters=False, operands=None):
+    def _run(self, indptr, indices, counts, **outputs):
         tb = self._table()
-        dev = tb.t.device
-        B = check_documents(indptr, indices, counts, dev)
-        indptr, indices, counts = kernel_documents(indptr, indices, counts)
-        K = tb.K
-        out = {}
-        if theta:
-            out["theta"] = torch.empty((B, K), dtype=torch.float64, device=dev)
-        if gamma:
-            out["gamma"] = torch.empty((B, K), dtype=torch.float64, device=dev)
-        if iters:
-            out["iters"] = torch.empty(B, dtype=torch.int32, device=dev)
-        threshold = 0.0
-        if operands is not None:
-            threshold = float(operands)
-            for k in ("x", "a"):   # rows 16-byte aligned: what DocumentScorer takes without a copy
-                out[k] = torch.empty((B, (K + 3) // 4 * 4), dtype=torch.float32, device=dev)[:, :K]
-        ptr = lambda k: out[k].data_ptr() if k in out else None   # noqa: E731
-        ld = lambda k: out[k].stride(0) if k in out else 0        # noqa: E731
-        with torch.cuda.device(dev):
-            rc = _lib.load().gcnk_lda_estep_f64(
-                indptr.data_ptr(), indices.data_ptr(), counts.data_ptr(), _COUNTS[counts.dtype], B, tb.V, K,
-                tb.t.data_ptr(), tb.t.stride(0), self.doc_topic_prior, self.mean_change_tol, self.max_doc_update_iter,
-                ptr("theta"), K, ptr("gamma"), ptr("iters"), ptr("x"), ld("x"), ptr("a"), ld("a"), threshold,
-                _lib.stream(dev))
-        _lib.check(rc, "gcnk_lda_estep_f64")   # (no fallback: a shape the kernel refuses is an error)
-        return out
+        B = check_documents(indptr, indices, counts, tb.t.device)
+        return run_estep(tb.t, tb.K, tb.V, *kernel_documents(indptr, indices, counts), B, self.doc_topic_prior,
+                         self.mean_change_tol, self.max_doc_update_iter, **outputs)
 
     def __call__(self, indptr, indices, counts, return_iterations=False):
         """theta, float64 [B x K] on the model's device (sklearn's ``transform``); with

@@ -25,6 +25,8 @@
  *   build_graph.py:118 cosine_similarity(topic_embeddings)     -> gcnk_topic_cosine_f64
  *   topic_model.py:133-164 LatentDirichletAllocation.transform -> gcnk_lda_estep_f64 (device, a wave per document)
  *   topic_model.py:74-131  LatentDirichletAllocation.fit (batch) -> gcnk_lda_estep_fit_f64 + gcnk_lda_mstep_f64
+ *   experiments/r8.yaml num_topics, max_iter: LatentDirichletAllocation.score / perplexity / bound_
+ *                                                            -> gcnk_lda_bound_*_f64 (gcnk_lda_bound.h, included below)
  *   layer.py:185 th.dropout keep-mask draw (CPU generator)    -> gcnk_bernoulli_mt19937 (host, same stream)
  *   trainer.py:307, 358-361, 383-384 CrossEntropyLoss on logits[idx] -> gcnk_ce_forward_f32 / gcnk_ce_backward_f32
  *   trainer.py:308, 359, 362 th.optim.Adam step (and zero_grad)   -> gcnk_adam_f32 (one launch per 8 tensors)
@@ -1197,6 +1199,10 @@ int gcnk_stream_copy_f32(const float* src, float* dst, int64_t n, void* stream);
  * Process-global and not thread-safe, which is why the product build
  * compiles it out: there it returns GCNK_EUNSUP for a non-null buffer. */
 int gcnk_debug_set_stamps(void* buf);
+
+/* The topic model's variational bound, score and perplexity (additions within
+ * ABI 13), declared in a header of its own in this one's form. */
+#include "gcnk_lda_bound.h"
 
 #ifdef __cplusplus
 }
