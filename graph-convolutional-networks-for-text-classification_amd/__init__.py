@@ -3,13 +3,14 @@
 Drop-in for the reference's ``layer.py`` (GraphConvolution, GCN) — see
 DESIGN.md for the path, the boundary and the kernels.
 """
-from . import (_lib, datasets, inductive, metrics, parallel, sparse, topic_bound, topic_fit, topic_graph, topic_infer,
-               train)
+from . import (_lib, datasets, inductive, metrics, parallel, sparse, text_count, topic_bound, topic_fit, topic_graph,
+               topic_infer, train)
 from .inductive import DocumentScorer, from_theta
 from .layer import GCN, GraphConvolution
 from .ops import GCNFn, GraphConvFn, Operand, colsum, gemm, spmm
 from .parallel import ColumnShardedSpMM, shard_bounds, sharded_gcn_forward
 from .sparse import CSR, as_csr, from_arrays, from_torch, preprocess_adj
+from .text_count import TextCounter
 from .topic_bound import TopicBound
 from .topic_fit import OnlineTopics, TopicFit, fit_topics
 from .topic_graph import TopicGraph, build_topic_graph, topic_similarity
@@ -18,7 +19,7 @@ from .train import Adam, BestKeeper, EpochLog, FitResult, IndexedCrossEntropy, c
 
 __all__ = [
     "datasets", "inductive", "metrics", "parallel", "sparse", "topic_bound", "topic_fit", "topic_graph", "topic_infer",
-    "train", "DocumentScorer", "TopicBound", "TopicFit", "fit_topics", "OnlineTopics",
+    "train", "text_count", "TextCounter", "DocumentScorer", "TopicBound", "TopicFit", "fit_topics", "OnlineTopics",
     "from_theta", "TopicGraph", "build_topic_graph", "topic_similarity", "TopicInferencer", "doc_term",
     "Adam", "IndexedCrossEntropy", "cross_entropy",
     "EpochLog", "BestKeeper", "FitResult", "fit", "run_epoch",

@@ -6,7 +6,8 @@ imported (``parse_header``), so a new entry point is declared there,
 implemented, and bound.  What the reader cannot take whole it refuses.
 include/gcnk_lda_bound.h, which gcnk.h includes, declares the topic model's
 bound, score and perplexity in the same form and is read the same way
-(``LDA_BOUND_SIGNATURES``).
+(``LDA_BOUND_SIGNATURES``), and so is include/gcnk_text.h, which declares the
+word counter (``TEXT_SIGNATURES``).
 
 The shared library is built in-tree by ``__graft_entry__.build()`` (or
 ``make -C <package>/csrc``).  There is no fallback: if the library is missing
@@ -44,6 +45,8 @@ LIB_PATH = _resolve_lib()
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "gcnk.h")
 # the topic model's bound, score and perplexity: a header of its own in gcnk.h's form, which gcnk.h includes
 LDA_BOUND_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "gcnk_lda_bound.h")
+# counting words (CountVectorizer.transform): a header of its own the same way
+TEXT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "gcnk_text.h")
 
 # ---- The binding is read from include/gcnk.h, once, at import: entry points, structs and constants are stated
 # there and nowhere else.
@@ -132,6 +135,10 @@ globals().update(CONSTANTS)   # GCNK_OK is _lib.OK, GCNK_EPI_BIAS_RELU _lib.EPI_
 LDA_BOUND_SIGNATURES, _structs, _constants = read_header(LDA_BOUND_HEADER_PATH)
 if _structs or _constants or set(LDA_BOUND_SIGNATURES) & set(SIGNATURES):
     raise RuntimeError("gcnk_lda_bound.h: expected function declarations alone, none of them gcnk.h's own")
+# name -> (restype, argtypes) of gcnk_text.h's entry points, likewise
+TEXT_SIGNATURES, _structs, _constants = read_header(TEXT_HEADER_PATH)
+if _structs or _constants or set(TEXT_SIGNATURES) & (set(SIGNATURES) | set(LDA_BOUND_SIGNATURES)):
+    raise RuntimeError("gcnk_text.h: expected function declarations alone, none of them another header's")
 AdamTensor, EpochState = STRUCTS["gcnk_adam_tensor"], STRUCTS["gcnk_epoch_state"]
 KeepTensor, KeepState = STRUCTS["gcnk_keep_tensor"], STRUCTS["gcnk_keep_state"]
 
@@ -174,7 +181,7 @@ NEWER_THAN_SOME_VARIANTS = ("gcnk_hubfactor_gc2_f32", "gcnk_factor_diag_f32", "g
                             "gcnk_lda_tile_words", "gcnk_lda_docs_per_block", "gcnk_lda_exp_dirichlet_f64",
                             "gcnk_lda_table_from_exp_f64", "gcnk_lda_estep_f64", "gcnk_lda_words_per_block",
                             "gcnk_lda_estep_fit_f64", "gcnk_lda_mstep_f64", "gcnk_lda_mstep_online_f64",
-                            *LDA_BOUND_SIGNATURES)
+                            *LDA_BOUND_SIGNATURES, *TEXT_SIGNATURES)
 
 _lock = threading.Lock()
 _lib = None
@@ -197,7 +204,7 @@ def load():
                 f"libgcnk.so not found at {LIB_PATH}: build it with __graft_entry__.build() "
                 "or `make -C <package>/csrc` (hipcc --offload-arch=gfx950). There is no CPU fallback.")
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in (*SIGNATURES.items(), *LDA_BOUND_SIGNATURES.items()):
+        for name, (res, args) in (*SIGNATURES.items(), *LDA_BOUND_SIGNATURES.items(), *TEXT_SIGNATURES.items()):
             fn = getattr(lib, name, None)
             if fn is None:
                 # an experiment variant built from an older csrc (an A/B's parent library)

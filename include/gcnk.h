@@ -27,6 +27,7 @@
  *   topic_model.py:74-131  LatentDirichletAllocation.fit (batch) -> gcnk_lda_estep_fit_f64 + gcnk_lda_mstep_f64
  *   experiments/r8.yaml num_topics, max_iter: LatentDirichletAllocation.score / perplexity / bound_
  *                                                            -> gcnk_lda_bound_*_f64 (gcnk_lda_bound.h, included below)
+ *   topic_model.py:159 CountVectorizer.transform (unseen text) -> gcnk_text_count + gcnk_text_emit (gcnk_text.h, below)
  *   layer.py:185 th.dropout keep-mask draw (CPU generator)    -> gcnk_bernoulli_mt19937 (host, same stream)
  *   trainer.py:307, 358-361, 383-384 CrossEntropyLoss on logits[idx] -> gcnk_ce_forward_f32 / gcnk_ce_backward_f32
  *   trainer.py:308, 359, 362 th.optim.Adam step (and zero_grad)   -> gcnk_adam_f32 (one launch per 8 tensors)
@@ -1203,6 +1204,9 @@ int gcnk_debug_set_stamps(void* buf);
 /* The topic model's variational bound, score and perplexity (additions within
  * ABI 13), declared in a header of its own in this one's form. */
 #include "gcnk_lda_bound.h"
+/* Counting words, CountVectorizer.transform against a fitted vocabulary (additions
+ * within ABI 13), the same way. */
+#include "gcnk_text.h"
 
 #ifdef __cplusplus
 }
