@@ -175,8 +175,9 @@ def epoch_row_words(nclass):
 # variants of an older tree
 NEWER_THAN_SOME_VARIANTS = ("gcnk_hubfactor_gc2_f32", "gcnk_factor_diag_f32", "gcnk_gcn_bwd2_route",
                             "gcnk_hubfactor_gc1_route", "gcnk_score_docs_f32", "gcnk_score_docs_route",
-                            "gcnk_spmm_route", "gcnk_topic_graph_chunk", "gcnk_topic_graph_max_topics",
-                            "gcnk_topic_graph_nnz_bound", "gcnk_topic_graph_workspace_bytes",
+                            "gcnk_spmm_route", "gcnk_dense_gc1_route", "gcnk_topic_graph_chunk",
+                            "gcnk_topic_graph_max_topics", "gcnk_topic_graph_nnz_bound",
+                            "gcnk_topic_graph_workspace_bytes",
                             "gcnk_topic_graph_build", "gcnk_topic_cosine_f64", "gcnk_lda_max_topics",
                             "gcnk_lda_tile_words", "gcnk_lda_docs_per_block", "gcnk_lda_exp_dirichlet_f64",
                             "gcnk_lda_table_from_exp_f64", "gcnk_lda_estep_f64", "gcnk_lda_words_per_block",

@@ -428,25 +428,38 @@ dense_gc1_kernel(DenseArgs a) {
   stamp(a.epi, 3);
 }
 
-// NI = 3 (the rotating tail) while F <= 208, P <= 20 and KS <= 25 (past those
-// its registers spill); otherwise NI = 4 with one or two MFMA tiles of P
-template <int KS>
-int launch_ks(const DenseArgs& a, unsigned grid, hipStream_t s) {
-  if constexpr (KS <= 25) {
-    if (a.F <= kTail0 + 16 && a.P <= 20) {
-      if (a.P <= 16)
-        hipLaunchKernelGGL((dense_gc1_kernel<KS, 3, 1, 0>), dim3(grid), dim3(kThreads), 0, s, a);
-      else
-        hipLaunchKernelGGL((dense_gc1_kernel<KS, 3, 1, 4>), dim3(grid), dim3(kThreads), 0, s, a);
-      return launch_check("dense_gc1_kernel");
-    }
-  }
-  if (a.P <= 16) {
-    hipLaunchKernelGGL((dense_gc1_kernel<KS, 4, 1, 0>), dim3(grid), dim3(kThreads), 0, s, a);
+// What gcnk_dense_gc1_f32 launches for a shape, and whether it launches at all:
+// the one place these rules live.  The entry point launches from this and
+// gcnk_dense_gc1_route reports it; no HIP call here (the grid's cap of two
+// workgroups per CU is the launch's).  Returns the first check that fails, in
+// the entry point's order (its own checks on the other operands sit between
+// them): 0 none, 1 sizes, 3 unsupported shape.
+//   KS: the k-steps of W1, the smallest of 8 / 13 / 16 / 25 / 32 with K <= 4 KS.
+//   NI = 3 (the rotating tail n-tile past column 192) while F <= 208, P <= 20
+//   and KS <= 25 (past those its registers spill), P's columns past 16 on the
+//   VALU (PV = 4); otherwise NI = 4 with one or two MFMA tiles of P.
+// The 18 instantiations dense_gc1_kernel<KS, NI, NPM, PV>:
+//   KS 8, 13, 16, 25 x {<3, 1, 0>, <3, 1, 4>, <4, 1, 0>, <4, 2, 0>}
+//   KS 32            x {<4, 1, 0>, <4, 2, 0>}
+struct DenseRoute {
+  int ks, ni, npm, pv, tail;
+  int64_t ntiles;   // ceil(M / 16)
+};
+
+int dense_gc1_route(int32_t M, int32_t K, int32_t F, int32_t P, DenseRoute& rt) {
+  rt = DenseRoute{};
+  if (M <= 0 || K <= 0 || F <= 0 || P <= 0) return 1;
+  if (K > 128 || F > 256 || F % 4 || P > kMaxP) return 3;
+  const int ks = (K + 3) / 4;
+  rt.ks = ks <= 8 ? 8 : ks <= 13 ? 13 : ks <= 16 ? 16 : ks <= 25 ? 25 : 32;
+  if (rt.ks <= 25 && F <= kTail0 + 16 && P <= 20) {
+    rt.ni = 3; rt.npm = 1; rt.pv = P <= 16 ? 0 : 4;
   } else {
-    hipLaunchKernelGGL((dense_gc1_kernel<KS, 4, 2, 0>), dim3(grid), dim3(kThreads), 0, s, a);
+    rt.ni = 4; rt.npm = P <= 16 ? 1 : 2; rt.pv = 0;
   }
-  return launch_check("dense_gc1_kernel");
+  rt.tail = rt.ni == 3 && F > kTail0;
+  rt.ntiles = ((int64_t)M + 15) / 16;
+  return 0;
 }
 
 int cu_count() {
@@ -461,15 +474,10 @@ int cu_count() {
   return n;
 }
 
-int launch(const DenseArgs& a, hipStream_t s) {
-  // persistent: 4 waves per workgroup, two workgroups per CU (<= 256 registers a wave)
-  const unsigned grid = (unsigned)std::min<int64_t>(a.ntiles, 2 * cu_count());
-  const int ks = (a.K + 3) / 4;
-  if (ks <= 8) return launch_ks<8>(a, grid, s);
-  if (ks <= 13) return launch_ks<13>(a, grid, s);
-  if (ks <= 16) return launch_ks<16>(a, grid, s);
-  if (ks <= 25) return launch_ks<25>(a, grid, s);
-  return launch_ks<32>(a, grid, s);
+template <int KS, int NI, int NPM, int PV>
+int launch_dense(const DenseArgs& a, unsigned grid, hipStream_t s) {
+  hipLaunchKernelGGL((dense_gc1_kernel<KS, NI, NPM, PV>), dim3(grid), dim3(kThreads), 0, s, a);
+  return launch_check("dense_gc1_kernel");
 }
 
 }  // namespace
@@ -477,17 +485,34 @@ int launch(const DenseArgs& a, hipStream_t s) {
 
 using namespace gcnk;
 
+extern "C" int gcnk_dense_gc1_route(int32_t M, int32_t K, int32_t F, int32_t P, int64_t* out6) {
+  DenseRoute rt;
+  const int bad = out6 ? dense_gc1_route(M, K, F, P, rt) : 1;
+  if (bad == 1) {
+    set_error("gcnk_dense_gc1_route: null out6 or bad sizes (M=%d K=%d F=%d P=%d)", M, K, F, P);
+    return GCNK_EARG;
+  }
+  if (bad) {
+    set_error("gcnk_dense_gc1_route: unsupported shape (K=%d <= 128, F=%d <= 256 and %% 4, P=%d <= 32)", K, F, P);
+    return GCNK_EUNSUP;
+  }
+  out6[0] = rt.ks; out6[1] = rt.ni; out6[2] = rt.npm; out6[3] = rt.pv; out6[4] = rt.tail; out6[5] = rt.ntiles;
+  return GCNK_OK;
+}
+
 extern "C" int gcnk_dense_gc1_f32(int32_t M, int32_t K, int32_t F, int32_t P, const float* AX, int64_t ldax,
                                   const float* W1, int64_t ldw1, const float* bias, int32_t epilogue,
                                   const uint8_t* drop_mask, int64_t ldm, float drop_scale, float keep_prob,
                                   uint64_t seed, uint64_t offset, const uint64_t* rng_base, const float* W2,
                                   int64_t ldw2, float* H, int64_t ldh, float* C2, int64_t ldc2, void* stream) {
-  if (M <= 0 || K <= 0 || F <= 0 || P <= 0 || !AX || !W1 || !W2 || !C2 || ldax < K || ldw1 < F || ldw2 < P ||
+  DenseRoute rt;
+  const int bad = dense_gc1_route(M, K, F, P, rt);
+  if (bad == 1 || !AX || !W1 || !W2 || !C2 || ldax < K || ldw1 < F || ldw2 < P ||
       ldc2 < P || (H && ldh < F)) {
     set_error("gcnk_dense_gc1_f32: bad sizes or null operand (M=%d K=%d F=%d P=%d)", M, K, F, P);
     return GCNK_EARG;
   }
-  if (K > 128 || F > 256 || F % 4 || P > kMaxP || ldw1 % 4 || !aligned16(W1) ||
+  if (bad == 3 || ldw1 % 4 || !aligned16(W1) ||
       (int64_t)K * ldw1 * 4 >= INT32_MAX || (int64_t)F * ldw2 * 4 >= INT32_MAX ||   // (32-bit buffer offsets;
       (int64_t)16 * ldax * 4 >= kBufOob ||                                             //  A's tile sentinel past them)
       (bias && !aligned16(bias)) || (H && (ldh % 4 || !aligned16(H)))) {
@@ -504,6 +529,19 @@ extern "C" int gcnk_dense_gc1_f32(int32_t M, int32_t K, int32_t F, int32_t P, co
   a.M = M; a.K = K; a.F = F; a.P = P;
   a.A = AX; a.lda = ldax; a.W = W1; a.ldw = ldw1; a.W2 = W2; a.ldw2 = ldw2;
   a.H = H; a.ldh = ldh; a.C2 = C2; a.ldc2 = ldc2;
-  a.ntiles = (M + 15) / 16;
-  return launch(a, reinterpret_cast<hipStream_t>(stream));
+  a.ntiles = (int32_t)rt.ntiles;
+  // persistent: 4 waves per workgroup, two workgroups per CU (<= 256 registers a wave)
+  const unsigned grid = (unsigned)std::min<int64_t>(rt.ntiles, 2 * cu_count());
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const int ks = rt.ks, ni = rt.ni, npm = rt.npm, pv = rt.pv;
+#define GCNK_DENSE_CASE(KS_, NI_, NPM_, PV_) \
+  if (ks == KS_ && ni == NI_ && npm == NPM_ && pv == PV_) return launch_dense<KS_, NI_, NPM_, PV_>(a, grid, s);
+#define GCNK_DENSE_KS(KS_) \
+  GCNK_DENSE_CASE(KS_, 3, 1, 0) GCNK_DENSE_CASE(KS_, 3, 1, 4) GCNK_DENSE_CASE(KS_, 4, 1, 0) GCNK_DENSE_CASE(KS_, 4, 2, 0)
+  GCNK_DENSE_KS(8) GCNK_DENSE_KS(13) GCNK_DENSE_KS(16) GCNK_DENSE_KS(25)
+  GCNK_DENSE_CASE(32, 4, 1, 0) GCNK_DENSE_CASE(32, 4, 2, 0)
+#undef GCNK_DENSE_KS
+#undef GCNK_DENSE_CASE
+  set_error("gcnk_dense_gc1_f32: no kernel for K=%d F=%d P=%d", K, F, P);
+  return GCNK_EUNSUP;
 }

@@ -62,7 +62,7 @@ extern "C" {
 
 /* ABI note: 13 also covers gcnk_factor_diag_f32, gcnk_hubfactor_gc2_f32, the
  * gc2_* fields at the end of gcnk_gcn_fwd and the route reports
- * gcnk_gcn_bwd2_route / gcnk_hubfactor_gc1_route / gcnk_spmm_route and held-graph scoring,
+ * gcnk_gcn_bwd2_route / gcnk_hubfactor_gc1_route / gcnk_spmm_route / gcnk_dense_gc1_route and held-graph scoring,
  * gcnk_score_docs_f32 / gcnk_score_docs_route, and the graph built on the
  * device, gcnk_topic_graph_* / gcnk_topic_cosine_f64, and the topic mixtures
  * inferred and the topic model fitted on the device, gcnk_lda_* (additions only: no existing
@@ -457,6 +457,19 @@ int gcnk_dense_gc1_f32(int32_t M, int32_t K, int32_t F, int32_t P, const float* 
                        int64_t ldw1, const float* bias, int32_t epilogue, const uint8_t* drop_mask, int64_t ldm,
                        float drop_scale, float keep_prob, uint64_t seed, uint64_t offset, const uint64_t* rng_base,
                        const float* W2, int64_t ldw2, float* H, int64_t ldh, float* C2, int64_t ldc2, void* stream);
+/* Test aid (within ABI 13, an addition only): what gcnk_dense_gc1_f32 launches
+ * for these sizes, from the host function the launch itself is made from
+ * (nothing is launched here, no GPU is needed).  out6 =
+ *   0 KS, 1 NI, 2 NPM, 3 PV   the instantiation dense_gc1_kernel<KS, NI, NPM, PV>:
+ *                       k-steps of AX W1 (8, 13, 16, 25, 32), 16-column n-tiles
+ *                       of F per wave (3, 4), MFMA tiles of P (1, 2), columns of
+ *                       P past them on the VALU (0, 4)
+ *   4 tail              1 when NI = 3 and F > 192: the rotating tail n-tile runs
+ *   5 ntiles            16-row tiles, ceil(M / 16); the launch's grid is
+ *                       min(ntiles, two workgroups per CU)
+ * GCNK_EARG / GCNK_EUNSUP where gcnk_dense_gc1_f32 returns them for these
+ * sizes (a size <= 0; K > 128, F > 256, F % 4, P > 32). */
+int gcnk_dense_gc1_route(int32_t M, int32_t K, int32_t F, int32_t P, int64_t* out6);
 int gcnk_aggregate_f32(const int32_t* rowptr, const int32_t* colind, const float* val, int32_t M, const float* X,
                        int64_t ldx, int32_t K, float* out, int64_t ldo, int32_t Kp, void* stream);
 

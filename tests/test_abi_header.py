@@ -98,7 +98,7 @@ def test_text_outside_the_extern_block_and_a_missing_header_raise(tmp_path):
 
 def test_real_header_is_read_whole_and_the_public_names_are_its_structs():
     sig, structs, const = _lib.read_header()
-    assert len(sig) == 83 and set(test_abi._declared_symbols()) == set(sig) == set(_lib.SIGNATURES)
+    assert len(sig) == 84 and set(test_abi._declared_symbols()) == set(sig) == set(_lib.SIGNATURES)
     assert {k: C.sizeof(v) for k, v in structs.items()} == {
         "gcnk_plan_ref": 112, "gcnk_gcn_fwd": 536, "gcnk_gcn_bwd": 440, "gcnk_adam_tensor": 40, "gcnk_epoch_state": 32,
         "gcnk_keep_tensor": 24, "gcnk_keep_state": 16}
