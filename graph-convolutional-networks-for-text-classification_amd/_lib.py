@@ -1,13 +1,10 @@
-"""ctypes binding of libgcnk.so (the C-ABI declared in include/gcnk.h).
+"""ctypes binding of libgcnk.so (the C-ABI declared in include/gcnk.h and its family headers).
 
-The header is the only statement of the ABI: every entry point's signature,
-every struct and every ``GCNK_*`` constant is read from it when this module is
-imported (``parse_header``), so a new entry point is declared there,
-implemented, and bound.  What the reader cannot take whole it refuses.
-include/gcnk_lda_bound.h, which gcnk.h includes, declares the topic model's
-bound, score and perplexity in the same form and is read the same way
-(``LDA_BOUND_SIGNATURES``), and so is include/gcnk_text.h, which declares the
-word counter (``TEXT_SIGNATURES``).
+The headers are the only statement of the ABI: every entry point's signature,
+every struct and every ``GCNK_*`` constant is read from them when this module
+is imported (``read_headers``), so a new entry point is declared in its
+family's header, or in a new header that gcnk.h includes, implemented, and
+bound.  What the reader cannot take whole it refuses.
 
 The shared library is built in-tree by ``__graft_entry__.build()`` (or
 ``make -C <package>/csrc``).  There is no fallback: if the library is missing
@@ -43,13 +40,8 @@ def _resolve_lib():
 LIB_PATH = _resolve_lib()
 
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "gcnk.h")
-# the topic model's bound, score and perplexity: a header of its own in gcnk.h's form, which gcnk.h includes
-LDA_BOUND_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "gcnk_lda_bound.h")
-# counting words (CountVectorizer.transform): a header of its own the same way
-TEXT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "gcnk_text.h")
 
-# ---- The binding is read from include/gcnk.h, once, at import: entry points, structs and constants are stated
-# there and nowhere else.
+# ---- The binding is read from include/gcnk.h and the headers it includes, once, at import: they alone state the ABI.
 _SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint32_t": ctypes.c_uint32,
             "uint64_t": ctypes.c_uint64, "float": ctypes.c_float, "double": ctypes.c_double}
 _POINTEES = ("void", "char", "uint8_t")   # what a pointer may point to besides a scalar and a struct
@@ -57,88 +49,101 @@ _DEFINE = re.compile(r"^[ \t]*#[ \t]*define[ \t]+GCNK_(\w+)[ \t]+(\S.*?)[ \t]*$"
 _STRUCT = re.compile(r"typedef\s+struct\s+\w+\s*\{([^{}]*)\}\s*(\w+)\s*;\s*")
 _FUNCTION = re.compile(r"([\w\s*]+?)\b(gcnk_\w+)\s*\(([^()]*)\)\s*;\s*")
 _DECLARATOR = re.compile(r"(.*?[\s*])((?:\w+(?:\[\d+\])?\s*,\s*)*\w+(?:\[\d+\])?)", re.S)
+_COMMENT = re.compile(r"/\*.*?\*/|//[^\n]*", re.S)
+_INCLUDE = re.compile(r'^[ \t]*#[ \t]*include[ \t]+"(gcnk_\w+\.h)"', re.M)   # a family header, beside the one naming it
 
 
-def _ctype(spelling, structs, decl):
+def _ctype(spelling, structs, decl, header):
     """The ctypes class of a C type as the header spells it: a pointer is c_void_p (``const char*``: c_char_p), a
-    scalar its ctypes namesake, an earlier struct that struct.  ``decl``: the declaration, for the error."""
+    scalar its ctypes namesake, an earlier struct that struct.  ``decl``, ``header``: for the error."""
     words = spelling.replace("*", " * ").split()
     base = [w for w in words if w not in ("const", "*")]
     if len(base) != 1 or not (base[0] in _SCALARS or base[0] in structs or ("*" in words and base[0] in _POINTEES)):
-        raise RuntimeError(f"gcnk.h: unknown type '{' '.join(spelling.split())}' in '{decl}'")
+        raise RuntimeError(f"{header}: unknown type '{' '.join(spelling.split())}' in '{decl}'")
     if "*" in words:
         return ctypes.c_char_p if base[0] == "char" and "const" in words else ctypes.c_void_p
     return _SCALARS.get(base[0]) or structs[base[0]]
 
 
-def _declared(decl, structs, member):
+def _declared(decl, structs, member, header):
     """[(name, ctypes class)] of a struct's member declaration (``T a, b``, ``T a[16]``) or of a function's parameter
     (one name, no array)."""
     decl = " ".join(decl.split())
     m = _DECLARATOR.fullmatch(decl)
     if not m or ("*" in m.group(1) and "," in m.group(2)) or ("[" in m.group(2) and not member):
-        raise RuntimeError(f"gcnk.h: cannot read the declaration '{decl}'")
-    ctype = _ctype(m.group(1), structs, decl)
+        raise RuntimeError(f"{header}: cannot read the declaration '{decl}'")
+    ctype = _ctype(m.group(1), structs, decl, header)
     names = [d.strip().rstrip("]").partition("[") for d in m.group(2).split(",")]
     return [(name, ctype * int(dim) if dim else ctype) for name, _, dim in names]
 
 
-def parse_header(text):
+def parse_header(text, header="gcnk.h"):
     """(signatures, structs, constants) of a header in include/gcnk.h's form: {entry point: (restype, [argtypes])},
     {typedef'd struct: its ctypes.Structure} and {NAME: value} for every ``#define GCNK_<NAME> <integer>``.  Besides
     comments and preprocessor lines the text is one ``extern "C" { ... }`` of function declarations and struct
-    typedefs; anything else raises RuntimeError naming it, because an entry point left unbound would be called with
-    ctypes' default conversions (a pointer passed as a 32-bit int)."""
-    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    typedefs; anything else raises RuntimeError naming ``header`` and it, because an entry point left unbound would
+    be called with ctypes' default conversions (a pointer passed as a 32-bit int)."""
+    text = _COMMENT.sub(" ", text)
     constants = {}
     for name, value in _DEFINE.findall(text):
         try:
             constants[name] = int(value[1:-1] if value[0] + value[-1] == "()" else value, 0)
         except ValueError:   # (an expression, or another macro's name)
-            raise RuntimeError(f"gcnk.h: GCNK_{name} is defined as '{value}', not as an integer") from None
+            raise RuntimeError(f"{header}: GCNK_{name} is defined as '{value}', not as an integer") from None
     code = "\n".join(line for line in text.splitlines() if not line.lstrip().startswith("#"))
     block = re.fullmatch(r'\s*extern\s+"C"\s*\{\s*(.*)\}\s*', code, re.S)
     if not block:
-        raise RuntimeError('gcnk.h: expected one extern "C" { ... } block and nothing outside it')
+        raise RuntimeError(f'{header}: expected one extern "C" {{ ... }} block and nothing outside it')
     body, pos, signatures, structs = block.group(1), 0, {}, {}
     while pos < len(body):
         s = _STRUCT.match(body, pos)
         f = None if s else _FUNCTION.match(body, pos)
         if s:
-            fields = [fld for d in s.group(1).split(";") if d.strip() for fld in _declared(d, structs, True)]
+            fields = [fld for d in s.group(1).split(";") if d.strip() for fld in _declared(d, structs, True, header)]
             structs[s.group(2)] = type(s.group(2), (ctypes.Structure,), {"_fields_": fields})
         elif f:
             params = [] if f.group(3).strip() == "void" else f.group(3).split(",")
-            signatures[f.group(2)] = (_ctype(f.group(1), structs, f.group(2)),
-                                      [_declared(p, structs, False)[0][1] for p in params])
+            signatures[f.group(2)] = (_ctype(f.group(1), structs, f.group(2), header),
+                                      [_declared(p, structs, False, header)[0][1] for p in params])
         else:
             stmt = " ".join(body[pos:body.find(";", pos) + 1 or None].split())
-            raise RuntimeError(f"gcnk.h: neither a function declaration nor a struct typedef: '{stmt[:200]}'")
+            raise RuntimeError(f"{header}: neither a function declaration nor a struct typedef: '{stmt[:200]}'")
         pos = (s or f).end()   # (each pattern takes the white space behind its statement)
     return signatures, structs, constants
 
 
-def read_header(path=HEADER_PATH):
+def _header_text(path):
     if not os.path.exists(path):
-        raise RuntimeError(f"gcnk.h not found at {path}: libgcnk.so is bound from the header it was built with "
-                           "(include/gcnk.h of the source tree). There is no hand-written fallback.")
+        raise RuntimeError(f"header not found at {path}: libgcnk.so is bound from its source tree's include/ alone")
     with open(path) as f:
-        return parse_header(f.read())
+        return f.read()
 
 
-# name -> (restype, argtypes) of every entry point; C name -> ctypes.Structure; GCNK_<NAME> -> value
-SIGNATURES, STRUCTS, CONSTANTS = read_header()
+def read_header(path=HEADER_PATH):
+    return parse_header(_header_text(path), os.path.basename(path))
+
+
+def read_headers(path=HEADER_PATH):
+    """The header at ``path`` and then every ``#include "gcnk_*.h"`` it names, beside it and in the order named, as
+    one ABI -> (paths, {entry point: its header's basename}, signatures, structs, constants).  An entry point, struct
+    or constant that two headers declare raises RuntimeError naming both."""
+    names = _INCLUDE.findall(_COMMENT.sub(" ", _header_text(path)))
+    paths = [path] + [os.path.join(os.path.dirname(path), name) for name in names]
+    where, merged = {}, ({}, {}, {})   # C name -> header; signatures, structs, constants
+    for p in paths:
+        for into, part, prefix in zip(merged, read_header(p), ("", "", "GCNK_")):
+            for key, value in part.items():
+                if prefix + key in where:
+                    raise RuntimeError(f"{os.path.basename(p)}: {prefix}{key} is declared in {where[prefix + key]} too")
+                where[prefix + key], into[key] = os.path.basename(p), value
+    return (paths, {name: where[name] for name in merged[0]}, *merged)
+
+
+# header paths, gcnk.h's first; entry point -> header, -> (restype, argtypes); struct -> class; GCNK_<NAME> -> value
+HEADERS, DECLARED_IN, SIGNATURES, STRUCTS, CONSTANTS = read_headers()
 if set(CONSTANTS) & set(globals()):
-    raise RuntimeError(f"gcnk.h: GCNK_{sorted(set(CONSTANTS) & set(globals()))[0]} would replace a name of {__name__}")
+    raise RuntimeError(f"GCNK_{sorted(set(CONSTANTS) & set(globals()))[0]} would replace a name of {__name__}")
 globals().update(CONSTANTS)   # GCNK_OK is _lib.OK, GCNK_EPI_BIAS_RELU _lib.EPI_BIAS_RELU, ..., GCNK_ABI_VERSION too
-# name -> (restype, argtypes) of gcnk_lda_bound.h's entry points, read the same way (it holds nothing else)
-LDA_BOUND_SIGNATURES, _structs, _constants = read_header(LDA_BOUND_HEADER_PATH)
-if _structs or _constants or set(LDA_BOUND_SIGNATURES) & set(SIGNATURES):
-    raise RuntimeError("gcnk_lda_bound.h: expected function declarations alone, none of them gcnk.h's own")
-# name -> (restype, argtypes) of gcnk_text.h's entry points, likewise
-TEXT_SIGNATURES, _structs, _constants = read_header(TEXT_HEADER_PATH)
-if _structs or _constants or set(TEXT_SIGNATURES) & (set(SIGNATURES) | set(LDA_BOUND_SIGNATURES)):
-    raise RuntimeError("gcnk_text.h: expected function declarations alone, none of them another header's")
 AdamTensor, EpochState = STRUCTS["gcnk_adam_tensor"], STRUCTS["gcnk_epoch_state"]
 KeepTensor, KeepState = STRUCTS["gcnk_keep_tensor"], STRUCTS["gcnk_keep_state"]
 
@@ -171,18 +176,12 @@ def epoch_row_words(nclass):
     return 3 * nclass + 3
 
 
-# added within ABI 13 (gc2 from the hub factor, the backward's and the factored gc1's route reports): absent from
-# variants of an older tree
+# added within ABI 13 (gc2 from the hub factor, the backward's and the factored gc1's route reports, and every family
+# header's entry points): absent from variants of an older tree
 NEWER_THAN_SOME_VARIANTS = ("gcnk_hubfactor_gc2_f32", "gcnk_factor_diag_f32", "gcnk_gcn_bwd2_route",
                             "gcnk_hubfactor_gc1_route", "gcnk_score_docs_f32", "gcnk_score_docs_route",
-                            "gcnk_spmm_route", "gcnk_dense_gc1_route", "gcnk_topic_graph_chunk",
-                            "gcnk_topic_graph_max_topics", "gcnk_topic_graph_nnz_bound",
-                            "gcnk_topic_graph_workspace_bytes",
-                            "gcnk_topic_graph_build", "gcnk_topic_cosine_f64", "gcnk_lda_max_topics",
-                            "gcnk_lda_tile_words", "gcnk_lda_docs_per_block", "gcnk_lda_exp_dirichlet_f64",
-                            "gcnk_lda_table_from_exp_f64", "gcnk_lda_estep_f64", "gcnk_lda_words_per_block",
-                            "gcnk_lda_estep_fit_f64", "gcnk_lda_mstep_f64", "gcnk_lda_mstep_online_f64",
-                            *LDA_BOUND_SIGNATURES, *TEXT_SIGNATURES)
+                            "gcnk_spmm_route", "gcnk_dense_gc1_route",
+                            *(name for name, header in DECLARED_IN.items() if header != "gcnk.h"))
 
 _lock = threading.Lock()
 _lib = None
@@ -205,7 +204,7 @@ def load():
                 f"libgcnk.so not found at {LIB_PATH}: build it with __graft_entry__.build() "
                 "or `make -C <package>/csrc` (hipcc --offload-arch=gfx950). There is no CPU fallback.")
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in (*SIGNATURES.items(), *LDA_BOUND_SIGNATURES.items(), *TEXT_SIGNATURES.items()):
+        for name, (res, args) in SIGNATURES.items():
             fn = getattr(lib, name, None)
             if fn is None:
                 # an experiment variant built from an older csrc (an A/B's parent library)

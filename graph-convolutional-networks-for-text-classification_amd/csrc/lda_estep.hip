@@ -57,9 +57,10 @@
 // terms (a workgroup per topic, the table builder's serial row sum) and one workgroup that sums both and the counts.
 // Every sum has a fixed order: no atomics, no workspace, no host synchronisation.
 //
-// The entry points, at the end of the file, are four families, each with its refusals and launch stated once:
+// The entry points, at the end of the file and all declared in include/gcnk_lda.h, are four families, each with
+// its refusals and launch stated once:
 //     bound     gcnk_lda_bound_docs_f64 (check_table, check_documents), gcnk_lda_bound_topics_f64,
-//               gcnk_lda_bound_finish_f64 (check_topics); declared in include/gcnk_lda_bound.h
+//               gcnk_lda_bound_finish_f64 (check_topics)
 //     tables    gcnk_lda_exp_dirichlet_f64, gcnk_lda_table_from_exp_f64: check_table, then their own source check
 //     E-step    gcnk_lda_estep_f64 (transform), gcnk_lda_estep_fit_f64 (both fits): estep_args -- check_table, the
 //               document refusals, the common EStep fields -- then each one's own outputs; launch_estep<kFit>

@@ -24,7 +24,7 @@ psi(lambda_kw) - psi(sum_w lambda_kw), psi sklearn's AS 103:
 ``_unnormalized_transform``: the E-step started from gamma = 1).  An evaluation is
 the gamma E-step and three launches (the documents' terms, one wave each; the
 topics' terms, cached; one workgroup that sums), all queued on the current stream:
-nothing synchronises, every sum has a fixed order (include/gcnk_lda_bound.h), so a
+nothing synchronises, every sum has a fixed order (include/gcnk_lda.h), so a
 result is bitwise reproducible and a document's term does not depend on its batch.
 
 The limit of the model's validity: the logsumexp shifts theta's side only and

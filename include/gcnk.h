@@ -23,10 +23,12 @@
  *   trainer.py:98-148 edge list -> symmetric adjacency        -> gcnk_edgelist_size / _csr (host, no networkx)
  *   build_graph.py:99-133 theta, topic similarities -> graph   -> gcnk_topic_graph_build (device, straight to A-hat)
  *   build_graph.py:118 cosine_similarity(topic_embeddings)     -> gcnk_topic_cosine_f64
+ *                                                            (both in gcnk_topic_graph.h, included below)
  *   topic_model.py:133-164 LatentDirichletAllocation.transform -> gcnk_lda_estep_f64 (device, a wave per document)
  *   topic_model.py:74-131  LatentDirichletAllocation.fit (batch) -> gcnk_lda_estep_fit_f64 + gcnk_lda_mstep_f64
  *   experiments/r8.yaml num_topics, max_iter: LatentDirichletAllocation.score / perplexity / bound_
- *                                                            -> gcnk_lda_bound_*_f64 (gcnk_lda_bound.h, included below)
+ *                                                            -> gcnk_lda_bound_*_f64
+ *                                                            (every gcnk_lda_* in gcnk_lda.h, included below)
  *   topic_model.py:159 CountVectorizer.transform (unseen text) -> gcnk_text_count + gcnk_text_emit (gcnk_text.h, below)
  *   layer.py:185 th.dropout keep-mask draw (CPU generator)    -> gcnk_bernoulli_mt19937 (host, same stream)
  *   trainer.py:307, 358-361, 383-384 CrossEntropyLoss on logits[idx] -> gcnk_ce_forward_f32 / gcnk_ce_backward_f32
@@ -983,201 +985,13 @@ int gcnk_keep_best_f32(const gcnk_keep_tensor* t /* host */, int32_t ntensors, c
 int gcnk_edgelist_size(const char* path, int64_t* n_nodes, int64_t* nnz);
 int gcnk_edgelist_csr(const char* path, int64_t n_nodes, int64_t nnz, int32_t* rowptr, int32_t* colind, float* val);
 
-/* ---------------------------------------------------------------------------
- * The doc-topic graph built on the device (csrc/topic_graph.hip; additions
- * within ABI 13): the topic model's output -> the CSR of A-hat, without the
- * nx.Graph, the text edge list and scipy of build_graph.py:99-133 and
- * trainer.py:98-151.  N = D + K nodes: documents 0 .. D-1, topics D .. N-1.
- *   theta [D x K], sim [K x K] (nullable: no topic-topic edges): row-major
- *     fp64 (*_f32 = 0) or fp32 (*_f32 = 1, widened exactly), leading
- *     dimensions ldt / lds in elements.
- *   edge (d, D+k)    iff theta[d,k] >= doc_topic_threshold, in float64
- *                    (build_graph.py:106), weight float32(theta[d,k]);
- *   edge (D+i, D+j)  i < j, iff sim[i,j] > topic_topic_threshold (strict,
- *                    build_graph.py:124), weight float32(sim[i,j]); the lower
- *                    triangle and the diagonal of sim are never read;
- *   A_hat = D^-1/2 (A + I) D^-1/2 with gcnk_sym_normalize's arithmetic: float64
- *     row sums taken sequentially in ascending column order with the diagonal
- *     at its sorted place, d = rowsum^-0.5 (inf -> 0), (d[r] a) d[c] rounded
- *     to fp32 once -- bit for bit what the reference's path gives.
- * Unlike the reference, a document or topic without a kept edge is still a
- * node (its row is the diagonal alone, A_hat = 1.0), and NaN / negative theta
- * is not looked for (a NaN compares false and is dropped).
- * Output: rowptr int32[N + 1] (rowptr[N] = nnz, readable once the stream
- * completes), colind / val of `capacity` >= gcnk_topic_graph_nnz_bound(D, K,
- * sim != NULL) entries, columns ascending in every row; edges (nullable)
- * int32[2] = doc-topic edges, topic-topic edges (undirected counts:
- * nnz = N + 2 (edges[0] + edges[1])).  Nothing is allocated; six launches on
- * `stream`.  GCNK_EARG: D < 1, K < 1, a threshold not > 0 (0 would keep
- * explicit zeros), a null pointer, a leading dimension < K, a short capacity
- * or workspace.  GCNK_EUNSUP: K > gcnk_topic_graph_max_topics() (128), or
- * N + the nnz bound >= 2^31.  Every refusal comes before any HIP call.
- * gcnk_topic_graph_chunk(): documents per workgroup (256) -- a topic column's
- * entries are ranked per 64-document segment of such a chunk, in order.
- * ------------------------------------------------------------------------- */
-int32_t gcnk_topic_graph_chunk(void);
-int32_t gcnk_topic_graph_max_topics(void);
-int64_t gcnk_topic_graph_nnz_bound(int32_t D, int32_t K, int32_t has_sim);
-int64_t gcnk_topic_graph_workspace_bytes(int32_t D, int32_t K);
-int gcnk_topic_graph_build(const void* theta, int32_t theta_f32, int64_t ldt, const void* sim, int32_t sim_f32,
-                           int64_t lds, int32_t D, int32_t K, double doc_topic_threshold,
-                           double topic_topic_threshold, int32_t* rowptr, int32_t* colind, float* val,
-                           int64_t capacity, int32_t* edges, void* workspace, int64_t workspace_bytes, void* stream);
-/* sim [K x K] fp64 = the cosine similarity of the rows of emb [K x dim] (fp64,
- * or fp32 with emb_f32 = 1), build_graph.py:118: dot products and squared
- * norms as float64 sums in ascending index order, dot / (|a| |b|); a zero row
- * gives 0.  sim is written symmetric, diagonal included. */
-int gcnk_topic_cosine_f64(const void* emb, int32_t emb_f32, int64_t lde, int32_t K, int32_t dim, double* sim,
-                          int64_t lds, void* stream);
-
-/* ---------------------------------------------------------------------------
- * Documents' topic mixtures on the device (csrc/lda_estep.hip; additions within
- * ABI 13): the LDA E-step behind topic_model.py:133-164, sklearn's
- * LatentDirichletAllocation.transform, restated in float64 with sklearn's own
- * rules -- its AS 103 psi (_online_lda_fast.pyx, not an accurate digamma),
- * gamma = 1 at the start, eps = 2^-52 added to phi, the mean-change stop rule
- * taken after the prior is added.
- *
- * The model is held as a transposed table [V x ldt] float64, ldt even and >= K,
- * 16-byte aligned, V * ldt * 8 < 2^31 - 2^20: table[w * ldt + k] =
- * exp(E[log beta_kw]).  Columns K .. ldt-1 are never read into a sum and never
- * written.
- *   gcnk_lda_exp_dirichlet_f64   from components (lambda, [K x V], row stride
- *       ldc): exp(psi(lambda_kw) - psi(sum_w lambda_kw)), the row sum serial and
- *       ascending in w (_dirichlet_expectation_2d, then exp).
- *   gcnk_lda_table_from_exp_f64  the transpose of a model's own
- *       exp_dirichlet_component_ ([K x V], row stride lde), bit for bit.
- *
- * gcnk_lda_estep_f64: B documents as a CSR over the vocabulary -- indptr
- * int32[B + 1], indices int32, counts float64 / int32 / int64 (counts_kind 0 /
- * 1 / 2, widened exactly) -- one wave each, one launch:
- *     gamma = 1;  etheta_k = exp(psi(1) - psi(K))
- *     at most max_iter times:
- *       phi_w    = sum_k etheta_k table[id_w, k] + 2^-52
- *       gamma'_k = etheta_k * sum_w (c_w / phi_w) table[id_w, k] + alpha
- *       etheta_k = exp(psi(gamma'_k) - psi(sum_k gamma'_k))
- *       stop after this update if sum_k |gamma_k - gamma'_k| / K < tol
- *     theta = gamma / sum_k gamma
- * Sums over k ascend, sums over a document's words run in stored order (the two
- * dot products by fma, nothing else contracted): a document's row depends on its
- * own words and K alone, not on B, its place in the batch or the launch.  No
- * atomics, no workspace, no synchronisation.  Outputs, each nullable:
- *   theta, gamma  float64 [B x ldth]  (gamma: sklearn's _unnormalized_transform)
- *   iters         int32 [B], the updates run (0 .. max_iter)
- *   x, a          fp32 [B x ldx], [B x lda], given together: what
- *       gcnk_score_docs_f32 reads, made from this launch's theta as the
- *       reference makes them (trainer.py:205-221, build_graph.py:105-110):
- *       x = theta / (sum_k theta + 1e-8) rounded to fp32, over its float64 L2
- *       norm (a zero row stays zero), rounded to fp32; a = fp32(theta) where
- *       theta >= threshold in float64, else 0.  The two sums ascend in k.
- * A word id outside [0, V) is the caller's error and is not checked on the
- * device (the table is read through a bounds-checked buffer resource: such an id
- * reads another row or zeros).  indptr must ascend within the arrays given.
- * GCNK_EARG: B < 1, K < 1, V < 1, a null input, a bad table (see above),
- * counts_kind outside 0..2, max_iter outside [0, 10000], x without a or a
- * without x, no output at all, a leading dimension < K.  GCNK_EUNSUP: K >
- * gcnk_lda_max_topics() (128), a table past 32-bit byte offsets.  Every refusal
- * comes before any HIP call.  gcnk_lda_tile_words(): the words a wave holds in
- * LDS (64; a longer document walks chunks of that many, re-read every update);
- * gcnk_lda_docs_per_block(): waves per workgroup (2).
- * ------------------------------------------------------------------------- */
-int32_t gcnk_lda_max_topics(void);
-int32_t gcnk_lda_tile_words(void);
-int32_t gcnk_lda_docs_per_block(void);
-int gcnk_lda_exp_dirichlet_f64(const double* components, int64_t ldc, int32_t K, int32_t V, double* table, int64_t ldt,
-                               void* stream);
-int gcnk_lda_table_from_exp_f64(const double* exp_topic_word, int64_t lde, int32_t K, int32_t V, double* table,
-                                int64_t ldt, void* stream);
-int gcnk_lda_estep_f64(const int32_t* indptr, const int32_t* indices, const void* counts, int32_t counts_kind,
-                       int32_t B, int32_t V, int32_t K, const double* table, int64_t ldt, double alpha, double tol,
-                       int32_t max_iter, double* theta, int64_t ldth, double* gamma, int32_t* iters, float* x,
-                       int64_t ldx, float* a, int64_t lda, double threshold, void* stream);
-
-/* ---------------------------------------------------------------------------
- * The topic model fitted on the device (csrc/lda_estep.hip; additions within
- * ABI 13): sklearn's batch variational EM behind topic_model.py:74-131,
- * LatentDirichletAllocation.fit with learning_method='batch' (_lda.py
- * _em_step(batch_update=True)), all float64.  One EM iteration is three
- * launches on one stream, none of which synchronises:
- *   gcnk_lda_exp_dirichlet_f64   the table from lambda (above)
- *   gcnk_lda_estep_fit_f64       the update loop of gcnk_lda_estep_f64, the same
- *       device code instantiated a second time, started from gamma0 [B x ldg0]
- *       (sklearn's fresh Gamma(100, .01) draw of every EM iteration) instead of
- *       1: etheta_k = exp(psi(gamma0_k) - psi(sum_k gamma0_k)), the sum ascending.
- *       After the loop it walks the document's words once more with the final
- *       etheta: ratio[indptr[d] + w] = c_w / (sum_k etheta_k table[id_w, k] +
- *       2^-52), one per stored nonzero in CSR order (nnz of them), and stores
- *       etheta [B x lde]; gamma [B x ldg] and iters int32 [B] are nullable.
- *   gcnk_lda_mstep_f64           lambda[k * ldl + w] = eta + S_kw * table[w, k],
- *       S_kw = sum over the documents d that hold w, ASCENDING d, of
- *       etheta[d, k] * ratio[its entry]: the product rounded, then added (as
- *       np.outer and += do; no fma, no atomics), one wave per word and no word's
- *       chain split, so lambda is bit for bit that serial loop.  The word-major
- *       index of the document-term matrix: wptr int32 [V + 1] (word w's entries
- *       are [wptr[w], wptr[w + 1])), pos int32 [nnz] (an entry's position in CSR
- *       order, so in ratio) and doc int32 [nnz] (its document), a word's entries
- *       in ascending document order (a stable sort of indices).  A word no
- *       document holds gets exactly eta.
- * The M-step's chain runs over [wptr[w], wptr[w + 1]) clamped to [0, nnz]; ratio
- * and etheta are accessed through bounds-checked buffer resources (a bad pos or
- * doc reads zeros, a bad indptr stores nothing outside ratio).
- * GCNK_EARG: B < 1, K < 1, V < 1, a null pointer (gamma and iters excepted), a
- * bad table, counts_kind outside 0..2, max_iter outside [0, 10000], a leading
- * dimension below K (ldl below V), nnz < 0.  GCNK_EUNSUP: K > 128, a table, nnz
- * ratios or an etheta of B * lde doubles past 32-bit byte offsets (2^31 - 2^20).
- * Every refusal comes before any HIP call.  gcnk_lda_words_per_block(): the
- * M-step's waves per workgroup (4).
- * ------------------------------------------------------------------------- */
-int32_t gcnk_lda_words_per_block(void);
-int gcnk_lda_estep_fit_f64(const int32_t* indptr, const int32_t* indices, const void* counts, int32_t counts_kind,
-                           int32_t B, int32_t V, int32_t K, const double* table, int64_t ldt, double alpha, double tol,
-                           int32_t max_iter, const double* gamma0, int64_t ldg0, int64_t nnz, double* ratio,
-                           double* etheta, int64_t lde, double* gamma, int64_t ldg, int32_t* iters, void* stream);
-int gcnk_lda_mstep_f64(const int32_t* wptr, const int32_t* pos, const int32_t* doc, int64_t nnz, const double* ratio,
-                       const double* etheta, int64_t lde, int32_t B, int32_t V, int32_t K, const double* table,
-                       int64_t ldt, double eta, double* lambda, int64_t ldl, void* stream);
-
-/* ---------------------------------------------------------------------------
- * The topic model fitted ONLINE on the device (csrc/lda_estep.hip; an addition
- * within ABI 13): sklearn's minibatch variational EM, learning_method='online'
- * and partial_fit (_lda.py _em_step(batch_update=False)), which the reference's
- * TopicModel offers as learning_method (topic_model.py:46,55,113).  A minibatch
- * of documents [doc_lo, doc_hi) is three launches on one stream:
- *   gcnk_lda_exp_dirichlet_f64   the table from the current lambda
- *   gcnk_lda_estep_fit_f64       on the row range: indptr + doc_lo, B = doc_hi -
- *       doc_lo, gamma0 and etheta advanced by doc_lo rows, the WHOLE ratio and
- *       nnz (a ratio is stored at its absolute CSR position)
- *   gcnk_lda_mstep_online_f64    for every word w and topic k, in place, every
- *       line one correctly rounded float64 operation (no fma, no atomics):
- *           S   = sum over w's entries whose document d is in [doc_lo, doc_hi),
- *                 ASCENDING d, of etheta[d, k] * ratio[its entry] (the product
- *                 rounded, then added: gcnk_lda_mstep_f64's chain, the same code)
- *           ss  = S * table[w, k]
- *           t   = doc_ratio * ss
- *           u   = eta + t
- *           v   = rho * u
- *           a   = lambda[k * ldl + w] * (1.0 - rho)
- *           lambda[k * ldl + w] = a + v
- *       wptr / pos / doc are the word-major index of the WHOLE matrix, the one
- *       gcnk_lda_mstep_f64 takes; etheta is [B x lde] with the minibatch's rows
- *       filled.  A word's entries ascend in document, so the minibatch's are a
- *       contiguous sub-range of [wptr[w], wptr[w + 1]) (clamped to [0, nnz]),
- *       found on the device by a lower-bound search on doc for doc_lo and for
- *       doc_hi: no index is built per minibatch.  A word the minibatch does not
- *       hold is blended with S = 0.  rho = (learning_offset + n_batch_iter) ^
- *       -learning_decay is the caller's (float64, on the host); 1.0 - rho is
- *       formed from it once; rho = 1 gives a = +0.  doc_ratio = total_samples /
- *       (doc_hi - doc_lo).
- * GCNK_EARG: gcnk_lda_mstep_f64's (B < 1, K < 1, V < 1, a null pointer, a bad
- * table, lde < K, ldl < V, nnz < 0), doc_lo < 0, doc_hi > B, doc_lo >= doc_hi,
- * rho outside (0, 1] or not finite, doc_ratio not finite or <= 0.  GCNK_EUNSUP:
- * K > 128, a table, nnz ratios or an etheta past 32-bit byte offsets.  Every
- * refusal comes before any HIP call.
- * ------------------------------------------------------------------------- */
-int gcnk_lda_mstep_online_f64(const int32_t* wptr, const int32_t* pos, const int32_t* doc, int64_t nnz, int32_t doc_lo,
-                              int32_t doc_hi, const double* ratio, const double* etheta, int64_t lde, int32_t B,
-                              int32_t V, int32_t K, const double* table, int64_t ldt, double eta, double rho,
-                              double doc_ratio, double* lambda, int64_t ldl, void* stream);
+/* The doc-topic graph built on the device (additions within ABI 13), declared in a
+ * header of its own in this one's form. */
+#include "gcnk_topic_graph.h"
+/* The topic model on the device: documents' mixtures, the batch and the online fit,
+ * and the variational bound, score and perplexity (additions within ABI 13), the
+ * same way. */
+#include "gcnk_lda.h"
 
 /* ---------------------------------------------------------------------------
  * Dropout keep-mask exactly as the reference's CPU th.dropout draws it
@@ -1214,9 +1028,6 @@ int gcnk_stream_copy_f32(const float* src, float* dst, int64_t n, void* stream);
  * compiles it out: there it returns GCNK_EUNSUP for a non-null buffer. */
 int gcnk_debug_set_stamps(void* buf);
 
-/* The topic model's variational bound, score and perplexity (additions within
- * ABI 13), declared in a header of its own in this one's form. */
-#include "gcnk_lda_bound.h"
 /* Counting words, CountVectorizer.transform against a fitted vocabulary (additions
  * within ABI 13), the same way. */
 #include "gcnk_text.h"

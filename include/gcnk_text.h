@@ -2,8 +2,8 @@
  * gcnk_text.h — the part of libgcnk.so's C-ABI that counts words: sklearn's
  * CountVectorizer.transform of unseen text against a fitted vocabulary.
  * include/gcnk.h includes this file, so a C caller sees one ABI; it is a file
- * of its own in gcnk.h's form (_lib.py reads both with the same reader) so that
- * gcnk.h's own list of entry points stays the one its tests count.
+ * of its own in gcnk.h's form (_lib.py reads every public header with the same
+ * reader): a header per family.
  */
 #ifndef GCNK_TEXT_H_
 #define GCNK_TEXT_H_

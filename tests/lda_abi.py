@@ -1,13 +1,14 @@
-"""The call harness of the three LDA ABI test files (test_lda_abi.py, test_lda_fit_abi.py, test_lda_online_abi.py):
-one row per gcnk_lda_* entry point, and the declared / exported / bound check they share.  No GPU: every call made
-through here is refused before any HIP call, so PTR is never dereferenced."""
+"""The call harness of the LDA ABI test files (test_lda_abi.py, test_lda_fit_abi.py, test_lda_online_abi.py and
+test_lda_bound_abi.py): one row per gcnk_lda_* entry point, the declared / exported / bound check they share, and
+the whole of include/gcnk_lda.h against their names.  No GPU: every call made through here is refused before any HIP
+call, so PTR is never dereferenced."""
 import os
 
 import gcn_amd  # noqa: F401
 from graph_convolutional_networks_for_text_classification_amd import _lib
 
 import abi_bound
-from abi_bound import header  # noqa: F401  (the three files take it from here)
+from abi_bound import header  # noqa: F401  (the test files take it from here)
 
 CSRC = os.path.join(abi_bound.ROOT, "graph-convolutional-networks-for-text-classification_amd", "csrc")
 PTR = 0x10000   # an aligned address that no refused call dereferences
@@ -46,9 +47,9 @@ ENTRY = {
 }
 
 
-def call(name, **kw):
-    """The entry point on its defaults with ``kw`` over them -> (return code, gcnk_last_error)."""
-    spec = ENTRY[name]
+def call(name, entry=ENTRY, **kw):
+    """The entry point on its defaults (``entry``'s row) with ``kw`` over them -> (return code, gcnk_last_error)."""
+    spec = entry[name]
     assert set(kw) <= {k for k, _ in spec}, (name, kw)
     given = {k: kw.get(k, d) for k, d in spec if not callable(d)}
     lib = _lib.load()
@@ -63,8 +64,16 @@ def kernels_source():
         return f.read()
 
 
-def assert_declared_exported_bound(names):
-    """names: entry point -> its argument count, the stream included (abi_bound's check, and ENTRY's rows agree)."""
-    abi_bound.assert_declared_exported_bound(names)
+def assert_declared_exported_bound(names, entry=ENTRY, restype=None):
+    """names: entry point -> its argument count, the stream included (abi_bound's check against include/gcnk_lda.h,
+    and ``entry``'s rows agree)."""
+    abi_bound.assert_declared_exported_bound(names, restype=restype, header="gcnk_lda.h")
     for name, nargs in names.items():
-        assert name not in ENTRY or len(ENTRY[name]) + 1 == nargs
+        assert name not in entry or len(entry[name]) + 1 == nargs
+
+
+def all_names():
+    """The names of the four LDA ABI test files, which between them are to be all that gcnk_lda.h declares."""
+    import test_lda_abi, test_lda_bound_abi, test_lda_fit_abi, test_lda_online_abi   # noqa: E401 (they import this)
+    return (set(test_lda_abi.NAMES) | set(test_lda_fit_abi.NAMES) | {test_lda_online_abi.ONLINE}
+            | set(test_lda_bound_abi.NAMES))

@@ -9,7 +9,7 @@ rules (_lda.py _approx_bound, score, _perplexity_precomp_distr), on lda_ref's ps
     bound   = doc_ratio sum_d doc_d + sum_k topic_k      perplexity = exp(-bound / (doc_ratio sum c))
 
 The logsumexp here is the real one over the LOG-domain b (scipy's unless another is given): the device's shifted
-form over the exp table is what is under test.  The summation orders are the ones include/gcnk_lda_bound.h
+form over the exp table is what is under test.  The summation orders are the ones include/gcnk_lda.h
 documents: sums over k ascend; a document's words in tiles of 64, a tile by the wave tree, the tiles one after the
 other; a topic's words dealt to 256 threads (thread t: words t, t + 256, ... ascending), then the block tree; the
 final sums dealt to 1024 threads the same way.

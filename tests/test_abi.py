@@ -1,6 +1,7 @@
 """CPU checks of the C-ABI boundary: the library loads, exports every symbol
-include/gcnk.h declares, and validates arguments (no compute without a GPU)."""
+the headers under include/ declare, and validates arguments (no compute without a GPU)."""
 import ctypes
+import glob
 import os
 import re
 
@@ -13,8 +14,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _declared_symbols():
-    with open(os.path.join(ROOT, "include", "gcnk.h")) as f:
-        src = f.read()
+    src = ""
+    for path in sorted(glob.glob(os.path.join(ROOT, "include", "*.h"))):   # gcnk.h and every family header
+        with open(path) as f:
+            src += f.read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     return sorted(set(re.findall(r"\b(gcnk_[a-z0-9_]+)\s*\(", src)))
 
@@ -25,7 +28,7 @@ def test_library_exports_every_declared_symbol():
     assert len(declared) >= 14
     for name in declared:
         assert hasattr(lib, name), name
-    assert set(declared) == set(_lib.SIGNATURES), "ctypes signatures out of sync with include/gcnk.h"
+    assert set(declared) == set(_lib.SIGNATURES), "ctypes signatures out of sync with include/*.h"
 
 
 MAGIC = sparse.PLAN_MAGIC  # plan header word 0 ("GNK5")

@@ -1,5 +1,7 @@
-"""_lib's reader of include/gcnk.h without a GPU: the exact ctypes result on a synthetic header that holds every
-form the real one uses, the loud failures, and the real header against test_abi.py's own regex and the library."""
+"""_lib's reader of include/gcnk.h and the family headers it includes, without a GPU: the exact ctypes result on a
+synthetic header that holds every form the real ones use, the loud failures, an umbrella with a family header, and
+the real headers against test_abi.py's own regex and the library."""
+import collections
 import ctypes as C
 import os
 
@@ -83,6 +85,9 @@ def test_what_the_reader_cannot_take_whole_raises_and_names_it(line, named):
     with pytest.raises(RuntimeError, match=r"gcnk\.h") as e:
         _lib.parse_header(_with(line))
     assert named in str(e.value)
+    with pytest.raises(RuntimeError, match=r"^gcnk_family\.h: ") as e:      # the header at fault is the one named
+        _lib.parse_header(_with(line), "gcnk_family.h")
+    assert named in str(e.value)
 
 
 def test_text_outside_the_extern_block_and_a_missing_header_raise(tmp_path):
@@ -96,14 +101,75 @@ def test_text_outside_the_extern_block_and_a_missing_header_raise(tmp_path):
     assert missing in str(e.value)
 
 
+FAMILY = """\
+/* a family header in the same form; it may hold constants and structs of its own */
+#ifndef GCNK_FAMILY_H_
+#define GCNK_FAMILY_H_
+#include <stdint.h>
+#ifdef __cplusplus
+extern "C" {
+#endif
+#define GCNK_FAMILY_CHUNK 256
+typedef struct gcnk_f { int64_t n; } gcnk_f;
+int gcnk_family_run(const gcnk_f* f, void* stream);
+#ifdef __cplusplus
+}
+#endif
+#endif
+"""
+
+
+def _two_headers(tmp_path, family=FAMILY, include='#include "gcnk_family.h"   /* beside this file */'):
+    umbrella = tmp_path / "gcnk.h"
+    umbrella.write_text(SYNTHETIC.replace("int32_t gcnk_count(", "// #include \"gcnk_commented_out.h\"\n" + include
+                                          + "\nint32_t gcnk_count("))
+    if family is not None:
+        (tmp_path / "gcnk_family.h").write_text(family)
+    return str(umbrella)
+
+
+def test_an_umbrella_and_the_family_header_it_includes_are_one_binding(tmp_path):
+    paths, declared_in, sig, structs, const = _lib.read_headers(_two_headers(tmp_path))
+    assert paths == [str(tmp_path / "gcnk.h"), str(tmp_path / "gcnk_family.h")]
+    assert declared_in == {"gcnk_last_error": "gcnk.h", "gcnk_open": "gcnk.h", "gcnk_count": "gcnk.h",
+                           "gcnk_family_run": "gcnk_family.h"}
+    assert list(sig) == list(declared_in) and sig["gcnk_family_run"] == (C.c_int, [C.c_void_p, C.c_void_p])
+    assert list(structs) == ["gcnk_x", "gcnk_y", "gcnk_f"] and structs["gcnk_f"]._fields_ == [("n", C.c_int64)]
+    assert const == {"ABI_VERSION": 13, "EARG": -1, "EPI_BIAS": 1, "MASK": 16, "FAMILY_CHUNK": 256}
+
+
+@pytest.mark.parametrize("line, named", [("int gcnk_count(void);", "gcnk_count"),             # an entry point,
+                                         ("typedef struct gcnk_x { int n; } gcnk_x;", "gcnk_x"),   # a struct,
+                                         ("#define GCNK_MASK 0x10", "GCNK_MASK")])                # a constant
+def test_a_name_declared_in_two_headers_raises_and_names_both(tmp_path, line, named):
+    twice = FAMILY.replace("int gcnk_family_run(", line + "\nint gcnk_family_run(")
+    with pytest.raises(RuntimeError) as e:
+        _lib.read_headers(_two_headers(tmp_path, twice))
+    assert named in str(e.value) and "gcnk_family.h" in str(e.value) and "gcnk.h" in str(e.value).replace(
+        "gcnk_family.h", "")
+
+
+def test_a_named_include_that_does_not_exist_and_a_bad_family_header_raise(tmp_path):
+    with pytest.raises(RuntimeError, match="not found") as e:
+        _lib.read_headers(_two_headers(tmp_path, family=None))
+    assert str(tmp_path / "gcnk_family.h") in str(e.value)
+    with pytest.raises(RuntimeError, match=r"^gcnk_family\.h: .*size_t"):
+        _lib.read_headers(_two_headers(tmp_path, FAMILY.replace("void* stream", "size_t n")))
+
+
 def test_real_header_is_read_whole_and_the_public_names_are_its_structs():
-    sig, structs, const = _lib.read_header()
-    assert len(sig) == 84 and set(test_abi._declared_symbols()) == set(sig) == set(_lib.SIGNATURES)
+    paths, declared_in, sig, structs, const = _lib.read_headers()
+    assert [os.path.relpath(p, test_abi.ROOT) for p in paths] == [os.path.join("include", h) for h in (
+        "gcnk.h", "gcnk_topic_graph.h", "gcnk_lda.h", "gcnk_text.h")] and paths == _lib.HEADERS
+    assert collections.Counter(_lib.DECLARED_IN.values()) == {"gcnk.h": 68, "gcnk_topic_graph.h": 6, "gcnk_lda.h": 14,
+                                                              "gcnk_text.h": 7}
+    assert declared_in == _lib.DECLARED_IN and list(declared_in) == list(sig)
+    assert len(sig) == 95 and set(test_abi._declared_symbols()) == set(sig) == set(_lib.SIGNATURES)
     assert {k: C.sizeof(v) for k, v in structs.items()} == {
         "gcnk_plan_ref": 112, "gcnk_gcn_fwd": 536, "gcnk_gcn_bwd": 440, "gcnk_adam_tensor": 40, "gcnk_epoch_state": 32,
         "gcnk_keep_tensor": 24, "gcnk_keep_state": 16}
     assert len(const) == 41 and all(getattr(_lib, k) == v for k, v in const.items())
-    assert _lib.HEADER_PATH == os.path.join(test_abi.ROOT, "include", "gcnk.h")
+    assert _lib.HEADER_PATH == os.path.join(test_abi.ROOT, "include", "gcnk.h") == _lib.HEADERS[0]
     # the module's own tables are one reading of it, and every public struct name is the derived class itself
     assert const == _lib.CONSTANTS and sig == _lib.SIGNATURES
     S = _lib.STRUCTS

@@ -7,6 +7,8 @@ import torch
 import gcn_amd
 from graph_convolutional_networks_for_text_classification_amd import TopicInferencer, _lib, doc_term, topic_infer
 
+import abi_bound
+import lda_abi
 from lda_abi import PTR, assert_declared_exported_bound, call, header, kernels_source
 
 NAMES = {"gcnk_lda_max_topics": 0, "gcnk_lda_tile_words": 0, "gcnk_lda_docs_per_block": 0,
@@ -23,6 +25,10 @@ def test_symbols_declared_exported_and_bound():
     text = header()[0]
     assert "topic_model.py:133-164" in text and "gcnk_lda_" in text.split("#define GCNK_ABI_VERSION")[0]
     assert ESTEP in kernels_source()
+
+
+def test_gcnk_lda_h_declares_the_four_files_names_and_nothing_else():
+    assert abi_bound.declared_names("gcnk_lda.h") == lda_abi.all_names() and len(lda_abi.all_names()) == 14
 
 
 def test_constants_and_public_names():

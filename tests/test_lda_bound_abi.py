@@ -1,9 +1,7 @@
 """The variational bound's entry points without a GPU: gcnk_lda_bound_{docs,topics,finish}_f64 declared in
-include/gcnk_lda_bound.h (which include/gcnk.h includes), exported and bound within ABI 13, every refusal before any
+include/gcnk_lda.h (which include/gcnk.h includes), exported and bound within ABI 13, every refusal before any
 HIP call with its reason in gcnk_last_error, the public names, and the Python refusals that need no device."""
 import ctypes
-import os
-import re
 
 import pytest
 import torch
@@ -12,6 +10,7 @@ import gcn_amd
 from graph_convolutional_networks_for_text_classification_amd import TopicBound, _lib, fit_topics, topic_bound, topic_fit
 
 import abi_bound
+import lda_abi
 from lda_abi import PTR, _even_K, _K, _V, kernels_source
 
 DOCS, TOPICS, FINISH = "gcnk_lda_bound_docs_f64", "gcnk_lda_bound_topics_f64", "gcnk_lda_bound_finish_f64"
@@ -27,13 +26,7 @@ ENTRY = {
 
 
 def call(name, **kw):
-    """The entry point on its defaults with ``kw`` over them -> (return code, gcnk_last_error)."""
-    spec = ENTRY[name]
-    assert set(kw) <= {k for k, _ in spec}, (name, kw)
-    given = {k: kw.get(k, d) for k, d in spec if not callable(d)}
-    lib = _lib.load()
-    rc = getattr(lib, name)(*[kw[k] if k in kw else d(given) if callable(d) else d for k, d in spec], None)
-    return rc, lib.gcnk_last_error().decode()
+    return lda_abi.call(name, ENTRY, **kw)
 
 
 def _ids(kw):
@@ -41,24 +34,11 @@ def _ids(kw):
 
 
 def test_symbols_declared_exported_and_bound():
-    with open(_lib.LDA_BOUND_HEADER_PATH) as f:
-        text = f.read()
-    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    assert _lib.LDA_BOUND_HEADER_PATH == os.path.join(abi_bound.ROOT, "include", "gcnk_lda_bound.h")
-    assert '#include "gcnk_lda_bound.h"' in abi_bound.header()[1]        # a C caller of gcnk.h sees them
-    assert set(re.findall(r"\b(gcnk_[a-z0-9_]+)\s*\(", src)) == set(NAMES) == set(_lib.LDA_BOUND_SIGNATURES)
-    assert not set(NAMES) & set(_lib.SIGNATURES)
-    lib = _lib.load()
-    for name, nargs in NAMES.items():
-        decl = re.search(r"\b" + name + r"\s*\(([^)]*)\)", src)
-        assert decl and (nargs == 0 or len(decl.group(1).split(",")) == nargs), name
-        res, args = _lib.LDA_BOUND_SIGNATURES[name]
-        assert len(args) == nargs and (name not in ENTRY or len(ENTRY[name]) + 1 == nargs)
-        assert name in _lib.NEWER_THAN_SOME_VARIANTS
-        fn = getattr(lib, name)
-        assert fn.argtypes == args and fn.restype is res
-        assert res is (ctypes.c_int32 if nargs == 0 else ctypes.c_int)
-    assert lib.gcnk_abi_version() == _lib.ABI_VERSION == 13
+    text = abi_bound.header("gcnk_lda.h")[0]
+    assert '#include "gcnk_lda.h"' in abi_bound.header("gcnk.h")[1]        # a C caller of gcnk.h sees them
+    assert set(NAMES) <= abi_bound.declared_names("gcnk_lda.h")   # (test_lda_abi.py: the four files' are all of it)
+    lda_abi.assert_declared_exported_bound({k: v for k, v in NAMES.items() if v == 0}, ENTRY, ctypes.c_int32)
+    lda_abi.assert_declared_exported_bound({k: v for k, v in NAMES.items() if v != 0}, ENTRY, ctypes.c_int)
     assert "within ABI 13" in text and "_approx_bound" in text
     kernels = kernels_source()
     assert all(name in kernels for name in NAMES)

@@ -4,7 +4,6 @@ the public names, from_sklearn's refusal of every setting it does not restate, a
 check program under the host compiler's sanitizers (make table-sanitize; a CPU program of its own)."""
 import ctypes
 import os
-import re
 import shutil
 import subprocess
 import types
@@ -48,26 +47,14 @@ def _ids(kw):
 
 
 def test_symbols_declared_exported_and_bound():
-    with open(_lib.TEXT_HEADER_PATH) as f:
-        text = f.read()
-    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    assert _lib.TEXT_HEADER_PATH == os.path.join(abi_bound.ROOT, "include", "gcnk_text.h")
-    assert '#include "gcnk_text.h"' in abi_bound.header()[1]        # a C caller of gcnk.h sees them
-    assert set(re.findall(r"\b(gcnk_[a-z0-9_]+)\s*\(", src)) == set(NAMES) == set(_lib.TEXT_SIGNATURES)
-    assert not set(NAMES) & set(_lib.SIGNATURES) and not set(NAMES) & set(_lib.LDA_BOUND_SIGNATURES)
-    lib = _lib.load()
-    for name, nargs in NAMES.items():
-        decl = re.search(r"\b" + name + r"\s*\(([^)]*)\)", src)
-        assert decl and len(decl.group(1).split(",")) == nargs, name
-        res, args = _lib.TEXT_SIGNATURES[name]
-        assert len(args) == nargs and (name not in ENTRY or len(ENTRY[name]) + 1 == nargs)
-        assert name in _lib.NEWER_THAN_SOME_VARIANTS
-        fn = getattr(lib, name)
-        assert fn.argtypes == args and fn.restype is res
+    text = abi_bound.header("gcnk_text.h")[0]
+    assert '#include "gcnk_text.h"' in abi_bound.header("gcnk.h")[1]        # a C caller of gcnk.h sees them
+    assert abi_bound.declared_names("gcnk_text.h") == set(NAMES) and len(NAMES) == 7   # these and nothing else
+    abi_bound.assert_declared_exported_bound(NAMES, header="gcnk_text.h")
+    assert all(name not in ENTRY or len(ENTRY[name]) + 1 == nargs for name, nargs in NAMES.items())
     want = {"gcnk_text_table_slots": ctypes.c_int32, "gcnk_text_table_bytes": ctypes.c_int64,
             "gcnk_text_token_bound": ctypes.c_int64, "gcnk_text_workspace_bytes": ctypes.c_int64}
-    assert all(_lib.TEXT_SIGNATURES[n][0] is want.get(n, ctypes.c_int) for n in NAMES)
-    assert lib.gcnk_abi_version() == _lib.ABI_VERSION == 13
+    assert all(_lib.SIGNATURES[n][0] is want.get(n, ctypes.c_int) for n in NAMES)
     assert "within ABI 13" in text and "FNV-1a" in text and "CountVectorizer" in text
     with open(os.path.join(CSRC, "Makefile")) as f:
         make = f.read()

@@ -11,7 +11,7 @@ import gcn_amd
 from graph_convolutional_networks_for_text_classification_amd import _lib, factor, topic_graph
 
 import topic_graph_ref as ref
-from abi_bound import assert_declared_exported_bound, header
+from abi_bound import assert_declared_exported_bound, declared_names, header
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = {"gcnk_topic_graph_chunk": 0, "gcnk_topic_graph_max_topics": 0, "gcnk_topic_graph_nnz_bound": 3,
@@ -32,7 +32,8 @@ def _build(theta=PTR, theta_f32=0, ldt=None, sim=PTR, sim_f32=0, lds=None, D=300
 
 
 def test_symbols_declared_exported_and_bound():
-    assert_declared_exported_bound(NAMES)
+    assert_declared_exported_bound(NAMES, header="gcnk_topic_graph.h")
+    assert declared_names("gcnk_topic_graph.h") == set(NAMES) and len(NAMES) == 6   # these and nothing else
     text = header()[0]
     assert "build_graph.py:99-133" in text and "gcnk_topic_graph_" in text.split("#define GCNK_ABI_VERSION")[0]
     with open(os.path.join(ROOT, "graph-convolutional-networks-for-text-classification_amd", "csrc", "Makefile")) as f:
